@@ -10,6 +10,19 @@ update).  With N > 1 the driver starts one process per GPU (torch.distributed.ru
 contiguously and each step performs one RCCL all-reduce of the packed dual accumulators ("strong" scaling: total
 work is fixed).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, takes W untimed and K timed steps and prints the headline: `metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype` and the workload's `config`.  Everything else moves behind --full:
+
+    python bench.py --full [--no-side-lines] [--no-state-match] [--no-elbo-match] [--no-cpu-baseline] [--loop em]
+
+--full brackets every launch of the timed steps with HIP events (`kernels`, `roofline`, `step_roofline`; 0.05-0.1 ms per
+step) and adds the route gate, the other routes, the warm / hipGraph / skip-variance side lines, the ELBO after the steps,
+the oracle's parity checks (`elbo_match`, `state_match`), the CPU baseline and, with several ranks, the collective timings.
+
+--dump-outputs DIR writes, after the timed steps, the state their last step left -- what ``natgrad_step`` hands a caller
+(it returns None and updates the sites in place) -- as DIR/<name>.npy: lambda_1 [M, P] and lambda_2_sqrt [P, M, M]
+(t_SVGP_white: lambda_1 and lambda_2).  Inputs are seeded, so two builds run with the same arguments compare file for file.
+
 Workloads (BASELINE.json):
   ns  (default) north_star target / the metric's sizes: Gaussian regression N=1e6, M=1024, D=8, P=1, fp64
   c2  configs[1]: Gaussian regression N=1e6, M=512,  D=8,  fp64
@@ -47,6 +60,7 @@ WORKLOADS = {
 }
 PEAK_TFLOPS = {"f64": 78.6, "f32": 157.3}  # dense MFMA peaks (AMD datasheet; f32: MI355X_MICROARCH.md; f64 = f32/2)
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs stays below 64 MB in all (c5 / c5s: lambda_2_sqrt alone is 67 MB)
 
 
 def make_data(w, seed=0):
@@ -90,6 +104,28 @@ def make_kernel(mod, w):
         return mod.SeparateIndependent([mod.SquaredExponential(variance=var, lengthscales=float(l))
                                         for l in np.linspace(0.8, 1.5, w["P"])]), mod.SharedIndependentInducingVariables
     return mod.SquaredExponential(variance=var, lengthscales=w.get("lengthscales", 1.0)), (lambda Z: Z)
+
+
+def step_outputs(model, kind):
+    """The state the last step left, as host arrays: lambda_1 and the factor lambda_2_sqrt (t_SVGP) or lambda_2 (t_SVGP_white)."""
+    second = "lambda_2" if kind == "white" else "lambda_2_sqrt"
+    return {"lambda_1": model.lambda_1.numpy(), second: getattr(model, second).numpy()}
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array as DIR/<name>.npy in float32 / float64, at most `limit` bytes in all.  The budget goes to the
+    smallest arrays first; one that does not fit its share is written as DIR/<name>_sample.npy, a sample of its flattened
+    elements whose indices are drawn with a fixed seed and sorted, so the same shape gives the same sample in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = limit
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        keep = min(a.size, budget // (len(arrays) - i) // a.itemsize)
+        budget -= keep * a.itemsize
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+            name += "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _blas_info():
@@ -451,7 +487,16 @@ def main():
     ap.add_argument("--state-budget", type=float, default=250.0,
                     help="seconds the oracle's full-N E-step may take (projected from its first row block); beyond it the step "
                          "is skipped and elbo_match / the extrapolated cpu_baseline stand alone")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel HIP events inside the timed region, roofline, side lines, oracle "
+                         "parity and CPU baseline (the --no-* options and --loop refine it); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state their last step left as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.loop and not args.full:
+        ap.error("--loop is a side line of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # A plain `python bench.py --gpus N`: start one rank per GPU as a FRESH child process (torch.distributed.run), relay
@@ -496,7 +541,7 @@ def main():
             sys.exit(3)
 
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         # what the process group itself reports -- not what this script was asked for: the multi-GPU line proves by itself that
         # `world` ranks on `world` devices took part and which backend moved the bytes
         props = torch.cuda.get_device_properties(device)
@@ -568,16 +613,17 @@ def main():
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         replayed = bool(int(flag.item()))
     # The projection route ("auto": by cond(K_uu + jitter I)) is decided once per change of (theta, Z, jitter) and cached,
-    # so the timed steps below do not pay for it; its cost is measured here and reported as `route_gate_ms`.
+    # so the timed steps below do not pay for it; with --full its cost is measured here and reported as `route_gate_ms`.
     routes, conds, route_gate_ms = None, None, None
     if args.model == "tsvgp":
-        model._routes(1e-9)  # library handles, first-call allocations
-        model._cond_cache = None
-        torch.cuda.synchronize(device)
-        t0 = time.perf_counter()
-        routes = model._routes(1e-9)
-        torch.cuda.synchronize(device)
-        route_gate_ms = (time.perf_counter() - t0) * 1e3
+        routes = model._routes(1e-9)  # library handles, first-call allocations
+        if args.full:
+            model._cond_cache = None
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            routes = model._routes(1e-9)
+            torch.cuda.synchronize(device)
+            route_gate_ms = (time.perf_counter() - t0) * 1e3
         conds = [float(c) for c in model._cond_cache[1]] if model._cond_cache is not None else None
     n_warm = max(args.warmup, 3 if replayed else 0)  # a graph is captured on the second occurrence of a step
     # Housekeeping that takes the host tens of milliseconds -- the full garbage collection of `timed_region`, the pool of timing
@@ -585,27 +631,64 @@ def main():
     # (profiles/r05_clock_lab.txt), and a 40 ms pause there made the first timed step 2.3 ms slower than the others.  The timed
     # region itself is unchanged: W untimed steps, barrier + synchronize, K steps, barrier + synchronize.
     gc.collect()
-    if not replayed and hasattr(eng, "reserve_events"):
+    if args.full and not replayed and hasattr(eng, "reserve_events"):
         eng.reserve_events(2 * 8 * args.steps * max(1, w["P"] if w.get("separate") else 1) + 64)
-    if world > 1:
+    if args.full and world > 1:
         pkg.distributed.reserve_timing(8 * args.steps + 16)
     for _ in range(n_warm):
         model.natgrad_step((Xd, Yd), lr=0.8)
     barrier()
-    # Every C-ABI launch inside the timed region is bracketed with HIP events on its launch stream (pooled: no event is
-    # created inside the region); they cost 0.05-0.1 ms per step (A/B with the collector paused: 11.38 vs 11.44 ms at
-    # M = 512, 37.14 vs 37.14-37.4 ms at the headline size).
-    eng.profile = None if replayed else {}
+    # With --full every C-ABI launch inside the timed region is bracketed with HIP events on its launch stream (pooled: no
+    # event is created inside the region); they cost 0.05-0.1 ms per step (A/B with the collector paused: 11.38 vs 11.44 ms
+    # at M = 512, 37.14 vs 37.14-37.4 ms at the headline size).  A plain run takes no events: the same launches, unbracketed.
     D_ = pkg.distributed
-    if world > 1:
-        D_.TIMING = []  # HIP events around every collective of the timed steps (pooled; replayed steps take them too: the
-        #                 all-reduce sits BETWEEN the two graphs of a step)
+    if args.full:
+        eng.profile = None if replayed else {}
+        if world > 1:
+            D_.TIMING = []  # HIP events around every collective of the timed steps (pooled; replayed steps take them too:
+            #                 the all-reduce sits BETWEEN the two graphs of a step)
     with timed_region(collected=True):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             model.natgrad_step((Xd, Yd), lr=0.8)
         barrier()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the state is replicated over the ranks
+        dump_outputs(args.dump_outputs, step_outputs(model, args.model))
+    t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    elapsed = float(t)
+
+    def headline():
+        """The result line's headline fields.  Computed on EVERY rank: _routes() may issue a broadcast when its cache misses,
+        and a collective only rank 0 enters (the others already wait in the closing barrier) would hang the job."""
+        split_on = bool(world > 1 and getattr(model, "_latent_split", None) is not None
+                        and model._latent_split(model._routes(1e-9)))
+        return {
+            "metric": "natgrad E-steps/sec", "value": round(args.steps / elapsed, 4), "unit": "E-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": w["dtype"],
+            "data": "synthetic",
+            "config": {"workload": w["name"], "N": w["N"], "M": w["M"], "D": w["D"], "P": w["P"],
+                       "likelihood": w["lik"], "rows_per_gpu": rows, "parallelism": (f"N-sharded x{world}, M x M work of the latents split over the ranks (all-gather of operands, "
+                                       f"reduce-scatter of the sums, all-gather of the state)"
+                                       if split_on else f"N-sharded x{world}, 1 all-reduce/step"),
+                       "e_step": "cold (K_uu, K_uf, Choleskys, whitening rebuilt every step; the projection-route decision "
+                                 "is cached per (theta, Z, jitter): see route_gate_ms with --full)", "lr": 0.8,
+                       "projection": getattr(model, "projection", None), "routes": routes,
+                       "cond_Kuu_plus_jitter": conds},
+        }
+
+    if not args.full:
+        out = headline()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     coll_times = None
     if world > 1:
         coll_times, D_.TIMING = D_.timing_summary(D_.TIMING, args.steps), None
@@ -628,10 +711,6 @@ def main():
         eng.profile = None
         model.use_graph = "auto"
 
-    t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed = float(t)
     elbo = float(model.elbo((Xd, Yd)))
     steps_before_elbo = n_warm + args.steps + ((2 + args.steps) if replayed else 0)
 
@@ -789,10 +868,7 @@ def main():
         for n, (p_, _) in tr.trainable_parameters(model).items():
             p_.assign(saved[2][n])
 
-    # the label of config.parallelism is computed on EVERY rank: _routes() may issue a broadcast when its cache misses, and a
-    # collective only rank 0 enters (the others already wait in the closing barrier) would hang the job
-    split_on = bool(world > 1 and getattr(model, "_latent_split", None) is not None
-                    and model._latent_split(model._routes(1e-9)))
+    out = headline()  # on every rank (see there)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         flops = kernel_flops(w, rows, batched=getattr(eng, "last_batched", False) or not w.get("separate"),
@@ -836,19 +912,7 @@ def main():
                 e["gbs"] = round(byts[k] / (ms * 1e-3) / 1e9, 1)
                 e["hbm_frac"] = round(e["gbs"] / HBM_PEAK_GBS, 4)
             kernels[k] = e
-        out = {
-            "metric": "natgrad E-steps/sec", "value": round(args.steps / elapsed, 4), "unit": "E-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": w["dtype"],
-            "data": "synthetic",
-            "config": {"workload": w["name"], "N": w["N"], "M": w["M"], "D": w["D"], "P": w["P"],
-                       "likelihood": w["lik"], "rows_per_gpu": rows, "parallelism": (f"N-sharded x{world}, M x M work of the latents split over the ranks (all-gather of operands, "
-                                       f"reduce-scatter of the sums, all-gather of the state)"
-                                       if split_on else f"N-sharded x{world}, 1 all-reduce/step"),
-                       "e_step": "cold (K_uu, K_uf, Choleskys, whitening rebuilt every step; the projection-route decision "
-                                 "is cached per (theta, Z, jitter): see route_gate_ms)", "lr": 0.8,
-                       "projection": getattr(model, "projection", None), "routes": routes,
-                       "cond_Kuu_plus_jitter": conds},
+        out.update({
             "route_gate_ms": None if route_gate_ms is None else round(route_gate_ms, 3),
             "other_routes": forced,
             "elbo_after_steps": elbo, "steps_before_elbo": steps_before_elbo,
@@ -867,7 +931,7 @@ def main():
                               ("in an EAGER pass of the same steps right behind the timed region (the headline replays the step "
                                "from a captured hipGraph, which takes no events)" if replayed else "inside the timed region") +
                               "; the cyclic garbage collector is paused inside timed loops (as timeit does)"),
-        }
+        })
         # The parity half of the metric and the CPU baseline ride on every line, also with N > 1 ranks: the oracle runs on
         # rank 0's host cores while the other ranks wait in the closing barrier.  (torch.distributed.run exports
         # OMP_NUM_THREADS=1 to its children unless told otherwise: the BLAS pool is widened to the box's cores here.)

@@ -28,7 +28,7 @@ elif [ "$mode" = run ]; then
   out=gpurun_out/ab/ab.txt; mkdir -p gpurun_out/ab; : > $out
   for lib in "$@"; do TSVGP_HIP_LIB=$PWD/$lib python tools/fill_alone.py 2>/dev/null >> $out; done
   for rep in $(seq 1 ${REPS:-2}); do for lib in "$@"; do for n in "${rows[@]}"; do
-    TSVGP_HIP_LIB=$PWD/$lib python bench.py --rows $n --steps ${STEPS:-20} --no-elbo-match --no-side-lines --cpu-budget 0 2>/dev/null | python -c "
+    TSVGP_HIP_LIB=$PWD/$lib python bench.py --full --rows $n --steps ${STEPS:-20} --no-elbo-match --no-side-lines --cpu-budget 0 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = d['kernels']
 print('$lib', $n, 'ms/step', d['ms_per_step'], *[f'{a} {k[b][\"avg_ms\"]}' for a, b in (('potrf', 'tsvgp_potrf'), ('moments', 'tsvgp_moments'), ('site_accum', 'tsvgp_site_accum'), ('fill', 'tsvgp_se_fill')) if b in k])" >> $out

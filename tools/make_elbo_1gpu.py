@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/elbo_1gpu.json from ONE-GPU bench lines (bench.py --gpus 1) measured on MI355X: the reference value of
+"""profiles/elbo_1gpu.json from ONE-GPU bench lines (bench.py --gpus 1 --full) measured on MI355X: the reference value of
 `elbo_vs_1gpu` in multi-rank bench lines.
 
     python tools/make_elbo_1gpu.py profiles/r03_*_bench.json [...]

@@ -3,7 +3,7 @@
 # default, alternating on ONE box.  usage: bash tools/run_ab_headline_r5.sh [out dir] [workload] [rows]
 R=$PWD; O=${1:-gpurun_out/r5g}; W=${2:-ns}; ROWS=${3:-1000000}; mkdir -p $O; : > $O/ab_$W.txt
 line() {
-  python bench.py --workload $W --rows $ROWS --steps 20 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$1_$W.json
+  python bench.py --full --workload $W --rows $ROWS --steps 20 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$1_$W.json
   python -c "
 import json
 d = json.loads([l for l in open('$O/line_$1_$W.json').read().splitlines() if l.startswith('{')][-1]); k = d['kernels']

@@ -6,7 +6,7 @@
 # usage (on the box): bash tools/run_chain_ab_r4.sh [out dir]
 R=$PWD; O=${1:-gpurun_out/r4g}; mkdir -p $O; : > $O/chain_ab.txt
 line() {  # workload rows steps tag
-  python bench.py --workload $1 --rows $2 --steps $3 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null | python -c "
+  python bench.py --full --workload $1 --rows $2 --steps $3 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); k = d['kernels']
 print('$4', '$1', $2, 'ms/step', d['ms_per_step'], 'hipgraph' if d.get('hipgraph') and d['hipgraph'].get('headline_mode') == 'hipGraph replay' else 'eager',
@@ -23,7 +23,7 @@ cat $O/chain_ab.txt
 cd /tmp && export TMPDIR=/tmp
 for spec in "ns 125000" "c3 125000" "ns 1000000"; do
   set -- $spec
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt_$1_$2 -- python3 $R/bench.py --workload $1 --rows $2 --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt_$1_$2.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt_$1_$2 -- python3 $R/bench.py --full --workload $1 --rows $2 --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt_$1_$2.log 2>&1
   f=$(find $R/$O/kt_$1_$2 -name "*kernel_trace.csv" | head -1)
   python3 $R/tools/mxm_timeline.py $f 4 --list > $R/$O/mxm_timeline_$1_rows$2.txt 2>&1 || true
   find $R/$O/kt_$1_$2 -name "*kernel_trace.csv" -delete

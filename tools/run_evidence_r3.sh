@@ -7,14 +7,14 @@ R=$PWD; O=gpurun_out/r3i; mkdir -p $O
 what=${1:-all}
 if [ "$what" = trace ] || [ "$what" = all ]; then
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines > $R/$O/kt.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines > $R/$O/kt.log 2>&1
   cd $R
   f=$(find $O/kt -name "*kernel_trace.csv" | head -1)
   python tools/mxm_timeline.py $f 4 --list > $O/mxm_timeline.txt 2>&1 || true
   python tools/trace_vs_events.py $f $O/kt.log > $O/trace_vs_events.txt 2>&1 || true
   find $O/kt -name "*kernel_trace.csv" -delete
   cd /tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt125 -- python3 $R/bench.py --rows 125000 --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines > $R/$O/kt125.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt125 -- python3 $R/bench.py --full --rows 125000 --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines > $R/$O/kt125.log 2>&1
   cd $R
   f=$(find $O/kt125 -name "*kernel_trace.csv" | head -1)
   python tools/mxm_timeline.py $f 4 --list > $O/mxm_timeline_125k.txt 2>&1 || true

@@ -7,7 +7,7 @@ R=$PWD; O=${2:-gpurun_out/r4k}; V=${3:-v1}; mkdir -p $O
 what=${1:-all}
 if [ "$what" = trace ] || [ "$what" = all ]; then
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt.log 2>&1
   cd $R
   f=$(find $O/kt -name "*kernel_trace.csv" | head -1)
   python tools/trace_vs_events.py $f $O/kt.log > $O/trace_vs_events.txt 2>&1 || true

@@ -4,7 +4,7 @@
 R=$PWD; O=${1:-gpurun_out/r5j}; W=${2:-ns}; mkdir -p $O; : > $O/fill_rows_$W.txt
 for rep in 1 2; do
   for rb in 64 32 16 8; do
-    TSVGP_FILL_ROWS_BLK=$rb python bench.py --workload $W --steps 20 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$W_$rb.json
+    TSVGP_FILL_ROWS_BLK=$rb python bench.py --full --workload $W --steps 20 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$W_$rb.json
     python -c "
 import json
 d = json.loads([l for l in open('$O/line_$W_$rb.json').read().splitlines() if l.startswith('{')][-1]); k = d['kernels']

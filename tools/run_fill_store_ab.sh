@@ -3,7 +3,7 @@
 # (nt), alternating on ONE box: the fill alone, then bench lines.   usage (on the box): bash tools/run_fill_store_ab.sh [out dir]
 O=${1:-gpurun_out/r6d}; mkdir -p $O; : > $O/fill_store_ab.txt
 line() {  # workload rows steps tag
-  python bench.py --workload $1 --rows $2 --steps $3 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$4_$1_$2.json
+  python bench.py --full --workload $1 --rows $2 --steps $3 --no-elbo-match --no-cpu-baseline --no-side-lines --no-state-match 2>/dev/null > $O/line_$4_$1_$2.json
   python -c "
 import json
 d = json.loads([l for l in open('$O/line_$4_$1_$2.json').read().splitlines() if l.startswith('{')][-1]); k = d['kernels']

@@ -3,7 +3,7 @@
 R=$PWD; O=${1:-gpurun_out/r5u}; W=${2:-ns}; ROWS=${3:-125000}; shift 3; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 leg() {  # tag
-  rocprofv3 --kernel-trace --output-format csv -d $R/$O/kt_$1 -- python3 $R/bench.py --workload $W --rows $ROWS --steps 30 --warmup 5 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt_$1.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d $R/$O/kt_$1 -- python3 $R/bench.py --full --workload $W --rows $ROWS --steps 30 --warmup 5 --no-cpu-baseline --no-elbo-match --no-side-lines --no-state-match > $R/$O/kt_$1.log 2>&1
   f=$(find $R/$O/kt_$1 -name "*kernel_trace.csv" | head -1)
   echo "== $1 ($W, $ROWS rows) ==" >> $R/$O/keeper_trace.txt
   grep -h '^{' $R/$O/kt_$1.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read().splitlines()[-1]); print('bench line under the tracer: ms/step', d['ms_per_step'])" >> $R/$O/keeper_trace.txt

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Do the HIP-event kernel times that bench.py prints agree with the rocprofv3 kernel trace of the SAME run?
+"""Do the HIP-event kernel times that bench.py --full prints agree with the rocprofv3 kernel trace of the SAME run?
 usage: trace_vs_events.py <kernel_trace.csv> <bench stdout (the JSON line is its last line starting with '{')>"""
 import csv, json, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
