@@ -48,6 +48,8 @@ extern "C" {
 #define TSVGP_LIK_NONE 0      /* moments only (predict_f) */
 #define TSVGP_LIK_GAUSSIAN 1  /* gpflow.likelihoods.Gaussian: closed form */
 #define TSVGP_LIK_BERNOULLI 2 /* gpflow.likelihoods.Bernoulli, probit + 1e-3 jitter, 20-pt Gauss-Hermite */
+#define TSVGP_LIK_HETERO 3    /* gpflow.likelihoods.HeteroskedasticTFPConditional (Normal, Exp scale) over TWO coupled latents:
+                                 tsvgp_lik_map_hetero_* only (the moments kernels and tsvgp_lik_map_* reject it) */
 #define TSVGP_LIK_NOCROP 0x100 /* OR-ed into the selector: leave g1 = d ve/d var uncropped (reference
                                   src/models/tsvgp_white.py:188-191 has no crop; src/models/tsvgp.py:262-263 has) */
 #define TSVGP_LIK_MEANONLY 0x200 /* OR-ed into the selector (NONE or GAUSSIAN only): skip the variance product.  Under a
@@ -68,7 +70,7 @@ const char *tsvgp_version(void);
 /* Number of this header's calling conventions: bumped whenever an entry point's argument list changes without a new symbol
  * name.  A binding checks it against the TSVGP_ABI_VERSION it was written for before the first call (t-svgp_amd/_backend.py
  * refuses a library whose number differs: a shifted argument would otherwise hand a kernel a garbage stream or pointer). */
-#define TSVGP_ABI_VERSION 4
+#define TSVGP_ABI_VERSION 5
 int tsvgp_abi_version(void);
 
 /* Upper bound on the number of workgroup slots the site-accumulation kernel can keep resident
@@ -186,6 +188,18 @@ int tsvgp_lik_map_f64(const double *mean, const double *var, const double *Y, in
                       double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, int P, void *stream);
 int tsvgp_lik_map_f32(const float *mean, const float *var, const float *Y, int lik, double lik_param, float *g0, float *g1,
                       double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, int P, void *stream);
+
+/* (4b) The heteroskedastic Gaussian likelihood map (reference docs/notebooks/heteroskedastic.py:58-76: gpflow
+ *     HeteroskedasticTFPConditional [ext] with a Normal distribution and an Exp scale; 20 x 20 Gauss-Hermite grid): the first
+ *     likelihood whose row couples two latents, log p(y | f0, f1) = log N(y | f0, exp(f1)^2), so it cannot run in the per-latent
+ *     epilogue of the moments kernels.  mean, var [N x 2] (latent 0: location, latent 1: log scale), Y [N x 1] ->
+ *     g0 = d ve / d mean, g1 = d ve / d var [Np x 2] of the quadrature sum (rows >= N zero; g1 cropped at -1e-8 unless
+ *     TSVGP_LIK_NOCROP), ve_partial [Np / 128] (fp64 per-128-row sums of ve), nonpos_partial [Np / 128] (count of var <= 0 over
+ *     both latents).  flags = TSVGP_LIK_HETERO, optionally | TSVGP_LIK_NOCROP.  Arithmetic in fp64 for either array type. */
+int tsvgp_lik_map_hetero_f64(const double *mean, const double *var, const double *Y, int flags, double *g0, double *g1,
+                             double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+int tsvgp_lik_map_hetero_f32(const float *mean, const float *var, const float *Y, int flags, float *g0, float *g1,
+                             double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
 /* (3b) The moments for P latents with one kernel each: latent p has its own operand A + p*strideA ([Np x Mp] each; strideA = 0
  *     is the shared operand of tsvgp_moments_*) and its own prior variance kdiag_host[p] (HOST array of P doubles, passed

@@ -25,6 +25,7 @@ SOURCE_FLAGS = {"tsvgp_chol.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 TILE = 128
 MAX_BATCH = 32  # TSVGP_MAX_BATCH: latents per launch of the *_batched entry points
 LIK_NONE, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
+LIK_HETERO = 3  # two coupled latents: tsvgp_lik_map_hetero_* only
 LIK_NOCROP = 0x100
 LIK_MEANONLY = 0x200
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 2, 3
@@ -34,7 +35,7 @@ POTRF_RHS_UPPER = 2  # TSVGP_POTRF_RHS_UPPER
 POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
 POTRF_DIAG_V2 = 8  # TSVGP_POTRF_DIAG_V2
 POTRF_FUSE = 16  # TSVGP_POTRF_FUSE
-ABI_VERSION = 4  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
+ABI_VERSION = 5  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
 
 _lib = None
 
@@ -126,6 +127,10 @@ _PROTOTYPES = {
                                   c_int, c_void_p]),
     "tsvgp_lik_map_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                   c_int, c_void_p]),
+    "tsvgp_lik_map_hetero_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                         c_void_p]),
+    "tsvgp_lik_map_hetero_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                         c_void_p]),
     "tsvgp_site_accum_work_bytes_f64": (c_int64, [c_int, c_int, c_int]),
     "tsvgp_site_accum_work_bytes_f32": (c_int64, [c_int, c_int, c_int]),
     "tsvgp_site_accum_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),

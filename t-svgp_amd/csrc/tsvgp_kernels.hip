@@ -1897,6 +1897,79 @@ __global__ __launch_bounds__(NTHREADS) void lik_map_kernel(const T* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// lik_map_hetero_kernel: the heteroskedastic Gaussian likelihood (gpflow HeteroskedasticTFPConditional with a Normal and an
+// Exp scale [ext]; reference docs/notebooks/heteroskedastic.py:58-76), the first map that couples two latents:
+//     log p(y | f0, f1) = -1/2 log 2 pi - f1 - 1/2 (y - f0)^2 exp(-2 f1),
+// its variational expectation by the 20 x 20 product Gauss-Hermite grid and the derivative OF THAT SUM with respect to
+// (mean, var) of each latent.  The grid sum separates (S0 = sum_i w_i (y - f0_i)^2, S1 = sum_j w_j exp(-2 f1_j),
+// W0 = sum_i w_i, Q2 = sum_i w_i z_i^2; the odd sums vanish node pair by node pair):
+//     ve = -1/2 log 2 pi W0^2 - W0^2 m1 - 1/2 S0 S1,   S0 = W0 r^2 + Q2 v0,   r = y - m0
+//     d/dm0 = W0 r S1,   d/dv0 = -1/2 Q2 S1,   d/dm1 = S0 S1 - W0^2,   d/dv1 = S0 T1 / (2 s1),  T1 = sum_j w_j z_j e^(-2 f1_j)
+// so a row needs 20 exponentials, not 400.  fp64 arithmetic for either array type: exp(-2 f1) at f1 = m1 - 7.6 s1 leaves the
+// fp32 range at moderate variances, and the map is bandwidth-trivial.  One thread per row, one workgroup per 128 rows.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(TILE) void lik_map_hetero_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                              const T* __restrict__ Y, int flags, T* __restrict__ g0o,
+                                                              T* __restrict__ g1o, double* __restrict__ ve_partial,
+                                                              int32_t* __restrict__ nonpos_partial, int64_t N) {
+    __shared__ double red[TILE / 64];
+    __shared__ int redi[TILE / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n = (int64_t)blockIdx.x * TILE + t;
+    const bool live = n < N;
+    double d0m = 0.0, d0v = 0.0, d1m = 0.0, d1v = 0.0, ve = 0.0;
+    int nonpos = 0;
+    if (live) {
+        const double m0 = (double)mean[2 * n], m1 = (double)mean[2 * n + 1];
+        const double v0 = (double)var[2 * n], v1 = (double)var[2 * n + 1];
+        const double r = (double)Y[n] - m0;
+        const double s1 = sqrt(v1);
+        double W0 = 0.0, Q2 = 0.0, S1 = 0.0, T1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {  // node pairs +-z
+            const double z = GH_X[i], wi = GH_W[i];
+            const double ep = exp(-2.0 * (m1 + s1 * z)), em = exp(-2.0 * (m1 - s1 * z));
+            W0 += 2.0 * wi;
+            Q2 += 2.0 * wi * z * z;
+            S1 += wi * (ep + em);
+            T1 += wi * z * (ep - em);
+        }
+        const double S0 = W0 * r * r + Q2 * v0;
+        ve = -0.5 * 1.83787706640934548356 * W0 * W0 - W0 * W0 * m1 - 0.5 * S0 * S1;
+        d0m = W0 * r * S1;
+        d0v = -0.5 * Q2 * S1;
+        d1m = S0 * S1 - W0 * W0;
+        d1v = S0 * T1 / (2.0 * s1);
+        if (!(flags & TSVGP_LIK_NOCROP)) {  // reference tsvgp.py:262-263
+            d0v = fmin(d0v, -1e-8);
+            d1v = fmin(d1v, -1e-8);
+        }
+        nonpos = (v0 > 0.0 ? 0 : 1) + (v1 > 0.0 ? 0 : 1);
+    }
+    g0o[2 * n] = (T)d0m;  // rows >= N of the [Np x 2] outputs: zeros
+    g0o[2 * n + 1] = (T)d1m;
+    g1o[2 * n] = (T)d0v;
+    g1o[2 * n + 1] = (T)d1v;
+    double s = ve;
+    int c = nonpos;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        c += __shfl_xor(c, o);
+    }
+    if (lane == 0) {
+        red[w] = s;
+        redi[w] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = red[0] + red[1];
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // mean_lik_kernel (TSVGP_LIK_MEANONLY): mean[n, p] = sum_j A[n, j] * gamma[j, p] and, for the Gaussian likelihood,
 // g0 = (y - mean) / s2, g1 = -1 / (2 s2) -- neither depends on the predictive variance.  HBM bound: one sweep of A.
 // One workgroup per 128-row panel (same grid as panel_kernel, so the per-workgroup partial buffers keep their
@@ -4206,6 +4279,16 @@ int lik_map(const T* mean, const T* var, const T* Y, int lik, double lik_param, 
     return launch_status();
 }
 
+template <typename T>
+int lik_map_hetero(const T* mean, const T* var, const T* Y, int flags, T* g0, T* g1, double* ve_partial, int32_t* nonpos_partial,
+                   int64_t N, int64_t Np, void* stream) {
+    if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
+    if ((flags & ~TSVGP_LIK_NOCROP) != TSVGP_LIK_HETERO) return TSVGP_EINVAL;
+    hipLaunchKernelGGL(lik_map_hetero_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(TILE), 0, (hipStream_t)stream, mean, var, Y, flags,
+                       g0, g1, ve_partial, nonpos_partial, N);
+    return launch_status();
+}
+
 // kdiag: HOST array of P values (one kernel variance per latent), or of ONE value with kdiag_uniform (a shared kernel, any P).
 template <typename T>
 int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y, const double* kdiag, bool kdiag_uniform,
@@ -4597,6 +4680,14 @@ int tsvgp_lik_map_f64(const double* mean, const double* var, const double* Y, in
 int tsvgp_lik_map_f32(const float* mean, const float* var, const float* Y, int lik, double lik_param, float* g0, float* g1,
                       double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, int P, void* stream) {
     return lik_map<float>(mean, var, Y, lik, lik_param, g0, g1, ve_partial, nonpos_partial, N, Np, P, stream);
+}
+int tsvgp_lik_map_hetero_f64(const double* mean, const double* var, const double* Y, int flags, double* g0, double* g1,
+                             double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_hetero<double>(mean, var, Y, flags, g0, g1, ve_partial, nonpos_partial, N, Np, stream);
+}
+int tsvgp_lik_map_hetero_f32(const float* mean, const float* var, const float* Y, int flags, float* g0, float* g1,
+                             double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_hetero<float>(mean, var, Y, flags, g0, g1, ve_partial, nonpos_partial, N, Np, stream);
 }
 int tsvgp_moments_f64(const double* A, const double* Tm, const double* gamma, const double* Y, double kdiag, int lik,
                       double lik_param, double* mean, double* var, double* g0, double* g1, double* ve_partial,

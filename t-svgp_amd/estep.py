@@ -15,6 +15,10 @@ Kernel sequence of ``run(..., sites=True)`` by projection route (models/tsvgp.py
     whitened:   fill -> trmm(UPPER) -> moments(UPPER, on B) -> site_accum(B)
     projected:  fill -> trmm(UPPER) -> moments(UPPER, on B) -> trmm(LOWER) -> site_accum(a)
 ``mean_only`` replaces the moments product by one HBM-bound sweep (Gaussian likelihood, TSVGP_LIK_MEANONLY).
+A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, Y [N x 1]) cannot run in the moments kernels'
+per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then ``tsvgp_lik_map_hetero``
+on them, then the site sums of the route -- ``run`` with P = 2 on one kernel, ``_run_batched`` on separate kernels, and
+a two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).
 """
 from __future__ import annotations
 
@@ -546,6 +550,32 @@ class EStepEngine:
                                                                       mode, self._stream()))
         return C
 
+    def _coupled_map(self, mean, var, Y, lik_id, N, Np):
+        """g0, g1 [Np, 2] (rows >= N zero), ve_partial, nonpos_partial of the coupled likelihood map (``tsvgp_lik_map_hetero_*``)
+        on mean, var [N, 2] and Y [N, 1] in the compute dtype.  The outputs are cached buffers of their own: the site sums read
+        them where they are, and a one-latent pass of the same call (``site_grads``) does not overwrite them."""
+        T = self.dtype
+        nblk = Np // B.TILE
+        g0, g1 = self._get("het_g0", (Np, 2), T), self._get("het_g1", (Np, 2), T)
+        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
+        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_lik_map_hetero", lambda: self._fn("tsvgp_lik_map_hetero")(
+                mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(),
+                nonpos_partial.data_ptr(), N, Np, self._stream()))
+        return g0, g1, ve_partial, nonpos_partial
+
+    @staticmethod
+    def _check_y(Y, N, P, lik_id):
+        """Y [N, P]; a coupled likelihood (LIK_HETERO) maps two latents onto ONE target column: Y [N, 1], P = 2."""
+        if (lik_id & 0xFF) == B.LIK_HETERO:
+            if P != 2 or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
+                raise ValueError(f"the heteroskedastic likelihood needs 2 latent GPs and Y [N, 1] = [{N}, 1], got P = {P} and "
+                                 f"Y {None if Y is None else tuple(Y.shape)}")
+            return
+        if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:
+            raise ValueError(f"Y must be [N, P] = [{N}, {P}], got {tuple(Y.shape)}")
+
     def kernel_grad(self, X, Z, kernel, U, g0, g1, beta):
         """N-sized part of d ELBO / d (variance, lengthscales, Z) for ONE latent GP (``tsvgp_kernel_grad_*``):
         sum_{n,m} V[n,m] dK[n,m]/d theta with V = g0 beta^T - 2 g1 * U.  X [N, D], Z [M, D], U [Np, Mp] (compute dtype);
@@ -692,6 +722,7 @@ class EStepEngine:
         N, M, P = X.shape[0], Z.shape[0], moment_Tm.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         need_g = lik_id != B.LIK_NONE
+        coupled = (lik_id & 0xFF) == B.LIK_HETERO
         if need_g:
             Y = Y.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -730,20 +761,33 @@ class EStepEngine:
         nblk = Np // B.TILE
         ve_partial = self._get("ve_partial", (nblk,), torch.float64)
         nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
-        g0 = self._get("g0", (Np, P), T) if need_g else None
-        g1 = self._get("g1", (Np, P), T) if need_g else None
-        mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
-        var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
-        lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
         kdiag = (ctypes.c_double * P)(*[k.variance.item() for k in kernel.kernels])
-        with torch.cuda.device(dev):
-            self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
-                KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, kdiag, lik_flags,
-                float(lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
-                nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
+        if coupled:
+            if mean_only:
+                raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
+            # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
+            mean, var = self._get("het_mean", (N, P), T), self._get("het_var", (N, P), T)
+            with torch.cuda.device(dev):
+                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
+                    KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), None, kdiag, B.LIK_NONE, 0.0, mean.data_ptr(),
+                    var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
+                    self._stream()))
+            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np)
+        else:
+            g0 = self._get("g0", (Np, P), T) if need_g else None
+            g1 = self._get("g1", (Np, P), T) if need_g else None
+            mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
+            var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
+            lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
+            with torch.cuda.device(dev):
+                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
+                    KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, kdiag, lik_flags,
+                    float(lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
+                    nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
         stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
-        if want_moments:
-            stats.mean, stats.var = mean.to(torch.float64), (None if var is None else var.to(torch.float64))
+        if want_moments:  # (the coupled path's mean / var are cached buffers: copies)
+            stats.mean = mean.to(torch.float64, copy=coupled)
+            stats.var = None if var is None else var.to(torch.float64, copy=coupled)
         if want_grads and need_g:
             stats.g0, stats.g1 = g0[:N].to(torch.float64), g1[:N].to(torch.float64)
         if sites:
@@ -771,8 +815,10 @@ class EStepEngine:
         P = moment_Tm.shape[0]
         if len(kernel.kernels) != P:
             raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
-        if Y is not None and (Y.dim() != 2 or Y.shape[1] != P):
-            raise ValueError(f"Y must be [N, P] = [{X.shape[0]}, {P}], got {tuple(Y.shape)}")
+        lik_id = kw.get("lik_id", B.LIK_NONE)
+        coupled = (lik_id & 0xFF) == B.LIK_HETERO
+        if coupled or Y is not None:
+            self._check_y(Y, X.shape[0], P, lik_id)
         if X.shape[0] > 0:
             if prefill is not None and "KfuP" in prefill:  # the batched fill is already under way (start_fill)
                 whitened = [p for p in range(P) if self._per_latent(whiten_T, p) is not None]
@@ -787,6 +833,9 @@ class EStepEngine:
                                          want_moments=kw.get("want_moments", False), want_grads=want_grads,
                                          mean_only=kw.get("mean_only", False), prefill=prefill)
         self.last_batched = False
+        if coupled and X.shape[0] > 0:  # (an empty shard contributes zeros through the loop below)
+            return self._run_separate_coupled(X, Y, Z, kernel, moment_Tm=moment_Tm, gamma=gamma, whiten_T=whiten_T,
+                                              project_T=project_T, want_grads=want_grads, **kw)
         parts = []
         for p, kp in enumerate(kernel.kernels):
             if isinstance(whiten_T, (list, tuple)):  # per-latent routes: None = this latent works on K_fu directly
@@ -808,6 +857,45 @@ class EStepEngine:
         out = EStepStats(n_rows=parts[0].n_rows, ve_sum=sum(s.ve_sum for s in parts), nonpos=sum(s.nonpos for s in parts))
         out.mean, out.var, out.g0, out.g1 = cat("mean", 1), cat("var", 1), cat("g0", 1), cat("g1", 1)
         out.acc2, out.acc1 = cat("acc2", 0), cat("acc1", 0)
+        return out
+
+    def _run_separate_coupled(self, X, Y, Z, kernel, *, moment_Tm, gamma, whiten_T, project_T, want_grads, lik_id, sites=False,
+                              want_moments=False, mean_only=False, **kw) -> EStepStats:
+        """The one-pass-per-latent path under a likelihood that couples the latents (``LIK_HETERO``): the map needs the moments
+        of BOTH latents before any site sum, and this path has one K(X, Z) buffer.  Sweep 1: fill (and whitening) + moments with
+        no likelihood, per latent; the coupled map over [N, 2]; sweep 2 (``sites`` only): fill (and whitening / projection)
+        again + the site sums of each latent with its column of the map (``run(site_grads=...)``).  The refill costs one
+        K(X, Z) fill (plus the whitening product where the route has one) per latent -- the alternative, keeping both operands,
+        is the batched path's [P, Np, Mp] buffer, and this path runs exactly when that does not fit or is not wanted."""
+        if mean_only:
+            raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
+        T, dev = self.dtype, self.device
+        N, P = X.shape[0], moment_Tm.shape[0]
+        Np = B.round_up(N)
+        kw.pop("lik_param", None)
+        per = self._per_latent
+        mean = self._get("het_mean", (N, P), T)
+        var = self._get("het_var", (N, P), T)
+        for p, kp in enumerate(kernel.kernels):
+            st = self.run(X, None, Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1], whiten_T=per(whiten_T, p),
+                          want_moments=True, **kw)
+            mean[:, p] = st.mean[:, 0]
+            var[:, p] = st.var[:, 0]
+        Yc = Y.to(device=dev, dtype=T).contiguous()
+        g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Yc, lik_id, N, Np)
+        out = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
+        if want_moments:
+            out.mean, out.var = mean.to(torch.float64, copy=True), var.to(torch.float64, copy=True)
+        if want_grads:
+            out.g0, out.g1 = g0[:N].to(torch.float64, copy=True), g1[:N].to(torch.float64, copy=True)
+        if sites:
+            acc2, acc1 = [], []
+            for p, kp in enumerate(kernel.kernels):
+                st = self.run(X, None, Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1], whiten_T=per(whiten_T, p),
+                              project_T=per(project_T, p), sites=True, site_grads=(g0[:, p:p + 1], g1[:, p:p + 1]), **kw)
+                acc2.append(st.acc2)
+                acc1.append(st.acc1)
+            out.acc2, out.acc1 = torch.cat(acc2, dim=0), torch.cat(acc1, dim=0)
         return out
 
     # ------------------------------------------------------------------ K(X, Z) fill beside the M x M prelude
@@ -891,7 +979,7 @@ class EStepEngine:
     def run(self, X, Y, Z, kernel, *, moment_Tm, moment_mode, gamma, lik_id=B.LIK_NONE, lik_param=0.0,
             whiten_T=None, whiten_mode=B.TRI_UPPER, project_T=None, sites=False, want_moments=False, want_grads=False,
             b_tag=None, mean_only=False, prefill=None, moments_on_kfu=False, project_mode=B.TRI_LOWER,
-            keep_tile=False) -> EStepStats:
+            keep_tile=False, site_grads=None) -> EStepStats:
         """One pass over the shard's rows.
 
         keep_tile (one latent, no whitening): the triangular product of the moments, t_n = Tm k_n, is STORED (``tsvgp_trmm``
@@ -919,6 +1007,11 @@ class EStepEngine:
         stream; this call waits for it instead of filling.
         mean_only (likelihood NONE or GAUSSIAN): skip the variance product of the moments (TSVGP_LIK_MEANONLY) -- the
         Gaussian g0, g1 do not depend on it; ``var`` is then None and ``ve_sum`` NaN.
+        lik_id LIK_HETERO (P = 2, Y [N, 1]): moments of both latents with no likelihood, then the coupled map
+        (``tsvgp_lik_map_hetero_*``), then the site sums.
+        site_grads (lik_id NONE, one kernel): (g0, g1) [Np, P] in the compute dtype, rows >= N zero -- the site sums (and with
+        ``keep_tile`` the stored product) of this pass with gradients a coupled map made elsewhere; the moments product then
+        runs only for ``want_moments`` / ``keep_tile``, and ``ve_sum`` / ``nonpos`` are zero (the map's call counts them).
         """
         if isinstance(kernel, SeparateIndependent):
             return self._run_separate(X, Y, Z, kernel, moment_Tm=moment_Tm, moment_mode=moment_mode, gamma=gamma,
@@ -926,6 +1019,8 @@ class EStepEngine:
                                       project_T=project_T, sites=sites, want_moments=want_moments, want_grads=want_grads,
                                       mean_only=mean_only, moments_on_kfu=moments_on_kfu, project_mode=project_mode,
                                       prefill=prefill)
+        if site_grads is not None and lik_id != B.LIK_NONE:
+            raise ValueError("site_grads replaces the likelihood: lik_id must be LIK_NONE")
         if mean_only and (lik_id & 0xFF) not in (B.LIK_NONE, B.LIK_GAUSSIAN):
             raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
         T, dev = self.dtype, self.device
@@ -950,10 +1045,10 @@ class EStepEngine:
             return st
         if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != D:
             raise ValueError(f"X must be [N, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
+        coupled = (lik_id & 0xFF) == B.LIK_HETERO
         if lik_id != B.LIK_NONE:
+            self._check_y(Y, N, P, lik_id)
             Y = Y.to(device=dev, dtype=T).contiguous()
-            if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:
-                raise ValueError(f"Y must be [N, P] = [{N}, {P}], got {tuple(Y.shape)}")
         Np, Mp = B.round_up(N), B.round_up(M)
         inv_ls = kernel.inv_lengthscales(D, T, dev)
         variance = kernel.variance.item()
@@ -993,13 +1088,16 @@ class EStepEngine:
         nblk = Np // B.TILE
         ve_partial = self._get("ve_partial", (nblk,), torch.float64)
         nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
-        need_g = lik_id != B.LIK_NONE
+        need_g = lik_id != B.LIK_NONE or site_grads is not None
         g0 = self._get("g0", (Np, P), T) if need_g else None
         g1 = self._get("g1", (Np, P), T) if need_g else None
         mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
         var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
         lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
         tile = None
+        if site_grads is not None:
+            g0.copy_(site_grads[0])
+            g1.copy_(site_grads[1])
         if keep_tile:
             if P != 1 or mean_only or whiten_T is not None or not need_g:
                 raise ValueError("keep_tile: one latent, a likelihood, no whitening")
@@ -1007,17 +1105,38 @@ class EStepEngine:
             self.trmm(A, Tm[0], tile, moment_mode)
             mean = torch.mv(A[:N], gam[:, 0]).reshape(N, 1)  # gam: [Mp, 1], rows >= M zero
             var = (variance - torch.linalg.vector_norm(tile[:N], dim=1).square()).reshape(N, 1)
+            if site_grads is None:
+                with torch.cuda.device(dev):
+                    self._launch("tsvgp_lik_map", lambda: self._fn("tsvgp_lik_map")(
+                        mean.data_ptr(), var.data_ptr(), Y.data_ptr(), lik_id, float(lik_param), g0.data_ptr(), g1.data_ptr(),
+                        ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, 1, self._stream()))
+        elif coupled:
+            if mean_only:
+                raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
+            # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
+            mean, var = self._get("het_mean", (N, P), T), self._get("het_var", (N, P), T)
             with torch.cuda.device(dev):
-                self._launch("tsvgp_lik_map", lambda: self._fn("tsvgp_lik_map")(
-                    mean.data_ptr(), var.data_ptr(), Y.data_ptr(), lik_id, float(lik_param), g0.data_ptr(), g1.data_ptr(),
-                    ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, 1, self._stream()))
+                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
+                    A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, variance, B.LIK_NONE, 0.0, mean.data_ptr(),
+                    var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
+                    self._stream()))
+            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np)
+            if want_moments:
+                mean, var = mean.clone(), var.clone()
+        elif site_grads is not None and not want_moments:
+            pass  # the site sums alone
         else:
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
-                    A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, variance, lik_flags,
-                    float(lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
+                    A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if lik_id != B.LIK_NONE else None, variance, lik_flags,
+                    float(lik_param), _ptr(mean), _ptr(var), None if site_grads is not None else _ptr(g0),
+                    None if site_grads is not None else _ptr(g1), ve_partial.data_ptr(),
                     nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
-        stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
+        if site_grads is not None:
+            zero = torch.zeros((), dtype=torch.float64, device=dev)
+            stats = EStepStats(n_rows=N, ve_sum=zero, nonpos=zero.clone())
+        else:
+            stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
         stats.tile = tile
         if want_moments:
             stats.mean, stats.var = mean.to(torch.float64), (None if var is None else var.to(torch.float64))

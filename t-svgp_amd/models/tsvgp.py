@@ -170,6 +170,8 @@ class t_SVGP(base_SVGP):
                          num_latent_gps=num_latent_gps, num_data=num_data, compute_dtype=compute_dtype, device=device)
         self.num_inducing = self.inducing_variable.num_inducing
         self._init_variational_parameters(self.num_inducing, lambda_1, lambda_2_sqrt)
+        if self._coupled() and self.num_latent_gps != 2:
+            raise ValueError(f"the heteroskedastic likelihood needs num_latent_gps = 2 (its latent_dim), got {self.num_latent_gps}")
         self.whiten = False
         self.force = force
         # Opt-in "warm" E-steps: keep chol(K_uu + jitter I), its inverse and the whitened B = K_fu L^-T between calls while
@@ -233,6 +235,15 @@ class t_SVGP(base_SVGP):
         """second natural parameter"""
         L = self.lambda_2_sqrt.value
         return L @ L.transpose(-1, -2)
+
+    def _coupled(self) -> bool:
+        """The likelihood couples the latents of a row (HeteroskedasticTFPConditional: two latents, one target column)."""
+        return getattr(self.likelihood, "lik_id", None) == B.LIK_HETERO
+
+    def _check_targets(self, X, Y):
+        """Y [N, 1] under the coupled likelihood (the engine checks Y [N, P] for the others)."""
+        if self._coupled() and (Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != X.shape[0]):
+            raise ValueError(f"the heteroskedastic likelihood takes Y [N, 1] = [{X.shape[0]}, 1], got {tuple(Y.shape)}")
 
     # -- M x M prelude -----------------------------------------------------------------------------------------
     def _kmv(self, K: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -602,6 +613,7 @@ class t_SVGP(base_SVGP):
         mean, var = predict_f(X); g0 = d ve/d mean; g1 = min(d ve/d var, -1e-8).  All [N, P] fp64 on the model device.
         Not part of the reference's API: what parity checks (tests/, bench.py's ``elbo_match``) read."""
         X, Y = self._as_device(data[0]), self._as_device(data[1])
+        self._check_targets(X, Y)
         ops = self._site_operands()
         st = self._get_engine().run(X, Y, ops["Z"], self.kernel, moment_Tm=ops["D"], moment_mode=ops["moment_mode"],
                                     gamma=ops["beta"], lik_id=self.likelihood.lik_id, lik_param=self.likelihood.lik_param,
@@ -613,15 +625,18 @@ class t_SVGP(base_SVGP):
         return self.likelihood.predict_mean_and_var(*self.predict_f(Xnew))
 
     def predict_log_density(self, data):
-        X, Y = data
+        X, Y = self._as_device(data[0]), self._as_device(data[1])
+        self._check_targets(X, Y)
         Fmu, Fvar = self.predict_f(X)
-        return self.likelihood.predict_log_density(Fmu, Fvar, self._as_device(Y).to(Fmu.dtype))
+        return self.likelihood.predict_log_density(Fmu, Fvar, Y.to(Fmu.dtype))
 
     # -- ELBO --------------------------------------------------------------------------------------------------
     def elbo(self, data):
         """Evidence lower bound  sum_n E_q[log p(y_n | f_n)] * scale - KL[q(u) || p(u)]  (tsvgp.py:79-95).
         With more than one rank ``data`` is this rank's row shard and the sum is all-reduced."""
         X, Y = data
+        if self._coupled():
+            self._check_targets(self._as_device(X), self._as_device(Y))
         ops = self._site_operands()
         kl = kl_from_dense_site(ops["K6"], self.lambda_1.value, ops["D"], ops["U_W"], ops["beta"])
         st = self._get_engine().run(self._as_device(X), self._as_device(Y), ops["Z"], self.kernel,
@@ -650,6 +665,7 @@ class t_SVGP(base_SVGP):
         rank's shard."""
         sep = isinstance(self.kernel, SeparateIndependent)
         X, Y = self._as_device(data[0]), self._as_device(data[1])
+        self._check_targets(X, Y)
         eng, P, M = self._get_engine(), self.num_latent_gps, self.num_inducing
         Dn = X.shape[1]
         ops = self._site_operands()
@@ -668,6 +684,17 @@ class t_SVGP(base_SVGP):
         # The TRUE d ve / d var here: the crop of tsvgp.py:262-263 belongs to the site update, not to the ELBO (with the
         # 1e-3 jitter of the probit link log p is not log-concave in the far tails, so some g1 are positive)
         parts = []
+        coupled = self._coupled()
+        if coupled:
+            # A likelihood that couples the latents cannot ride on a per-kernel pass: one pass over all latents maps the
+            # moments of both to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
+            # their columns as given (``site_grads``) for the site sums and the kernel-gradient contraction.
+            stc = eng.run(X, Y, ops["Z"], self.kernel, moment_Tm=Dm, moment_mode=ops["moment_mode"], gamma=beta,
+                          lik_id=self.likelihood.lik_id | B.LIK_NOCROP, want_grads=True)
+            Np = B.round_up(X.shape[0])
+            gc0 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
+            gc1 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
+            gc0[:X.shape[0]], gc1[:X.shape[0]] = stc.g0, stc.g1
         for ki, kern in enumerate(kernels):
             lat = [ki] if sep else list(range(P))
             sl = slice(lat[0], lat[-1] + 1)
@@ -675,9 +702,13 @@ class t_SVGP(base_SVGP):
             # triangular product of it -- 2 N M^2 flops for moments + U instead of the 3 N M^2 of the fused moments kernel plus a
             # dense GEMM with Q = D^T D (round 5; 16.8 + 28.1 ms -> 15.5 + ~5 + 16 ms at N = 1e6, M = 1024).
             tile_path = len(lat) == 1 and hasattr(eng, "trmm") and os.environ.get("TSVGP_MSTEP_TILE", "1") != "0"
-            st = eng.run(X, Y[:, sl], ops["Z"], kern, moment_Tm=Dm[sl], moment_mode=ops["moment_mode"], gamma=beta[:, sl],
-                         lik_id=self.likelihood.lik_id | B.LIK_NOCROP, lik_param=self.likelihood.lik_param, sites=True,
-                         want_moments=gaussian, **({"keep_tile": True} if tile_path else {}))
+            if coupled:
+                st = eng.run(X, None, ops["Z"], kern, moment_Tm=Dm[sl], moment_mode=ops["moment_mode"], gamma=beta[:, sl],
+                             sites=True, site_grads=(gc0[:, sl], gc1[:, sl]), **({"keep_tile": True} if tile_path else {}))
+            else:
+                st = eng.run(X, Y[:, sl], ops["Z"], kern, moment_Tm=Dm[sl], moment_mode=ops["moment_mode"], gamma=beta[:, sl],
+                             lik_id=self.likelihood.lik_id | B.LIK_NOCROP, lik_param=self.likelihood.lik_param, sites=True,
+                             want_moments=gaussian, **({"keep_tile": True} if tile_path else {}))
             parts.append(st)
             Kfu, g0, g1 = eng._buf["Kfu"], eng._buf["g0"], eng._buf["g1"]  # [Np, Mp], [Np, len(lat)] (rows >= N are zero)
             Ubuf = eng._get("U", tuple(Kfu.shape), Kfu.dtype)
@@ -704,6 +735,8 @@ class t_SVGP(base_SVGP):
             st = EStepStats(n_rows=parts[0].n_rows, ve_sum=sum(s_.ve_sum for s_ in parts),
                             nonpos=sum(s_.nonpos for s_ in parts))
             st.acc2, st.acc1 = torch.cat([s_.acc2 for s_ in parts], dim=0), torch.cat([s_.acc1 for s_ in parts], dim=0)
+        if coupled:
+            st.ve_sum, st.nonpos = stc.ve_sum, stc.nonpos
         extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1)])
         acc2, acc1, ve_sum, nonpos, rows, tail = D_.reduce_stats(st, P, M, True, self._reduce(), eng, extra=extra)
         o = 0
@@ -783,6 +816,7 @@ class t_SVGP(base_SVGP):
         Updates the parameters in place and returns None.  The whole step is enqueued without host
         synchronisation; one device->host read of the status flags ends it."""
         X, Y = self._as_device(data[0]), self._as_device(data[1])
+        self._check_targets(X, Y)
         routes = self._routes(jitter)
         if self._wants_graph(X) and self._graph_step(X, Y, lr, jitter, routes):
             return
@@ -1162,6 +1196,7 @@ class t_SVGP(base_SVGP):
         ``natgrad_step`` would take, mapped back to the reference's coordinates, without updating the state.  Not part of the
         reference's API: what full-size parity checks (tests/, bench.py's ``state_match``) compare with the CPU restatement's einsums."""
         X, Y = self._as_device(data[0]), self._as_device(data[1])
+        self._check_targets(X, Y)
         routes = self._routes(jitter)
         st, ops = self._step_front(X, Y, 0.0, jitter, routes)
         acc2, acc1, _, nonpos, _, _ = D_.reduce_stats(st, self.num_latent_gps, self.num_inducing, True, self._reduce(),
