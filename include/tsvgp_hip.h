@@ -201,6 +201,22 @@ int tsvgp_lik_map_hetero_f64(const double *mean, const double *var, const double
 int tsvgp_lik_map_hetero_f32(const float *mean, const float *var, const float *Y, int flags, float *g0, float *g1,
                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
+/* (4c) The per-datum site step of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-148) fused with the likelihood map of
+ *     (4): mean, var, Y [N x P] -> g0, g1 as tsvgp_lik_map_* (never cropped: TSVGP_LIK_NOCROP semantics whatever lik says), then
+ *     IN PLACE on the fp64 site state lambda_1, lambda_2 [Np x P]:
+ *         lambda_1 <- (1 - lr) lambda_1 + lr (g0 - 2 g1 mean),
+ *         lambda_2 <- -2 min((1 - lr)(-lambda_2 / 2) + lr g1, -1e-8)       (so lambda_2 >= 2e-8).
+ *     Rows >= N are not touched.  ve_partial / nonpos_partial [Np / 128] as tsvgp_lik_map_*.  var may be NULL with
+ *     lik = TSVGP_LIK_GAUSSIAN (neither update reads it): ve_partial is then NaN and nonpos_partial counts rows with a
+ *     non-finite mean or gradient.  0 <= lr <= 1.  The fp32 entry reads fp32 mean / var / Y, keeps the state in fp64 and also
+ *     writes fp32 copies of the new lambda_1, lambda_2 [Np x P] (the weights tsvgp_site_accum_f32 reads on the next step). */
+int tsvgp_diag_site_step_f64(const double *mean, const double *var, const double *Y, int lik, double lik_param, double lr,
+                             double *lambda_1, double *lambda_2, double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np,
+                             int P, void *stream);
+int tsvgp_diag_site_step_f32(const float *mean, const float *var, const float *Y, int lik, double lik_param, double lr,
+                             double *lambda_1, double *lambda_2, float *lambda_1_f32, float *lambda_2_f32, double *ve_partial,
+                             int32_t *nonpos_partial, int64_t N, int64_t Np, int P, void *stream);
+
 /* (3b) The moments for P latents with one kernel each: latent p has its own operand A + p*strideA ([Np x Mp] each; strideA = 0
  *     is the shared operand of tsvgp_moments_*) and its own prior variance kdiag_host[p] (HOST array of P doubles, passed
  *     as kernel arguments).  1 <= P <= TSVGP_MAX_BATCH.  Everything else as tsvgp_moments_*; one launch, each workgroup

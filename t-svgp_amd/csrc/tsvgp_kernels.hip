@@ -1970,6 +1970,89 @@ __global__ __launch_bounds__(TILE) void lik_map_hetero_kernel(const T* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// diag_site_step_kernel: the per-datum site update of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-145) fused with
+// the likelihood-gradient map of lik_map_kernel (same device functions, same two-threads-per-row quadrature split, g1 never
+// cropped).  Per row and latent, in place on the fp64 site state [Np x P]:
+//     g0' = g0 - 2 g1 mean,   lambda_1 <- (1 - lr) lambda_1 + lr g0',
+//     n2 = min((1 - lr)(-lambda_2 / 2) + lr g1, -1e-8),   lambda_2 <- -2 n2      (so lambda_2 >= 2e-8)
+// plus, when l1c / l2c are given (the fp32 entry), copies of the new values in T: the weights tsvgp_site_accum_f32 reads on
+// the next projection.  Rows >= N are not touched (the caller keeps them zero: the projection then adds nothing for them).
+// ve_partial / nonpos_partial as lik_map_kernel; var == nullptr (Gaussian only: neither update reads the variance) gives
+// NaN ve partials and counts rows with a non-finite mean or gradient instead, as mean_lik_kernel does.  One workgroup per
+// 128 rows; O(N P) loads and stores, HBM bound.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(NTHREADS) void diag_site_step_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                                  const T* __restrict__ Y, int lik, double lik_param, double lr,
+                                                                  double* __restrict__ l1, double* __restrict__ l2,
+                                                                  T* __restrict__ l1c, T* __restrict__ l2c,
+                                                                  double* __restrict__ ve_partial,
+                                                                  int32_t* __restrict__ nonpos_partial, int64_t N, int P) {
+    __shared__ double red[NTHREADS / 64];
+    __shared__ int redi[NTHREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int srow = t >> 1, skh = t & 1;
+    const int64_t n = (int64_t)blockIdx.x * TILE + srow;
+    const bool live = n < N;
+    const int lk = (lik & 0xFF) | TSVGP_LIK_NOCROP;
+    double ve_acc = 0.0;
+    int nonpos = 0;
+    for (int p = 0; p < P; ++p) {
+        const int64_t i = n * P + p;
+        const double mu = live ? (double)mean[i] : 0.0;
+        const double v = (live && var) ? (double)var[i] : 1.0;
+        double g0 = 0.0, g1 = 0.0, ve = 0.0;
+        if ((lk & 0xFF) == TSVGP_LIK_BERNOULLI) {
+            double a0, a1, av;
+            const double sd = sqrt(v);
+            bern_sums_t<T>(mu, sd, live && (double)Y[i] == 1.0, skh * 5, skh * 5 + 5, a0, a1, av);
+            a0 += __shfl_xor(a0, 1);
+            a1 += __shfl_xor(a1, 1);
+            av += __shfl_xor(av, 1);
+            g0 = a0;
+            g1 = a1 / (2.0 * sd);
+            ve = av;
+        } else if (live) {
+            lik_eval(lk, lik_param, mu, v, (double)Y[i], g0, g1, ve);
+        }
+        if (skh == 0 && live) {
+            if (var) {
+                if (!(v > 0.0)) nonpos += 1;
+                ve_acc += ve;
+            } else if (!(fabs(mu) <= 1.79769313486231570815e308) || !(fabs(g0) <= 1.79769313486231570815e308)) {
+                nonpos += 1;
+            }
+            const double g0m = g0 - 2.0 * g1 * mu;  // tsvgp_sites.py:133
+            const double a1 = (1.0 - lr) * l1[i] + lr * g0m;  // :139
+            const double n2 = fmin((1.0 - lr) * (-0.5 * l2[i]) + lr * g1, -1e-8);  // :136, :140, :144
+            const double a2 = -2.0 * n2;  // :148
+            l1[i] = a1;
+            l2[i] = a2;
+            if (l1c) {
+                l1c[i] = (T)a1;
+                l2c[i] = (T)a2;
+            }
+        }
+    }
+    double s = ve_acc;
+    int c = nonpos;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        c += __shfl_xor(c, o);
+    }
+    if (lane == 0) {
+        red[w] = s;
+        redi[w] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = var ? red[0] + red[1] + red[2] + red[3] : __builtin_nan("");
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1] + redi[2] + redi[3];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // mean_lik_kernel (TSVGP_LIK_MEANONLY): mean[n, p] = sum_j A[n, j] * gamma[j, p] and, for the Gaussian likelihood,
 // g0 = (y - mean) / s2, g1 = -1 / (2 s2) -- neither depends on the predictive variance.  HBM bound: one sweep of A.
 // One workgroup per 128-row panel (same grid as panel_kernel, so the per-workgroup partial buffers keep their
@@ -4280,6 +4363,22 @@ int lik_map(const T* mean, const T* var, const T* Y, int lik, double lik_param, 
 }
 
 template <typename T>
+int diag_site_step(const T* mean, const T* var, const T* Y, int lik, double lik_param, double lr, double* l1, double* l2, T* l1c,
+                   T* l2c, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, int P, void* stream) {
+    if (!mean || !Y || !l1 || !l2 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE) || P <= 0) return TSVGP_EINVAL;
+    if (!l1c != !l2c) return TSVGP_EINVAL;
+    if (lik & ~(0xFF | TSVGP_LIK_NOCROP)) return TSVGP_EINVAL;
+    const int base = lik & 0xFF;
+    if (base != TSVGP_LIK_GAUSSIAN && base != TSVGP_LIK_BERNOULLI) return TSVGP_EINVAL;
+    if (base == TSVGP_LIK_GAUSSIAN && !(lik_param > 0.0)) return TSVGP_EINVAL;
+    if (base == TSVGP_LIK_BERNOULLI && !var) return TSVGP_EINVAL;
+    if (!(lr >= 0.0 && lr <= 1.0)) return TSVGP_EINVAL;
+    hipLaunchKernelGGL(diag_site_step_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(NTHREADS), 0, (hipStream_t)stream, mean, var, Y,
+                       lik, lik_param, lr, l1, l2, l1c, l2c, ve_partial, nonpos_partial, N, P);
+    return launch_status();
+}
+
+template <typename T>
 int lik_map_hetero(const T* mean, const T* var, const T* Y, int flags, T* g0, T* g1, double* ve_partial, int32_t* nonpos_partial,
                    int64_t N, int64_t Np, void* stream) {
     if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
@@ -4688,6 +4787,19 @@ int tsvgp_lik_map_hetero_f64(const double* mean, const double* var, const double
 int tsvgp_lik_map_hetero_f32(const float* mean, const float* var, const float* Y, int flags, float* g0, float* g1,
                              double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
     return lik_map_hetero<float>(mean, var, Y, flags, g0, g1, ve_partial, nonpos_partial, N, Np, stream);
+}
+int tsvgp_diag_site_step_f64(const double* mean, const double* var, const double* Y, int lik, double lik_param, double lr,
+                             double* lambda_1, double* lambda_2, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np,
+                             int P, void* stream) {
+    return diag_site_step<double>(mean, var, Y, lik, lik_param, lr, lambda_1, lambda_2, nullptr, nullptr, ve_partial, nonpos_partial,
+                                  N, Np, P, stream);
+}
+int tsvgp_diag_site_step_f32(const float* mean, const float* var, const float* Y, int lik, double lik_param, double lr,
+                             double* lambda_1, double* lambda_2, float* lambda_1_f32, float* lambda_2_f32, double* ve_partial,
+                             int32_t* nonpos_partial, int64_t N, int64_t Np, int P, void* stream) {
+    if (!lambda_1_f32 || !lambda_2_f32) return TSVGP_EINVAL;
+    return diag_site_step<float>(mean, var, Y, lik, lik_param, lr, lambda_1, lambda_2, lambda_1_f32, lambda_2_f32, ve_partial,
+                                 nonpos_partial, N, Np, P, stream);
 }
 int tsvgp_moments_f64(const double* A, const double* Tm, const double* gamma, const double* Y, double kdiag, int lik,
                       double lik_param, double* mean, double* var, double* g0, double* g1, double* ve_partial,

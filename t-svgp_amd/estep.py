@@ -1175,16 +1175,17 @@ class EStepEngine:
         return acc2[:, :M, :M], acc1[:, :M]
 
     def run_two_product(self, X, Y, Z, kernel, *, whiten_T, moment_Tm, gamma, lik_id=B.LIK_NONE, lik_param=0.0, sites=False,
-                        want_moments=False) -> EStepStats:
+                        want_moments=False, prefill=None) -> EStepStats:
         """The pass of ``t_SVGP_white`` with the reference's OWN two-product variance (src/util.py:76-86):
             var = kff - |LA^-1 k|^2 + |LR^-1 k|^2 = kff - |b|^2 + |T2 b|^2,   b = U6^-1 k (whiten_T = U6^-1, upper form),
         T2 = U_R^-1 U6 (``moment_Tm``, upper triangular), mean = b^T gamma.  Used when Lambda_2 + 1e-9 I is not positive definite
         (the single triangular product of ``run`` needs its factor; the reference only needs K + Lambda_2 + 1e-9 I).  Sequence:
         fill -> trmm (B) -> moments with NO likelihood (mean, kff - |T2 b|^2) -> |b|^2 by a row reduction of B -> the
-        likelihood map on the assembled moments (``tsvgp_lik_map_*``) -> site sums over B.  One shared kernel, one latent."""
+        likelihood map on the assembled moments (``tsvgp_lik_map_*``) -> site sums over B.  One shared kernel, one latent.
+        ``prefill``: as ``run``."""
         T, dev = self.dtype, self.device
         st = self.run(X, None, Z, kernel, moment_Tm=moment_Tm, moment_mode=B.TRI_UPPER, gamma=gamma, lik_id=B.LIK_NONE,
-                      whiten_T=whiten_T, whiten_mode=B.TRI_UPPER, want_moments=True)
+                      whiten_T=whiten_T, whiten_mode=B.TRI_UPPER, want_moments=True, prefill=prefill)
         N, M = X.shape[0], Z.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         Bw = self._buf["B"]  # the whitened operand of the pass just run
@@ -1210,3 +1211,81 @@ class EStepEngine:
             if sites:
                 stats.acc2, stats.acc1 = self._site_sums(Bw, g0, g1, 1, M)
         return stats
+
+    # ------------------------------------------------------------------ per-datum diagonal sites (t_SVGP_sites)
+    def project_diag(self, X, Z, kernel, w1, w2):
+        """The projection of per-datum sites onto the inducing points (reference src/util.py:188-236 with cholesky=False and
+        no K_uu):  acc2 = sum_n w2_n k_n k_n^T [1, M, M],  acc1 = sum_n w1_n k_n [1, M]  over k_n = K(Z, x_n), fp64 -- the fill
+        and ``tsvgp_site_accum_*`` with the caller's weights w1, w2 [Np, 1] (compute dtype, rows >= N zero) in place of the
+        likelihood gradients.  The filled K(X, Z) stays in the buffer: the returned ticket hands it to ``run(prefill=...)`` /
+        ``run_two_product`` / ``diag_sites_moments`` of the same step, which then do not fill again."""
+        T, dev = self.dtype, self.device
+        X = X.to(device=dev, dtype=T).contiguous()
+        Z = Z.to(device=dev, dtype=T).contiguous()
+        N, D = X.shape
+        M = Z.shape[0]
+        Np, Mp = B.round_up(N), B.round_up(M)
+        if tuple(w1.shape) != (Np, 1) or tuple(w2.shape) != (Np, 1) or w1.dtype != T or w2.dtype != T:
+            raise ValueError(f"site weights must be [Np, 1] = [{Np}, 1] in {T}")
+        if N == 0:
+            zero = torch.zeros((1, M, M), dtype=torch.float64, device=dev)
+            return zero, torch.zeros((1, M), dtype=torch.float64, device=dev), None
+        self._b_tag = None
+        Kfu = self._get("Kfu", (Np, Mp), T)
+        if self._side is not None and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(dev).wait_stream(self._side)
+        self.se_fill(X, Z, kernel.inv_lengthscales(D, T, dev), kernel.variance.item(), Kfu, kernel.kind)
+        acc2, acc1 = self._site_sums(Kfu, w1, w2, 1, M)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return acc2, acc1, dict(event=done, Kfu=Kfu, keep=(X, Z))
+
+    def diag_sites_moments(self, X, Z, kernel, ticket, *, whiten_T, moment_Tm, moment_mode, gamma, mean_only=False):
+        """mean, var [N, 1] in the compute dtype (cached buffers; var None with ``mean_only``) on the K(X, Z) that
+        ``project_diag`` left (``ticket``): the whitening product when ``whiten_T`` is given, then the moments with no
+        likelihood (TSVGP_LIK_MEANONLY with ``mean_only``)."""
+        T, dev = self.dtype, self.device
+        N, M = X.shape[0], Z.shape[0]
+        Np, Mp = B.round_up(N), B.round_up(M)
+        Kfu = self._buf.get("Kfu")
+        if ticket is None or ticket["Kfu"] is not Kfu:
+            raise RuntimeError("diag_sites_moments needs the ticket of this engine's last project_diag")
+        torch.cuda.current_stream(dev).wait_event(ticket["event"])
+        A = Kfu
+        if whiten_T is not None:
+            A = self._get("B", (Np, Mp), T)
+            self.trmm(Kfu, self._pad_square(whiten_T, Mp, "pad_Linv"), A, B.TRI_UPPER)
+        Tm = self._pad_square(moment_Tm, Mp, "pad_Tm")
+        gam = self._padded_gamma(gamma, Mp, 1)
+        nblk = Np // B.TILE
+        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
+        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
+        mean = self._get("ds_mean", (N, 1), T)
+        var = None if mean_only else self._get("ds_var", (N, 1), T)
+        flags = (B.LIK_NONE | B.LIK_MEANONLY) if mean_only else B.LIK_NONE
+        with torch.cuda.device(dev):
+            self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
+                A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, kernel.variance.item(), flags, 0.0, mean.data_ptr(), _ptr(var),
+                None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, 1, moment_mode, self._stream()))
+        return mean, var
+
+    def diag_site_step(self, mean, var, Y, lik_id, lik_param, lr, l1, l2, l1c=None, l2c=None):
+        """One launch of ``tsvgp_diag_site_step_*``: the likelihood map on (mean, var, Y) [N, P] in the compute dtype and the
+        in-place site update of l1, l2 [Np, P] (fp64; fp32 copies into l1c, l2c for the fp32 engine).  ``var`` None: Gaussian
+        only (no variance read; the ve partials are then NaN).  Returns (ve_sum, nonpos) as fp64 device scalars."""
+        T, dev = self.dtype, self.device
+        N, P = mean.shape
+        Np = l1.shape[0]
+        if T == torch.float32 and (l1c is None or l2c is None):
+            raise ValueError("the fp32 site step writes fp32 copies of the sites: l1c, l2c are required")
+        Yc = Y.to(device=dev, dtype=T).contiguous()
+        nblk = Np // B.TILE
+        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
+        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
+        args = [mean.data_ptr(), _ptr(var), Yc.data_ptr(), int(lik_id), float(lik_param), float(lr), l1.data_ptr(), l2.data_ptr()]
+        if T == torch.float32:
+            args += [l1c.data_ptr(), l2c.data_ptr()]
+        args += [ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, P, self._stream()]
+        with torch.cuda.device(dev):
+            self._launch("tsvgp_diag_site_step", lambda: self._fn("tsvgp_diag_site_step")(*args))
+        return ve_partial.sum(), nonpos_partial.sum().to(torch.float64)

@@ -65,3 +65,35 @@ class DenseSites(Sites):
             self._lambda_2_sqrt.assign_owned(value)
         else:
             self._lambda_2_sqrt.assign(torch.tril(to_tensor(value, device=self._lambda_2_sqrt.device)))
+
+
+class DiagSites(Sites):
+    """Sites with diagonal lambda_2 (reference src/sites.py:25-40): one pair lambda_1, lambda_2 [N, P] per datum, the state of
+    ``t_SVGP_sites``.  Deviation: the reference keeps lambda_2 under GPflow's ``positive()`` (softplus) transform; the value
+    itself is stored here, as ``DenseSites`` does (the softplus round trip moves it by about one ulp).
+
+    Both parameters are views of one zero-padded fp64 buffer [2, Np, P] (Np = N rounded up to 128) that the HIP site step
+    updates in place and the projection reads as its weights; ``padded()`` hands it out, re-binding a parameter that was
+    replaced through ``assign`` first."""
+
+    def __init__(self, lambda_1, lambda_2, name=None, device=None, pad=128):
+        super().__init__(name=name)
+        self.lambda_1 = Parameter(lambda_1, trainable=False, device=device)  # [N, P]
+        self.lambda_2 = Parameter(lambda_2, trainable=False, device=device)  # [N, P]
+        if self.lambda_1.shape != self.lambda_2.shape or len(self.lambda_1.shape) != 2:
+            raise ValueError(f"lambda_1, lambda_2 must both be [N, P], got {self.lambda_1.shape} and {self.lambda_2.shape}")
+        N, P = self.lambda_1.shape
+        self._store = torch.zeros((2, -(-N // pad) * pad, P), dtype=torch.float64, device=self.lambda_1.device)
+        self._bind()
+
+    def _bind(self):
+        N = self.lambda_1.shape[0]
+        for k, par in enumerate((self.lambda_1, self.lambda_2)):
+            if par.value.data_ptr() != self._store[k].data_ptr():
+                self._store[k, :N].copy_(par.value)
+                par.assign_owned(self._store[k, :N])
+
+    def padded(self):
+        """(lambda_1, lambda_2) as [Np, P] fp64 views of the padded buffer (rows >= N zero)."""
+        self._bind()
+        return self._store[0], self._store[1]
