@@ -50,6 +50,8 @@ extern "C" {
 #define TSVGP_LIK_BERNOULLI 2 /* gpflow.likelihoods.Bernoulli, probit + 1e-3 jitter, 20-pt Gauss-Hermite */
 #define TSVGP_LIK_HETERO 3    /* gpflow.likelihoods.HeteroskedasticTFPConditional (Normal, Exp scale) over TWO coupled latents:
                                  tsvgp_lik_map_hetero_* only (the moments kernels and tsvgp_lik_map_* reject it) */
+#define TSVGP_LIK_SOFTMAX 4   /* gpflow.likelihoods.Softmax(C) (a MonteCarloLikelihood) over C coupled latents:
+                                 tsvgp_lik_map_softmax_* only */
 #define TSVGP_LIK_NOCROP 0x100 /* OR-ed into the selector: leave g1 = d ve/d var uncropped (reference
                                   src/models/tsvgp_white.py:188-191 has no crop; src/models/tsvgp.py:262-263 has) */
 #define TSVGP_LIK_MEANONLY 0x200 /* OR-ed into the selector (NONE or GAUSSIAN only): skip the variance product.  Under a
@@ -216,6 +218,46 @@ int tsvgp_diag_site_step_f64(const double *mean, const double *var, const double
 int tsvgp_diag_site_step_f32(const float *mean, const float *var, const float *Y, int lik, double lik_param, double lr,
                              double *lambda_1, double *lambda_2, float *lambda_1_f32, float *lambda_2_f32, double *ve_partial,
                              int32_t *nonpos_partial, int64_t N, int64_t Np, int P, void *stream);
+
+/* The normal generator of the Monte Carlo likelihoods: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11) and Box-Muller.
+ * The draw for (seed, draw, global row n, sample s, class c) is a pure function of those five integers -- not of the launch
+ * geometry, the array type or the rank that computes it:
+ *   key     = (seed & 0xffffffff, seed >> 32)                       seed, n taken as unsigned 64-bit, draw modulo 2^32
+ *   counter = (n & 0xffffffff, n >> 32, s * 8 + (c >> 2), draw)     (0 <= c < 32, 0 <= s < TSVGP_MC_MAX_SAMPLES)
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter, key): ten rounds of
+ *        (c0, c1, c2, c3) <- (hi(0xCD9E8D57 * c2) ^ c1 ^ k0, lo(0xCD9E8D57 * c2), hi(0xD2511F53 * c0) ^ c3 ^ k1, lo(0xD2511F53 * c0)),
+ *        the key stepping by (0x9E3779B9, 0xBB67AE85) after each round
+ *   u(x) = (x + 0.5) * 2^-32   (exact in fp64, inside (0, 1))
+ *   class 4 (c >> 2) + 0 = sqrt(-2 ln u(x0)) * cos(2 pi u(x1)),   + 1 = sqrt(-2 ln u(x0)) * sin(2 pi u(x1)),
+ *   class 4 (c >> 2) + 2 = sqrt(-2 ln u(x2)) * cos(2 pi u(x3)),   + 3 = sqrt(-2 ln u(x2)) * sin(2 pi u(x3))
+ * with 2 pi = 6.283185307179586 and every operation an fp64 operation in the order written (2 pi * u is one rounded product).
+ * Both array types compute the draws in fp64; the _f32 entry points round the finished draw.
+ *
+ * (4c) tsvgp_mc_normals_*: out [S x N x C] (GPflow's epsilon layout), out[s, n, c] = the draw of (seed, draw, row_offset + n, s, c).
+ *      1 <= C <= TSVGP_MAX_BATCH, 1 <= S <= TSVGP_MC_MAX_SAMPLES, row_offset >= 0, S * N * ceil(C / 4) <= (2^31 - 1) * 256. */
+#define TSVGP_MC_MAX_SAMPLES (1 << 28)
+int tsvgp_mc_normals_f64(double *out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void *stream);
+int tsvgp_mc_normals_f32(float *out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void *stream);
+
+/* (4d) The Softmax likelihood map (gpflow.likelihoods.Softmax(C), GPflow 2.2.1 [ext]; reference docs/notebooks/mnist.py): the
+ *      Monte Carlo estimate over S draws eps^s [N x C] of log p(y | f) = f_y - logsumexp_c f_c at f^s = mean + sqrt(var) eps^s, and
+ *      its derivative through the reparameterisation (reference src/models/tsvgp.py:256-263): with p^s = softmax(f^s),
+ *      d_c^s = [c == y] - p_c^s:  ve = 1/S sum_s log p(y | f^s),  g0_c = 1/S sum_s d_c^s,
+ *      g1_c = 1/S sum_s d_c^s eps_c^s / (2 sqrt(var_c)) (cropped at -1e-8 unless TSVGP_LIK_NOCROP; a NaN stays NaN
+ *      under the crop, as under np.minimum: a row with a negative variance has NaN g0 and g1 and is counted in nonpos_partial).
+ *      mean, var [N x C]; Y [N x 1] class labels 0 .. C-1 in the array type (never used as an address; a label that is not an
+ *      integer in [0, C) makes its row's ve, g0, g1 NaN); flags = TSVGP_LIK_SOFTMAX, optionally | TSVGP_LIK_NOCROP;
+ *      2 <= C <= TSVGP_MAX_BATCH; 1 <= S <= TSVGP_MC_MAX_SAMPLES; rng_state: DEVICE int64 [seed, draw], read by the kernel (a
+ *      captured graph replays with whatever the words hold then; the caller advances draw with an in-stream add);
+ *      row_offset: global number of row 0 (a row shard's first row); epsilon: NULL, or [S x N x C] draws that replace the
+ *      generator (GPflow's epsilon= hook; rng_state may then be NULL).  Outputs as tsvgp_lik_map_hetero_*: g0, g1 [Np x C] (rows
+ *      >= N zero), ve_partial, nonpos_partial [Np / 128].  Sums in fp64 for either array type, max-shifted logsumexp. */
+int tsvgp_lik_map_softmax_f64(const double *mean, const double *var, const double *Y, int flags, int C, int S,
+                              const int64_t *rng_state, int64_t row_offset, const double *epsilon, double *g0, double *g1,
+                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+int tsvgp_lik_map_softmax_f32(const float *mean, const float *var, const float *Y, int flags, int C, int S,
+                              const int64_t *rng_state, int64_t row_offset, const float *epsilon, float *g0, float *g1,
+                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
 /* (3b) The moments for P latents with one kernel each: latent p has its own operand A + p*strideA ([Np x Mp] each; strideA = 0
  *     is the shared operand of tsvgp_moments_*) and its own prior variance kdiag_host[p] (HOST array of P doubles, passed

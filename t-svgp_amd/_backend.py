@@ -26,6 +26,8 @@ TILE = 128
 MAX_BATCH = 32  # TSVGP_MAX_BATCH: latents per launch of the *_batched entry points
 LIK_NONE, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_HETERO = 3  # two coupled latents: tsvgp_lik_map_hetero_* only
+LIK_SOFTMAX = 4  # C coupled latents, Monte Carlo: tsvgp_lik_map_softmax_* only
+COUPLED_LIKS = (LIK_HETERO, LIK_SOFTMAX)  # likelihoods whose row couples its latents (Y [N, 1])
 LIK_NOCROP = 0x100
 LIK_MEANONLY = 0x200
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 2, 3
@@ -135,6 +137,12 @@ _PROTOTYPES = {
                                          c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_diag_site_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "tsvgp_lik_map_softmax_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_softmax_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_mc_normals_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "tsvgp_mc_normals_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_site_accum_work_bytes_f64": (c_int64, [c_int, c_int, c_int]),
     "tsvgp_site_accum_work_bytes_f32": (c_int64, [c_int, c_int, c_int]),
     "tsvgp_site_accum_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),

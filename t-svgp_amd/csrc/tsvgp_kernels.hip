@@ -2053,6 +2053,199 @@ __global__ __launch_bounds__(NTHREADS) void diag_site_step_kernel(const T* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The Monte Carlo normal generator (include/tsvgp_hip.h, "The normal generator"): Philox4x32-10 [Salmon et al. 2011] and
+// Box-Muller.  The draw for (seed, draw, global row n, sample s, class c) is a pure function of those five integers:
+// key = (seed lo, seed hi), counter = (n lo, n hi, s * 8 + (c >> 2), draw lo); one call gives the four normals of classes
+// 4 (c >> 2) .. + 3: outputs (x0, x1) -> classes +0 (cos) and +1 (sin), (x2, x3) -> +2 and +3.  All of it in fp64 for either
+// array type, so a draw does not depend on the dtype around it.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t& x0, uint32_t& x1, uint32_t& x2, uint32_t& x3) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    x0 = c0, x1 = c1, x2 = c2, x3 = c3;
+}
+
+__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, double& za, double& zb) {
+    const double u1 = ((double)xa + 0.5) * 0x1p-32, u2 = ((double)xb + 0.5) * 0x1p-32;  // exact: in (0, 1)
+    const double r = sqrt(-2.0 * log(u1));
+    const double th = 6.283185307179586 * u2;
+    za = r * cos(th);
+    zb = r * sin(th);
+}
+
+__device__ __forceinline__ void mc_normals4(int64_t seed, int64_t draw, int64_t n, uint32_t s, uint32_t q, double z[4]) {
+    uint32_t x0, x1, x2, x3;
+    philox4x32_10((uint32_t)(uint64_t)n, (uint32_t)((uint64_t)n >> 32), s * 8u + q, (uint32_t)(uint64_t)draw,
+                  (uint32_t)(uint64_t)seed, (uint32_t)((uint64_t)seed >> 32), x0, x1, x2, x3);
+    box_muller(x0, x1, z[0], z[1]);
+    box_muller(x2, x3, z[2], z[3]);
+}
+
+// mc_normals_kernel: out[s, n, c] (GPflow's epsilon layout [S x N x C]) = the draw of (seed, draw, row_offset + n, s, c).
+// One thread per (s, n, class quad).
+template <typename T>
+__global__ __launch_bounds__(256) void mc_normals_kernel(T* __restrict__ out, int64_t seed, int64_t draw, int64_t row_offset,
+                                                         int64_t S, int64_t N, int C) {
+    const int Q4 = (C + 3) >> 2;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * N * Q4) return;
+    const int q = (int)(i % Q4);
+    const int64_t sn = i / Q4, n = sn % N, s = sn / N;
+    double z[4];
+    mc_normals4(seed, draw, row_offset + n, (uint32_t)s, (uint32_t)q, z);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * q + k < C) out[sn * C + 4 * q + k] = (T)z[k];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// lik_map_softmax_kernel: gpflow.likelihoods.Softmax [ext] (a MonteCarloLikelihood; reference docs/notebooks/mnist.py), the
+// map that couples C latents: with f^s = mean + sqrt(var) eps^s, p^s = softmax(f^s), d_c^s = [c == y] - p_c^s,
+//     ve = 1/S sum_s (f_y^s - logsumexp_c f_c^s),  g0_c = 1/S sum_s d_c^s,  g1_c = 1/S sum_s d_c^s eps_c^s / (2 sqrt(var_c))
+// (the derivative of the estimator through the reparameterisation, reference src/models/tsvgp.py:256-263).
+// ONE WAVE PER ROW: lane = sg * Q + q holds the classes 4 q .. 4 q + 3 (one Philox call) of the samples s = sg, sg + 64 / Q, ...;
+// Q = the class quads of the row rounded up to a power of two (template: 1, 2, 4, 8), so the per-row values are a fixed four per
+// lane and nothing is indexed at run time.  The softmax of a sample is a max / sum butterfly over its Q lanes, the sample
+// sums a butterfly over the 64 / Q sample groups; every sum has one fixed order.  A workgroup of four waves takes 128 rows
+// (32 per wave, one after the other) and writes their fp64 block sum of ve.  eps comes from `epsilon` [S x N x C] if given,
+// else from the generator with (seed, draw) READ FROM DEVICE MEMORY (a replayed graph sees the advanced draw).
+// The label is never an address: lanes compare their class numbers with it; a label that is no integer in [0, C) makes the
+// row's ve, g0, g1 NaN.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T, int Q>
+__global__ __launch_bounds__(256) void lik_map_softmax_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                              const T* __restrict__ Y, int flags, int C, int S,
+                                                              const int64_t* __restrict__ rng_state, int64_t row_offset,
+                                                              const T* __restrict__ epsilon, T* __restrict__ g0o,
+                                                              T* __restrict__ g1o, double* __restrict__ ve_partial,
+                                                              int32_t* __restrict__ nonpos_partial, int64_t N) {
+    constexpr int NSG = 64 / Q;  // sample groups of a wave
+    __shared__ double red[4];
+    __shared__ int redi[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int q = lane % Q, sg = lane / Q;
+    int64_t seed = 0, draw = 0;
+    if (!epsilon) seed = rng_state[0], draw = rng_state[1];
+    bool valid[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) valid[k] = 4 * q + k < C;
+    const double inv_S = 1.0 / (double)S;
+    double ve_wave = 0.0;
+    int nonpos_wave = 0;
+    for (int r = 0; r < 32; ++r) {
+        const int64_t n = (int64_t)blockIdx.x * TILE + w * 32 + r;  // wave-uniform
+        if (n >= N) {  // rows >= N of the [Np x C] outputs: zeros
+            if (sg == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (valid[k]) g0o[n * C + 4 * q + k] = (T)0.0, g1o[n * C + 4 * q + k] = (T)0.0;
+            }
+            continue;
+        }
+        double m[4], sd[4], a0[4], a1[4];
+        bool isy[4];
+        const double y = (double)Y[n];
+        const bool bad = !(y >= 0.0 && y < (double)C && y == floor(y));
+        int nonpos = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double v = valid[k] ? (double)var[n * C + 4 * q + k] : 1.0;
+            m[k] = valid[k] ? (double)mean[n * C + 4 * q + k] : 0.0;
+            sd[k] = sqrt(v);
+            a0[k] = a1[k] = 0.0;
+            isy[k] = valid[k] && (double)(4 * q + k) == y;
+            nonpos += (sg == 0 && !(v > 0.0)) ? 1 : 0;
+        }
+        double vel = 0.0;
+        for (int s0 = 0; s0 < S; s0 += NSG) {  // wave-uniform trip count; lanes beyond S are masked
+            const int s = s0 + sg;
+            const bool act = s < S;
+            double eps[4] = {0.0, 0.0, 0.0, 0.0};
+            if (act && valid[0]) {
+                if (epsilon) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (valid[k]) eps[k] = (double)epsilon[((int64_t)s * N + n) * C + 4 * q + k];
+                } else {
+                    mc_normals4(seed, draw, row_offset + n, (uint32_t)s, (uint32_t)q, eps);
+                }
+            }
+            double f[4], mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                f[k] = m[k] + sd[k] * eps[k];
+                mx = valid[k] ? fmax(mx, f[k]) : mx;
+            }
+#pragma unroll
+            for (int o = 1; o < Q; o <<= 1) mx = fmax(mx, __shfl_xor(mx, o));
+            double e[4], sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                e[k] = valid[k] ? exp(f[k] - mx) : 0.0;
+                sum += e[k];
+            }
+#pragma unroll
+            for (int o = 1; o < Q; o <<= 1) sum += __shfl_xor(sum, o);
+            const double inv = 1.0 / sum;
+            if (act) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double d = (isy[k] ? 1.0 : 0.0) - e[k] * inv;
+                    a0[k] += d;
+                    a1[k] += d * eps[k];
+                    vel += isy[k] ? f[k] - mx : 0.0;
+                }
+                if (q == 0) vel -= log(sum);
+            }
+        }
+#pragma unroll
+        for (int o = Q; o < 64; o <<= 1) {  // over the sample groups
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a0[k] += __shfl_xor(a0[k], o);
+                a1[k] += __shfl_xor(a1[k], o);
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            vel += __shfl_xor(vel, o);
+            nonpos += __shfl_xor(nonpos, o);
+        }
+        const double poison = bad ? NAN : 0.0;
+        if (sg == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                double d0 = a0[k] * inv_S, d1 = a1[k] * inv_S / (2.0 * sd[k]);
+                // reference tsvgp.py:262-263; a NaN (non-positive variance) stays NaN as under np.minimum: fmin would drop it
+                if (!(flags & TSVGP_LIK_NOCROP)) d1 = d1 != d1 ? d1 : fmin(d1, -1e-8);
+                if (valid[k]) g0o[n * C + 4 * q + k] = (T)(d0 + poison), g1o[n * C + 4 * q + k] = (T)(d1 + poison);
+            }
+        }
+        ve_wave += vel * inv_S + poison;
+        nonpos_wave += nonpos;
+    }
+    if (lane == 0) {
+        red[w] = ve_wave;
+        redi[w] = nonpos_wave;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1] + redi[2] + redi[3];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // mean_lik_kernel (TSVGP_LIK_MEANONLY): mean[n, p] = sum_j A[n, j] * gamma[j, p] and, for the Gaussian likelihood,
 // g0 = (y - mean) / s2, g1 = -1 / (2 s2) -- neither depends on the predictive variance.  HBM bound: one sweep of A.
 // One workgroup per 128-row panel (same grid as panel_kernel, so the per-workgroup partial buffers keep their
@@ -4388,6 +4581,38 @@ int lik_map_hetero(const T* mean, const T* var, const T* Y, int flags, T* g0, T*
     return launch_status();
 }
 
+template <typename T>
+int lik_map_softmax(const T* mean, const T* var, const T* Y, int flags, int C, int S, const int64_t* rng_state, int64_t row_offset,
+                    const T* epsilon, T* g0, T* g1, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
+    if ((flags & ~TSVGP_LIK_NOCROP) != TSVGP_LIK_SOFTMAX) return TSVGP_EINVAL;
+    if (C < 2 || C > TSVGP_MAX_BATCH || S < 1 || S > TSVGP_MC_MAX_SAMPLES || row_offset < 0) return TSVGP_EINVAL;
+    if (!epsilon && !rng_state) return TSVGP_EINVAL;
+    const dim3 grid((unsigned)(Np / TILE)), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+#define TSVGP_SOFTMAX_LAUNCH(QQ)                                                                                              \
+    hipLaunchKernelGGL((lik_map_softmax_kernel<T, QQ>), grid, block, 0, st, mean, var, Y, flags, C, S, rng_state, row_offset, \
+                       epsilon, g0, g1, ve_partial, nonpos_partial, N)
+    if (C <= 4) TSVGP_SOFTMAX_LAUNCH(1);
+    else if (C <= 8) TSVGP_SOFTMAX_LAUNCH(2);
+    else if (C <= 16) TSVGP_SOFTMAX_LAUNCH(4);
+    else TSVGP_SOFTMAX_LAUNCH(8);
+#undef TSVGP_SOFTMAX_LAUNCH
+    return launch_status();
+}
+
+template <typename T>
+int mc_normals(T* out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void* stream) {
+    if (!out || S < 1 || S > TSVGP_MC_MAX_SAMPLES || N <= 0 || C < 1 || C > TSVGP_MAX_BATCH || row_offset < 0) return TSVGP_EINVAL;
+    const int64_t per_row = S * ((C + 3) / 4);  // <= 2^28 * 8
+    if (N > (int64_t)0x7fffffff * 256 / per_row) return TSVGP_EINVAL;  // the grid's block count is 31 bits (and the product cannot wrap)
+    const int64_t total = per_row * N, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffff) return TSVGP_EINVAL;
+    hipLaunchKernelGGL(mc_normals_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, seed, draw, row_offset,
+                       S, N, C);
+    return launch_status();
+}
+
 // kdiag: HOST array of P values (one kernel variance per latent), or of ONE value with kdiag_uniform (a shared kernel, any P).
 template <typename T>
 int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y, const double* kdiag, bool kdiag_uniform,
@@ -4800,6 +5025,24 @@ int tsvgp_diag_site_step_f32(const float* mean, const float* var, const float* Y
     if (!lambda_1_f32 || !lambda_2_f32) return TSVGP_EINVAL;
     return diag_site_step<float>(mean, var, Y, lik, lik_param, lr, lambda_1, lambda_2, lambda_1_f32, lambda_2_f32, ve_partial,
                                  nonpos_partial, N, Np, P, stream);
+}
+int tsvgp_lik_map_softmax_f64(const double* mean, const double* var, const double* Y, int flags, int C, int S,
+                              const int64_t* rng_state, int64_t row_offset, const double* epsilon, double* g0, double* g1,
+                              double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_softmax<double>(mean, var, Y, flags, C, S, rng_state, row_offset, epsilon, g0, g1, ve_partial, nonpos_partial, N,
+                                   Np, stream);
+}
+int tsvgp_lik_map_softmax_f32(const float* mean, const float* var, const float* Y, int flags, int C, int S,
+                              const int64_t* rng_state, int64_t row_offset, const float* epsilon, float* g0, float* g1,
+                              double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_softmax<float>(mean, var, Y, flags, C, S, rng_state, row_offset, epsilon, g0, g1, ve_partial, nonpos_partial, N,
+                                  Np, stream);
+}
+int tsvgp_mc_normals_f64(double* out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void* stream) {
+    return mc_normals<double>(out, seed, draw, row_offset, S, N, C, stream);
+}
+int tsvgp_mc_normals_f32(float* out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void* stream) {
+    return mc_normals<float>(out, seed, draw, row_offset, S, N, C, stream);
 }
 int tsvgp_moments_f64(const double* A, const double* Tm, const double* gamma, const double* Y, double kdiag, int lik,
                       double lik_param, double* mean, double* var, double* g0, double* g1, double* ve_partial,

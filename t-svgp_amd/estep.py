@@ -15,10 +15,11 @@ Kernel sequence of ``run(..., sites=True)`` by projection route (models/tsvgp.py
     whitened:   fill -> trmm(UPPER) -> moments(UPPER, on B) -> site_accum(B)
     projected:  fill -> trmm(UPPER) -> moments(UPPER, on B) -> trmm(LOWER) -> site_accum(a)
 ``mean_only`` replaces the moments product by one HBM-bound sweep (Gaussian likelihood, TSVGP_LIK_MEANONLY).
-A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, Y [N x 1]) cannot run in the moments kernels'
-per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then ``tsvgp_lik_map_hetero``
-on them, then the site sums of the route -- ``run`` with P = 2 on one kernel, ``_run_batched`` on separate kernels, and
-a two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).
+A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``LIK_SOFTMAX``: C latents; Y [N x 1]) cannot run in
+the moments kernels' per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then its map
+(``tsvgp_lik_map_hetero`` / ``tsvgp_lik_map_softmax``) on them, then the site sums of the route -- ``run`` with P = latent_dim on
+one kernel, ``_run_batched`` on separate kernels, and a two-sweep form on the one-pass-per-latent path
+(``_run_separate_coupled``).
 """
 from __future__ import annotations
 
@@ -550,15 +551,28 @@ class EStepEngine:
                                                                       mode, self._stream()))
         return C
 
-    def _coupled_map(self, mean, var, Y, lik_id, N, Np):
-        """g0, g1 [Np, 2] (rows >= N zero), ve_partial, nonpos_partial of the coupled likelihood map (``tsvgp_lik_map_hetero_*``)
-        on mean, var [N, 2] and Y [N, 1] in the compute dtype.  The outputs are cached buffers of their own: the site sums read
-        them where they are, and a one-latent pass of the same call (``site_grads``) does not overwrite them."""
+    def _coupled_map(self, mean, var, Y, lik_id, N, Np, lik_param=None):
+        """g0, g1 [Np, P] (rows >= N zero), ve_partial, nonpos_partial of the coupled likelihood map on mean, var [N, P] and
+        Y [N, 1] in the compute dtype: ``tsvgp_lik_map_hetero_*`` (P = 2) or ``tsvgp_lik_map_softmax_*`` (P = C; ``lik_param`` is
+        the Softmax object: its sample count, row offset and device generator state, whose draw this call advances in-stream).
+        The outputs are cached buffers of their own: the site sums read them where they are, and a one-latent pass of the same
+        call (``site_grads``) does not overwrite them."""
         T = self.dtype
         nblk = Np // B.TILE
-        g0, g1 = self._get("het_g0", (Np, 2), T), self._get("het_g1", (Np, 2), T)
+        P = mean.shape[1]
+        g0, g1 = self._get("coupled_g0", (Np, P), T), self._get("coupled_g1", (Np, P), T)
         ve_partial = self._get("ve_partial", (nblk,), torch.float64)
         nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
+        if (lik_id & 0xFF) == B.LIK_SOFTMAX:
+            lik = lik_param
+            state = lik.rng_state(self.device)
+            with torch.cuda.device(self.device):
+                self._launch("tsvgp_lik_map_softmax", lambda: self._fn("tsvgp_lik_map_softmax")(
+                    mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), P, int(lik.num_monte_carlo_points), state.data_ptr(),
+                    int(lik.row_offset), None, g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np,
+                    self._stream()))
+                lik.advance()
+            return g0, g1, ve_partial, nonpos_partial
         with torch.cuda.device(self.device):
             self._launch("tsvgp_lik_map_hetero", lambda: self._fn("tsvgp_lik_map_hetero")(
                 mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(),
@@ -566,12 +580,19 @@ class EStepEngine:
         return g0, g1, ve_partial, nonpos_partial
 
     @staticmethod
-    def _check_y(Y, N, P, lik_id):
-        """Y [N, P]; a coupled likelihood (LIK_HETERO) maps two latents onto ONE target column: Y [N, 1], P = 2."""
+    def _check_y(Y, N, P, lik_id, lik_param=None):
+        """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX: C) maps its latents onto ONE target column:
+        Y [N, 1], P = latent_dim."""
         if (lik_id & 0xFF) == B.LIK_HETERO:
             if P != 2 or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
                 raise ValueError(f"the heteroskedastic likelihood needs 2 latent GPs and Y [N, 1] = [{N}, 1], got P = {P} and "
                                  f"Y {None if Y is None else tuple(Y.shape)}")
+            return
+        if (lik_id & 0xFF) == B.LIK_SOFTMAX:
+            C = getattr(lik_param, "latent_dim", None)
+            if P != C or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
+                raise ValueError(f"the Softmax likelihood needs {C} latent GPs (its latent_dim) and Y [N, 1] = [{N}, 1], got "
+                                 f"P = {P} and Y {None if Y is None else tuple(Y.shape)}")
             return
         if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:
             raise ValueError(f"Y must be [N, P] = [{N}, {P}], got {tuple(Y.shape)}")
@@ -722,7 +743,7 @@ class EStepEngine:
         N, M, P = X.shape[0], Z.shape[0], moment_Tm.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         need_g = lik_id != B.LIK_NONE
-        coupled = (lik_id & 0xFF) == B.LIK_HETERO
+        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
         if need_g:
             Y = Y.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -766,13 +787,13 @@ class EStepEngine:
             if mean_only:
                 raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
             # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
-            mean, var = self._get("het_mean", (N, P), T), self._get("het_var", (N, P), T)
+            mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
                     KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), None, kdiag, B.LIK_NONE, 0.0, mean.data_ptr(),
                     var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
                     self._stream()))
-            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np)
+            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np, lik_param)
         else:
             g0 = self._get("g0", (Np, P), T) if need_g else None
             g1 = self._get("g1", (Np, P), T) if need_g else None
@@ -816,9 +837,9 @@ class EStepEngine:
         if len(kernel.kernels) != P:
             raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
         lik_id = kw.get("lik_id", B.LIK_NONE)
-        coupled = (lik_id & 0xFF) == B.LIK_HETERO
+        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
         if coupled or Y is not None:
-            self._check_y(Y, X.shape[0], P, lik_id)
+            self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"))
         if X.shape[0] > 0:
             if prefill is not None and "KfuP" in prefill:  # the batched fill is already under way (start_fill)
                 whitened = [p for p in range(P) if self._per_latent(whiten_T, p) is not None]
@@ -872,17 +893,17 @@ class EStepEngine:
         T, dev = self.dtype, self.device
         N, P = X.shape[0], moment_Tm.shape[0]
         Np = B.round_up(N)
-        kw.pop("lik_param", None)
+        lik_param = kw.pop("lik_param", None)
         per = self._per_latent
-        mean = self._get("het_mean", (N, P), T)
-        var = self._get("het_var", (N, P), T)
+        mean = self._get("coupled_mean", (N, P), T)
+        var = self._get("coupled_var", (N, P), T)
         for p, kp in enumerate(kernel.kernels):
             st = self.run(X, None, Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1], whiten_T=per(whiten_T, p),
                           want_moments=True, **kw)
             mean[:, p] = st.mean[:, 0]
             var[:, p] = st.var[:, 0]
         Yc = Y.to(device=dev, dtype=T).contiguous()
-        g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Yc, lik_id, N, Np)
+        g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Yc, lik_id, N, Np, lik_param)
         out = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
         if want_moments:
             out.mean, out.var = mean.to(torch.float64, copy=True), var.to(torch.float64, copy=True)
@@ -1007,8 +1028,9 @@ class EStepEngine:
         stream; this call waits for it instead of filling.
         mean_only (likelihood NONE or GAUSSIAN): skip the variance product of the moments (TSVGP_LIK_MEANONLY) -- the
         Gaussian g0, g1 do not depend on it; ``var`` is then None and ``ve_sum`` NaN.
-        lik_id LIK_HETERO (P = 2, Y [N, 1]): moments of both latents with no likelihood, then the coupled map
-        (``tsvgp_lik_map_hetero_*``), then the site sums.
+        lik_id LIK_HETERO (P = 2, Y [N, 1]) or LIK_SOFTMAX (P = C, Y [N, 1], ``lik_param`` = the Softmax object): moments of all
+        latents with no likelihood, then the coupled map (``tsvgp_lik_map_hetero_*`` / ``tsvgp_lik_map_softmax_*``), then the
+        site sums.
         site_grads (lik_id NONE, one kernel): (g0, g1) [Np, P] in the compute dtype, rows >= N zero -- the site sums (and with
         ``keep_tile`` the stored product) of this pass with gradients a coupled map made elsewhere; the moments product then
         runs only for ``want_moments`` / ``keep_tile``, and ``ve_sum`` / ``nonpos`` are zero (the map's call counts them).
@@ -1045,9 +1067,9 @@ class EStepEngine:
             return st
         if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != D:
             raise ValueError(f"X must be [N, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
-        coupled = (lik_id & 0xFF) == B.LIK_HETERO
+        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
         if lik_id != B.LIK_NONE:
-            self._check_y(Y, N, P, lik_id)
+            self._check_y(Y, N, P, lik_id, lik_param)
             Y = Y.to(device=dev, dtype=T).contiguous()
         Np, Mp = B.round_up(N), B.round_up(M)
         inv_ls = kernel.inv_lengthscales(D, T, dev)
@@ -1114,13 +1136,13 @@ class EStepEngine:
             if mean_only:
                 raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
             # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
-            mean, var = self._get("het_mean", (N, P), T), self._get("het_var", (N, P), T)
+            mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
                     A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, variance, B.LIK_NONE, 0.0, mean.data_ptr(),
                     var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
                     self._stream()))
-            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np)
+            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np, lik_param)
             if want_moments:
                 mean, var = mean.clone(), var.clone()
         elif site_grads is not None and not want_moments:

@@ -1,5 +1,6 @@
-"""Likelihood objects of the hot path: ``Gaussian``, ``Bernoulli`` (probit, 20-point Gauss-Hermite) and
-``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite).
+"""Likelihood objects of the hot path: ``Gaussian``, ``Bernoulli`` (probit, 20-point Gauss-Hermite),
+``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite) and ``Softmax`` (C latents,
+Monte Carlo with an in-kernel counter-based generator: ``tsvgp_lik_map_softmax_*``).
 
 Their N-sized maps -- variational expectations and the (mean, var) gradients the E-step needs
 (reference src/models/tsvgp.py:256-263) -- run inside the fused HIP moments kernel
@@ -120,4 +121,144 @@ class HeteroskedasticTFPConditional:
             f0, f1, logw = self._grid(mu, var)
             logp = -0.5 * math.log(2 * math.pi) - f1 - 0.5 * (y[:, :, None] - f0) ** 2 * torch.exp(-2.0 * f1)
             out.append(torch.logsumexp((logp + logw).reshape(mu.shape[0], -1), dim=1))
+        return torch.cat(out)
+
+
+class Softmax:
+    """gpflow.likelihoods.Softmax(num_classes) [ext] (GPflow 2.2.1, a ``MonteCarloLikelihood``): C = num_classes latent GPs,
+    Y [N, 1] class labels 0 .. C-1, log p(y | f) = f_y - logsumexp_c f_c, every expectation a Monte Carlo average over
+    ``num_monte_carlo_points`` (100; a plain attribute, as in GPflow) draws eps [S, N, C] at f = Fmu + sqrt(Fvar) eps (reference
+    docs/notebooks/mnist.py).  The variational expectations and their gradients run on the GPU (``tsvgp_lik_map_softmax_*``)
+    with the draws made inside the kernel by the counter-based generator of include/tsvgp_hip.h: the draw for
+    (seed, draw, global row, sample, class) is a pure function of those integers.  ``draw`` counts the evaluations: each one
+    (an E-step, an ELBO, a predictive helper without ``epsilon=``) takes the draws of the current ``draw`` and advances it by one,
+    on the device too (``rng_state`` = int64 [seed, draw], advanced in-stream, so a replayed graph draws afresh).  ``row_offset`` is
+    the global number of the first TRAINING row this process passes (a row shard sets it to its shard's first row; 0 otherwise);
+    the predictive helpers number the test points they are given from 0 on every rank, whatever ``row_offset`` is.  ``seed`` and
+    ``draw`` may be assigned at any time: the device words are edited in place, so a captured graph sees the new values."""
+
+    lik_id = B.LIK_SOFTMAX
+    _CHUNK = 1 << 13  # rows per [S, rows, C] evaluation of the predictive helpers
+
+    def __init__(self, num_classes: int, seed: int = 0):
+        if int(num_classes) != num_classes or not 2 <= num_classes <= B.MAX_BATCH:
+            raise ValueError(f"Softmax: num_classes must be an integer in [2, {B.MAX_BATCH}], got {num_classes!r}")
+        self.num_classes = self.latent_dim = int(num_classes)
+        self.num_monte_carlo_points = 100
+        self.row_offset = 0
+        self._seed = int(seed)
+        self._draw = 0
+        # device -> int64 [seed, draw]: made ONCE per device and only ever edited in place -- a captured graph holds its address
+        self._states = {}
+
+    # the engine takes the likelihood's scalar through ``lik_param``; this likelihood's "parameter" is its generator state
+    @property
+    def lik_param(self):
+        return self
+
+    def _sync(self):
+        """Host (seed, draw) -> every device copy, in place (a stream-ordered copy: replays enqueued later see it)."""
+        for state in self._states.values():
+            state.copy_(torch.tensor([self._seed, self._draw], dtype=torch.int64))
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    @seed.setter
+    def seed(self, value: int):
+        self._seed = int(value)
+        self._sync()
+
+    @property
+    def draw(self) -> int:
+        return self._draw
+
+    @draw.setter
+    def draw(self, value: int):
+        self._draw = int(value)
+        self._sync()
+
+    def graph_key(self):
+        """What a captured step bakes in of this likelihood (seed and draw are read from device memory: not part of it)."""
+        return (self.num_classes, int(self.num_monte_carlo_points), int(self.row_offset))
+
+    def rng_state(self, device) -> torch.Tensor:
+        """The device words [seed, draw] the map reads: one tensor per device for the life of this object, never replaced."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        state = self._states.get(device)
+        if state is None:
+            state = self._states[device] = torch.tensor([self._seed, self._draw], dtype=torch.int64).to(device)
+        return state
+
+    def advance(self):
+        """One evaluation consumed the current draws: draw + 1 on the host and, in-stream, on the device."""
+        self._draw += 1
+        for state in self._states.values():
+            state[1:].add_(1)
+
+    def _replayed(self, draw_before: int):
+        """A graph replay ran the captured in-stream add: bring the host count level with it."""
+        self._draw = int(draw_before) + 1
+
+    def normals(self, N: int, dtype, device, row_offset=None) -> torch.Tensor:
+        """eps [S, N, C] of the current (seed, draw) for the global rows row_offset .. row_offset + N (``tsvgp_mc_normals_*``);
+        does not advance ``draw``."""
+        if dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"Softmax.normals: float64 or float32, got {dtype}")
+        S, C = int(self.num_monte_carlo_points), self.num_classes
+        out = torch.empty((S, N, C), dtype=dtype, device=device)
+        if N == 0:
+            return out
+        if out.device.type != "cuda":
+            raise B.HipExtensionError("Softmax: the Monte Carlo draws are made by a HIP kernel; pass epsilon= on a CPU tensor")
+        fn = getattr(B.lib(), "tsvgp_mc_normals_f64" if dtype == torch.float64 else "tsvgp_mc_normals_f32")
+        with torch.cuda.device(out.device):
+            B.check(fn(out.data_ptr(), self.seed, self._draw, int(self.row_offset if row_offset is None else row_offset), S, N, C,
+                       torch.cuda.current_stream(out.device).cuda_stream), "tsvgp_mc_normals")
+        return out
+
+    def _samples(self, Fmu, Fvar, epsilon, lo, hi):
+        """softmax inputs f [S, rows, C] of the rows lo .. hi."""
+        mu, var = Fmu[lo:hi], Fvar[lo:hi]
+        if epsilon is None:
+            eps = self.normals(hi - lo, mu.dtype, mu.device, row_offset=lo)  # test points count from 0
+        else:
+            eps = torch.as_tensor(epsilon, dtype=mu.dtype, device=mu.device)[:, lo:hi]
+        return mu[None] + torch.sqrt(var[None]) * eps
+
+    def _check(self, Fmu, Fvar):
+        if Fmu.dim() != 2 or Fmu.shape[1] != self.num_classes or Fvar.shape != Fmu.shape:
+            raise ValueError(f"Softmax: Fmu, Fvar must be [N, {self.num_classes}], got {tuple(Fmu.shape)} and {tuple(Fvar.shape)}")
+
+    def predict_mean_and_var(self, Fmu, Fvar, epsilon=None):
+        """E[p], E[(p - p^2) + p^2] - E[p]^2 with p = softmax(f), averaged over the draws; [N, C] each."""
+        self._check(Fmu, Fvar)
+        means, variances = [], []
+        for lo in range(0, max(Fmu.shape[0], 1), self._CHUNK):
+            p = torch.softmax(self._samples(Fmu, Fvar, epsilon, lo, min(lo + self._CHUNK, Fmu.shape[0])), dim=-1)
+            ey = p.mean(dim=0)
+            means.append(ey)
+            variances.append(((p - p * p) + p * p).mean(dim=0) - ey * ey)
+        if epsilon is None:
+            self.advance()
+        return torch.cat(means), torch.cat(variances)
+
+    def predict_log_density(self, Fmu, Fvar, Y, epsilon=None):
+        """log (1/S sum_s p(y | f^s)), summed in log space; [N]."""
+        self._check(Fmu, Fvar)
+        if Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != Fmu.shape[0]:
+            raise ValueError(f"Softmax: Y must be [N, 1] = [{Fmu.shape[0]}, 1], got {tuple(Y.shape)}")
+        classes = torch.arange(self.num_classes, dtype=Fmu.dtype, device=Fmu.device)
+        out = []
+        for lo in range(0, max(Fmu.shape[0], 1), self._CHUNK):
+            hi = min(lo + self._CHUNK, Fmu.shape[0])
+            f = self._samples(Fmu, Fvar, epsilon, lo, hi)
+            onehot = (Y[lo:hi].to(Fmu.dtype) == classes[None, :]).to(Fmu.dtype)  # [rows, C]; no label is used as an index
+            logp = torch.sum(onehot[None] * f, dim=-1) - torch.logsumexp(f, dim=-1)
+            out.append(torch.logsumexp(logp, dim=0) - math.log(logp.shape[0]))
+        if epsilon is None:
+            self.advance()
         return torch.cat(out)

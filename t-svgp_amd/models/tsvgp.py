@@ -170,8 +170,11 @@ class t_SVGP(base_SVGP):
                          num_latent_gps=num_latent_gps, num_data=num_data, compute_dtype=compute_dtype, device=device)
         self.num_inducing = self.inducing_variable.num_inducing
         self._init_variational_parameters(self.num_inducing, lambda_1, lambda_2_sqrt)
-        if self._coupled() and self.num_latent_gps != 2:
+        if self._coupled() and self.likelihood.lik_id == B.LIK_HETERO and self.num_latent_gps != 2:
             raise ValueError(f"the heteroskedastic likelihood needs num_latent_gps = 2 (its latent_dim), got {self.num_latent_gps}")
+        if self._coupled() and self.num_latent_gps != self.likelihood.latent_dim:
+            raise ValueError(f"the {type(self.likelihood).__name__} likelihood needs num_latent_gps = {self.likelihood.latent_dim} "
+                             f"(its latent_dim), got {self.num_latent_gps}")
         self.whiten = False
         self.force = force
         # Opt-in "warm" E-steps: keep chol(K_uu + jitter I), its inverse and the whitened B = K_fu L^-T between calls while
@@ -237,13 +240,15 @@ class t_SVGP(base_SVGP):
         return L @ L.transpose(-1, -2)
 
     def _coupled(self) -> bool:
-        """The likelihood couples the latents of a row (HeteroskedasticTFPConditional: two latents, one target column)."""
-        return getattr(self.likelihood, "lik_id", None) == B.LIK_HETERO
+        """The likelihood couples the latents of a row (HeteroskedasticTFPConditional: two latents, Softmax: C latents; one
+        target column)."""
+        return getattr(self.likelihood, "lik_id", None) in B.COUPLED_LIKS
 
     def _check_targets(self, X, Y):
         """Y [N, 1] under the coupled likelihood (the engine checks Y [N, P] for the others)."""
         if self._coupled() and (Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != X.shape[0]):
-            raise ValueError(f"the heteroskedastic likelihood takes Y [N, 1] = [{X.shape[0]}, 1], got {tuple(Y.shape)}")
+            name = "heteroskedastic" if self.likelihood.lik_id == B.LIK_HETERO else type(self.likelihood).__name__
+            raise ValueError(f"the {name} likelihood takes Y [N, 1] = [{X.shape[0]}, 1], got {tuple(Y.shape)}")
 
     # -- M x M prelude -----------------------------------------------------------------------------------------
     def _kmv(self, K: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -687,10 +692,10 @@ class t_SVGP(base_SVGP):
         coupled = self._coupled()
         if coupled:
             # A likelihood that couples the latents cannot ride on a per-kernel pass: one pass over all latents maps the
-            # moments of both to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
+            # moments of all of them to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
             # their columns as given (``site_grads``) for the site sums and the kernel-gradient contraction.
             stc = eng.run(X, Y, ops["Z"], self.kernel, moment_Tm=Dm, moment_mode=ops["moment_mode"], gamma=beta,
-                          lik_id=self.likelihood.lik_id | B.LIK_NOCROP, want_grads=True)
+                          lik_id=self.likelihood.lik_id | B.LIK_NOCROP, lik_param=self.likelihood.lik_param, want_grads=True)
             Np = B.round_up(X.shape[0])
             gc0 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
             gc1 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
@@ -818,11 +823,14 @@ class t_SVGP(base_SVGP):
         X, Y = self._as_device(data[0]), self._as_device(data[1])
         self._check_targets(X, Y)
         routes = self._routes(jitter)
+        draw0 = getattr(self.likelihood, "draw", None)  # Monte Carlo likelihood: a step that is run again draws the same
         if self._wants_graph(X) and self._graph_step(X, Y, lr, jitter, routes):
             return
         old_l1, old_L = self.lambda_1.value, self.lambda_2_sqrt.value
         while True:
             soft = any(r != "projected" for r in routes)
+            if draw0 is not None and self.likelihood.draw != draw0:
+                self.likelihood.draw = draw0
             try:
                 flags = self._step_device(X, Y, lr, jitter, routes)
                 verdict = self._judge(self._read_flags(flags), soft_final=soft)
@@ -1080,6 +1088,9 @@ class t_SVGP(base_SVGP):
         # buffer, so every parameter is keyed on Parameter.stamp(): identity + assign counter + the tensor's own edit counter
         # (an in-place edit of .value -- likelihood.variance.value.mul_(2), Z.value.add_(..) -- never passes through assign)
         lik_v = tuple(p.stamp() for p in vars(self.likelihood).values() if hasattr(p, "stamp"))
+        if hasattr(self.likelihood, "graph_key"):  # Monte Carlo: sample count and row offset are baked in; (seed, draw) are not
+            lik_v += self.likelihood.graph_key()
+        draw0 = getattr(self.likelihood, "draw", None)
         key = (X.data_ptr(), Y.data_ptr(), tuple(X.shape), tuple(Y.shape), X.dtype, Y.dtype, self._kernel_versions(),
                lik_v, self.inducing_variable.Z.stamp(), float(lr), float(jitter), tuple(routes), self.num_data)
         entry = self._graphs.get(key)
@@ -1126,6 +1137,8 @@ class t_SVGP(base_SVGP):
                                                         reduced=(acc2, acc1, nonpos, rows))
                     entry = dict(graph=graph, tail=tail, packed=packed, ops=ops, flags=flags, state=(sl1, sL),
                                  backup=(bl1, bL), buf=eng._buf)
+                if hasattr(self.likelihood, "rng_state"):  # the map's nodes hold this tensor's address
+                    entry["lik_state"] = self.likelihood.rng_state(self.device)
                 self._graphs[key] = entry
             except RuntimeError as exc:
                 # What torch / HIP raise when an operation is not permitted under stream capture: never try this key again
@@ -1150,6 +1163,8 @@ class t_SVGP(base_SVGP):
             sL.copy_(Lp.value)
             Lp._value = sL
         entry["graph"].replay()
+        if draw0 is not None:  # the replay ran the map's in-stream draw + 1
+            self.likelihood._replayed(draw0)
         if "tail" in entry:
             D_.all_reduce_sum(entry["packed"])
             entry["tail"].replay()
