@@ -127,6 +127,28 @@ int tsvgp_gram_to_kernel_f64(int kind, double *K, const double *xx, const double
 int tsvgp_gram_to_kernel_f32(int kind, float *K, const float *xx, const float *zz, float variance, int64_t N, int M,
                              int64_t ldk, void *stream);
 
+/* (1e) Joint predictive covariance of one latent GP over N test points (GPflow conditional(..., full_cov=True) [ext], reference
+ *     src/models/tsvgp.py:103-112, src/models/tsvgp_white.py:122, src/models/tsvgp_sites.py:179-187): a symmetric rank-Mp update
+ *     with the kernel function in the epilogue,
+ *        C[i, j] = C[j, i] = base(i, j) + sign * sum_{m < Mp} T[i, m] * T[j, m]            i, j < N
+ *        base(i, j) = variance * k_kind(r(x_i, x_j))        r as tsvgp_kernel_fill_* (same device functions, D <= 32)
+ *                   = C[i, j] as found on entry             with TSVGP_COV_ACCUMULATE in flags: only the LOWER triangle (j <= i) is
+ *                                                           read; kind, X, inv_ls, variance and D are ignored (X, inv_ls may be NULL)
+ *     T [Np x Mp] row-major is the tile tsvgp_trmm_* writes (row n = Tm a_n, rows >= N zero), X [N x D], inv_ls [D], sign -1.0 or
+ *     +1.0, C [Np x ldc] with ldc >= Np.  Np = N rounded up to 128; rows and columns >= N of C are written as 0 off the diagonal
+ *     and 1 ON it -- the identity block tsvgp_potrf_f64 asks for, so C can be factored in place.  T and C on 16-byte boundaries,
+ *     ldc * sizeof(element) a multiple of 16, Np <= 128 * 32768.  One workgroup per 128 x 128 tile of the lower block triangle
+ *     stores the tile and its transpose; the upper part of a diagonal tile is a copy of its lower part, so C == C^T bit for bit;
+ *     no atomics, fixed summation order.  The variance forms of the models:
+ *        kff - |Tm a|^2                                 one call, sign -1
+ *        kff - |b|^2 + |T2 b|^2 (t_SVGP_white)          one call on the whitened tile b, sign -1; then ACCUMULATE on T2 b, sign +1
+ *        D > 32                                         K(X, X) into C by BLAS + tsvgp_gram_to_kernel_*; then ACCUMULATE, sign -1 */
+#define TSVGP_COV_ACCUMULATE 1
+int tsvgp_cov_f64(int kind, const double *T, const double *X, const double *inv_ls, double variance, double sign, double *C,
+                  int64_t N, int64_t Np, int Mp, int D, int64_t ldc, int flags, void *stream);
+int tsvgp_cov_f32(int kind, const float *T, const float *X, const float *inv_ls, float variance, float sign, float *C, int64_t N,
+                  int64_t Np, int Mp, int D, int64_t ldc, int flags, void *stream);
+
 /* (1c) M-step gradient for D beyond tsvgp_kernel_grad_*'s sizes, GEMM form (replaces TensorFlow autodiff through Kuf [ext],
  *     reference experiments/uci_regression.py:159-160, docs/notebooks/mnist.py:117-192 with D = 784).  G [N x ldk] holds the
  *     Gram block x~ z~^T on entry; on return W = -2 variance V * k'(r2) with V = g0 beta^T - 2 g1 * U (padding zero), and

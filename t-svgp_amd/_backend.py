@@ -32,6 +32,8 @@ LIK_NOCROP = 0x100
 LIK_MEANONLY = 0x200
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 2, 3
 TRI_LOWER, TRI_UPPER, TRI_DENSE = 0, 1, 2
+COV_ACCUMULATE = 1  # TSVGP_COV_ACCUMULATE
+MC_MAX_SAMPLES = 1 << 28  # TSVGP_MC_MAX_SAMPLES
 POTRF_SUBST = 1  # TSVGP_POTRF_SUBST
 POTRF_RHS_UPPER = 2  # TSVGP_POTRF_RHS_UPPER
 POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
@@ -100,6 +102,10 @@ _PROTOTYPES = {
                                               c_int64, c_int, c_void_p]),
     "tsvgp_gram_to_kernel_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int, c_int64, c_void_p]),
     "tsvgp_gram_to_kernel_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_int64, c_void_p]),
+    "tsvgp_cov_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int64, c_int64, c_int, c_int, c_int64,
+                              c_int, c_void_p]),
+    "tsvgp_cov_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64, c_int64, c_int, c_int, c_int64,
+                              c_int, c_void_p]),
     "tsvgp_gram_to_gradw_parts": (c_int64, [c_int64, c_int]),
     "tsvgp_gram_to_gradw_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                         c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p]),

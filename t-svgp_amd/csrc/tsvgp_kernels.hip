@@ -4348,6 +4348,208 @@ int gram_to_kernel(int kind, T* K, const T* xx, const T* zz, T variance, int64_t
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// cov_kernel: the joint predictive covariance of one latent over N test points (GPflow conditional(full_cov=True) [ext],
+// reference src/models/tsvgp.py:103-112) from the stored moments product T [Np x Mp] (row n = Tm a_n, tsvgp_trmm):
+//     C[i, j] = C[j, i] = base(i, j) + sign * sum_m T[i, m] T[j, m],    base = variance * k(r(x_i, x_j))  or  C[i, j] on entry
+// a symmetric rank-Mp update with the kernel function in the epilogue.  One workgroup per 128 x 128 tile of the LOWER block
+// triangle (tile (it, jt), jt <= it, from the linear workgroup index); the k-loop is panel_kernel's dense one -- both
+// 128-row panels of T as [row][k] images, two LDS buffers, one barrier per chunk, mma_chunk_rowk -- and the epilogue
+//   * stages the two 128-row X panels (pre-scaled by inv_ls) over the operand buffers and evaluates kernel_profile on the
+//     scaled squared distance in the fill's difference form, sum_d (x~_id - x~_jd)^2 in the order of d (runtime D <= 32);
+//   * forces the padding (row or column >= N) to the identity block tsvgp_potrf_f64 asks for;
+//   * stores the tile from the accumulator layout (16 consecutive elements per row and 16 lanes), then the TRANSPOSED tile
+//     to (jt, it) through LDS in two halves of 64 columns, read back row-wise as 16-byte vectors.
+// A diagonal tile computes all of its entries but stores only those with column <= row directly and those with column > row
+// from the transposed image, so its upper part is a copy of its lower part: the matrix is symmetric bit for bit.  No atomics,
+// one workgroup per output element pair, a fixed k order: run-to-run identical.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int COV_XS = 33;  // X panel image: row stride in elements (D <= 32; odd: the 16 rows of a fragment column hit 16 banks)
+template <typename T>
+struct CovArgs {
+    const T* Tt;      // [Np x Mp]
+    const T* X;       // [N x D]
+    const T* inv_ls;  // [D]
+    T* C;             // [Np x ldc]
+    T variance, sign;
+    int64_t N, ldc;
+    int Mp, D, accumulate;
+};
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(NTHREADS, 2) void cov_kernel(CovArgs<T> a) {
+    constexpr int RS = PanelK<T>::RS, KC = PanelK<T>::KC, H = PanelK<T>::H;  // KC shadows the site kernel's constant
+    constexpr int VW = 16 / sizeof(T);                    // elements per 16-byte vector
+    constexpr int TS = sizeof(T) == 8 ? 130 : 132;        // transposed half-tile image [64 columns][128 rows]: column stride
+    static_assert(2 * TILE * COV_XS <= 4 * TILE * RS && 64 * TS <= 4 * TILE * RS, "the epilogue images reuse the operand buffers");
+    __shared__ __attribute__((aligned(16))) T lds[2][2][TILE * RS];
+    typedef typename Mfma<T>::acc_t acc_t;
+    typedef typename std::conditional<sizeof(T) == 8, v2d, v4f>::type vec_t;
+
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    // tile (it, jt), jt <= it, of the lower block triangle: workgroup b = it (it + 1) / 2 + jt
+    const int bid = blockIdx.x;
+    int it = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
+    while ((it + 1) * (it + 2) / 2 <= bid) ++it;
+    while (it * (it + 1) / 2 > bid) --it;
+    const int jt = bid - it * (it + 1) / 2;
+    const bool diag = it == jt;
+    const int64_t i0 = (int64_t)it * TILE, j0 = (int64_t)jt * TILE;
+    const int Mp = a.Mp, nchunk = Mp / KC;
+    const int srow = t >> 1, skh = t & 1;  // staging role: row of the panel, which half of the k-chunk
+
+    const T* Arow = a.Tt + (i0 + srow) * Mp + skh * H;
+    const T* Brow = a.Tt + (j0 + srow) * Mp + skh * H;
+    T* const lds_wr = &lds[0][0][srow * RS + skh * H];
+    constexpr int BUF_STRIDE = 2 * TILE * RS, OP_STRIDE = TILE * RS;
+
+    acc_t acc[2][8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int n = 0; n < 8; ++n) acc[s][n] = acc_t{0, 0, 0, 0};
+
+    T ra[H], rb[H];
+    load_run<T, H>(ra, Arow);
+    load_run<T, H>(rb, Brow);
+    store_run<T, H>(lds_wr, ra);
+    store_run<T, H>(lds_wr + OP_STRIDE, rb);
+    __syncthreads();
+    int buf = 0;
+    for (int c = 0; c < nchunk; ++c) {
+        const bool has_next = c + 1 < nchunk;
+        if (has_next) {
+            load_run<T, H>(ra, Arow + (c + 1) * KC);
+            load_run<T, H>(rb, Brow + (c + 1) * KC);
+        }
+        mma_chunk_rowk<T, 0xFF, 0xFF>(acc, &lds[buf][0][0], &lds[buf][1][0], w, lane);
+        if (has_next) {
+            store_run<T, H>(lds_wr + (buf ^ 1) * BUF_STRIDE, ra);
+            store_run<T, H>(lds_wr + (buf ^ 1) * BUF_STRIDE + OP_STRIDE, rb);
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    // ---- epilogue (every wave is past its last fragment read: the operand buffers are free)
+    T* const img = &lds[0][0][0];
+    const int D = a.D;
+    if (!a.accumulate) {
+        for (int idx = t; idx < 2 * TILE * D; idx += NTHREADS) {
+            const int side = idx / (TILE * D), rem = idx - side * (TILE * D);
+            const int rr = rem / D, d = rem - rr * D;
+            const int64_t n = (side ? j0 : i0) + rr;
+            img[(side * TILE + rr) * COV_XS + d] = n < a.N ? a.X[n * D + d] * a.inv_ls[d] : T(0);
+        }
+        __syncthreads();
+    }
+    const int lr = lane & 15;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int li = row_block(w, s) * 16 + Mfma<T>::row(lane, r);
+            const int64_t gi = i0 + li;
+            T* const Cr = a.C + gi * a.ldc + j0 + lr;
+            T base[8];
+            if (a.accumulate) {
+#pragma unroll
+                for (int n = 0; n < 8; ++n) base[n] = (!diag || n * 16 + lr <= li) ? Cr[n * 16] : T(0);
+            } else {
+                T sv[8];
+#pragma unroll
+                for (int n = 0; n < 8; ++n) sv[n] = T(0);
+                const T* xi = img + li * COV_XS;
+                const T* xj = img + (TILE + lr) * COV_XS;
+                for (int d = 0; d < D; ++d) {
+                    const T x = xi[d];
+#pragma unroll
+                    for (int n = 0; n < 8; ++n) {
+                        const T dd = x - xj[n * 16 * COV_XS + d];
+                        sv[n] += dd * dd;
+                    }
+                }
+#pragma unroll
+                for (int n = 0; n < 8; ++n) base[n] = a.variance * kernel_profile<KIND>(sv[n]);
+            }
+#pragma unroll
+            for (int n = 0; n < 8; ++n) {
+                const int lj = n * 16 + lr;
+                const int64_t gj = j0 + lj;
+                T v = base[n] + a.sign * acc[s][n][r];
+                if (gi >= a.N || gj >= a.N) v = (gi == gj) ? T(1) : T(0);  // identity block in the padding
+                acc[s][n][r] = v;
+                if (!diag || lj <= li) Cr[n * 16] = v;
+            }
+        }
+
+    // ---- the mirror image: C[j0 + c, i0 + row] = tile[row, c], 64 columns c at a time through LDS
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        __syncthreads();  // the X panels (h = 0) / the first half's image (h = 1) have been read
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int li = row_block(w, s) * 16 + Mfma<T>::row(lane, r);
+#pragma unroll
+                for (int n = 0; n < 4; ++n) img[(n * 16 + lr) * TS + li] = acc[s][4 * h + n][r];
+            }
+        __syncthreads();
+        constexpr int UPR = TILE / VW;  // 16-byte units per image column (= output row)
+        for (int u = t; u < 64 * UPR; u += NTHREADS) {
+            const int c = u / UPR, q = u - c * UPR;
+            const vec_t v = *reinterpret_cast<const vec_t*>(img + c * TS + q * VW);
+            const int lj = 64 * h + c;  // output row within the mirrored tile
+            T* const dst = a.C + (j0 + lj) * a.ldc + i0 + q * VW;
+            if (!diag) {
+                *reinterpret_cast<vec_t*>(dst) = v;
+            } else {
+#pragma unroll
+                for (int e = 0; e < VW; ++e)
+                    if (q * VW + e > lj) dst[e] = v[e];
+            }
+        }
+    }
+}
+
+template <typename T>
+int cov(int kind, const T* Tt, const T* X, const T* inv_ls, T variance, T sign, T* C, int64_t N, int64_t Np, int Mp, int D,
+        int64_t ldc, int flags, void* stream) {
+    if (flags & ~TSVGP_COV_ACCUMULATE) return TSVGP_EINVAL;
+    const bool accumulate = (flags & TSVGP_COV_ACCUMULATE) != 0;
+    if (!accumulate && ((kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) || D <= 0 ||
+                        D > 32 || !X || !inv_ls))
+        return TSVGP_EINVAL;
+    if (!(sign == T(1) || sign == T(-1))) return TSVGP_EINVAL;
+    if (!Tt || !C || N <= 0 || Np < N || Np - N >= TILE || (Np % TILE) || Mp <= 0 || (Mp % TILE)) return TSVGP_EINVAL;
+    if (Np / TILE > 32768) return TSVGP_EINVAL;  // it (it + 1) / 2 in 32 bits
+    if (ldc < Np || (ldc * sizeof(T)) % 16 != 0) return TSVGP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(Tt) & 15) != 0 || (reinterpret_cast<uintptr_t>(C) & 15) != 0) return TSVGP_EINVAL;
+    CovArgs<T> a{};
+    a.Tt = Tt;
+    a.X = X;
+    a.inv_ls = inv_ls;
+    a.C = C;
+    a.variance = variance;
+    a.sign = sign;
+    a.N = N;
+    a.ldc = ldc;
+    a.Mp = Mp;
+    a.D = accumulate ? 0 : D;
+    a.accumulate = accumulate ? 1 : 0;
+    const int64_t nt = Np / TILE;
+    const dim3 grid((unsigned)(nt * (nt + 1) / 2)), block(NTHREADS);
+    if (accumulate || kind == TSVGP_KERNEL_SE)
+        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_SE>), grid, block, 0, (hipStream_t)stream, a);
+    else if (kind == TSVGP_KERNEL_MATERN32)
+        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_MATERN32>), grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_MATERN52>), grid, block, 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
 // M-step gradient for input dimensions beyond kgrad_kernel's compile-time sizes (D > 16): the contraction with dK/d(theta, Z)
 // in the same GEMM form as the fill above.  With s = |x~|^2 + |z~|^2 - 2 G (G = x~ z~^T from the BLAS library), V = g0 beta^T -
 // 2 g1 * U and W = -2 variance V * k'(s), everything N-sized that is left is
@@ -4963,6 +5165,14 @@ int tsvgp_gram_to_kernel_f64(int kind, double* K, const double* xx, const double
 int tsvgp_gram_to_kernel_f32(int kind, float* K, const float* xx, const float* zz, float variance, int64_t N, int M,
                              int64_t ldk, void* stream) {
     return gram_to_kernel<float>(kind, K, xx, zz, variance, N, M, ldk, stream);
+}
+int tsvgp_cov_f64(int kind, const double* T, const double* X, const double* inv_ls, double variance, double sign, double* C,
+                  int64_t N, int64_t Np, int Mp, int D, int64_t ldc, int flags, void* stream) {
+    return cov<double>(kind, T, X, inv_ls, variance, sign, C, N, Np, Mp, D, ldc, flags, stream);
+}
+int tsvgp_cov_f32(int kind, const float* T, const float* X, const float* inv_ls, float variance, float sign, float* C, int64_t N,
+                  int64_t Np, int Mp, int D, int64_t ldc, int flags, void* stream) {
+    return cov<float>(kind, T, X, inv_ls, variance, sign, C, N, Np, Mp, D, ldc, flags, stream);
 }
 // vpart: one double per workgroup = ceil(Mp / 512) * Np of them (tsvgp_gram_to_gradw_parts)
 int64_t tsvgp_gram_to_gradw_parts(int64_t N, int M) {

@@ -1234,6 +1234,115 @@ class EStepEngine:
                 stats.acc2, stats.acc1 = self._site_sums(Bw, g0, g1, 1, M)
         return stats
 
+    # ------------------------------------------------------------------ joint predictions
+    def cov(self, tile: torch.Tensor, C: torch.Tensor, N: int, *, sign: float = -1.0, X=None, inv_ls=None, variance: float = 0.0,
+            kind: int = B.KERNEL_SE, accumulate: bool = False):
+        """C [Np, ldc] <- base + sign * tile tile^T (``tsvgp_cov_*``): base = variance * k(x_i, x_j) from X [N, D <= 32] and
+        inv_ls [D], or what the lower triangle of C holds (``accumulate``).  tile [Np, Mp] and C in one of the two compute
+        dtypes; rows and columns >= N of C become the identity block."""
+        Np, Mp = tile.shape
+        if C.dtype != tile.dtype or C.shape[0] != Np or C.stride(1) != 1 or tile.stride(1) != 1 or tile.stride(0) != Mp:
+            raise ValueError("cov: tile [Np, Mp] contiguous and C [Np, >= Np] with unit column stride, in one dtype")
+        D = 0 if accumulate else X.shape[1]
+        fn = self._fn("tsvgp_cov", tile.dtype)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_cov", lambda: fn(int(kind), tile.data_ptr(), _ptr(None if accumulate else X),
+                                                 _ptr(None if accumulate else inv_ls), float(variance), float(sign), C.data_ptr(),
+                                                 int(N), Np, Mp, D, C.stride(0), B.COV_ACCUMULATE if accumulate else 0,
+                                                 self._stream()))
+        return C
+
+    def full_cov(self, X, Z, kernel, *, moment_Tm, moment_mode, gamma, whiten_T=None, whiten_mode=B.TRI_UPPER,
+                 two_product=False, padded=False):
+        """Joint posterior of the latents over the rows of X [N, D] (GPflow conditional(full_cov=True) [ext]; reference
+        src/models/tsvgp.py:103-112): (mean [N, P], cov [P, N, N], nonpos) in fp64, from the operands ``run`` takes.  Per latent
+        p, with a_n the row of K(X, Z_p) (or its whitening product b_n = whiten_T a_n):
+
+            mean[:, p] = a gamma[:, p],    cov_p = K_p(X, X) - t t^T,    t_n = moment_Tm[p] a_n   (``tsvgp_trmm`` into a tile)
+            two_product (``run_two_product``'s variance):  cov = K(X, X) - b b^T + (T2 b)(T2 b)^T,   T2 = moment_Tm[0]
+
+        One shared kernel or ``SeparateIndependent`` (per-latent inv_ls, variance, moment_Tm); D > 32: K(X, X) by the GEMM-form
+        fill into cov_p, then the accumulating form of ``tsvgp_cov_*``.  One [Np, Mp] tile and one [Np, Np] matrix are live per
+        latent beside the [P, Np, Np] result.  ``nonpos``: how many diagonal entries are not positive (the assert_positive of
+        src/models/tsvgp.py:113, what ``run`` counts for the marginal variances).  ``padded``: cov is returned as the
+        [P, Np, Np] buffer itself (identity block in the padding: ``cholesky(overwrite=True)`` factors it in place; the memory
+        check then counts the factor that call returns as well)."""
+        T, dev = self.dtype, self.device
+        X = X.to(device=dev, dtype=T).contiguous()
+        Z = Z.to(device=dev, dtype=T).contiguous()
+        if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != X.shape[1]:
+            raise ValueError(f"X must be [N, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
+        N, D = X.shape
+        M = Z.shape[0]
+        P = moment_Tm.shape[0]
+        if N == 0:
+            raise ValueError("full_cov needs at least one test point")
+        separate = isinstance(kernel, SeparateIndependent)
+        if separate and len(kernel.kernels) != P:
+            raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
+        if two_product and (P != 1 or whiten_T is None or separate):
+            raise ValueError("two_product: one latent, one kernel, a whitening factor")
+        Np, Mp = B.round_up(N), B.round_up(M)
+        esz = 8 if T == torch.float64 else 4
+        need = (2 if padded else 1) * P * Np * Np * 8 + (0 if T == torch.float64 else Np * Np * esz) + 3 * Np * Mp * esz
+        free, _ = torch.cuda.mem_get_info(dev)
+        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise ValueError(f"full_cov: {P} joint covariance(s) of {N} test points need {need / 2 ** 30:.1f} GiB of device memory "
+                             f"({P} x {Np} x {Np} fp64), {free / 2 ** 30:.1f} GiB are free; predict fewer points at a time")
+        self._b_tag = None  # the operand buffers below are overwritten
+        cov = torch.empty((P, Np, Np), dtype=torch.float64, device=dev)
+        Cw = None if T == torch.float64 else torch.empty((Np, Np), dtype=T, device=dev)
+        mean = torch.empty((N, P), dtype=torch.float64, device=dev)
+        gam = self._padded_gamma(gamma, Mp, P)
+        Kfu = self._get("Kfu", (Np, Mp), T)
+        tile = self._get("Tt", (Np, Mp), T)
+        if self._side is not None and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(dev).wait_stream(self._side)
+        for p in range(P):
+            kp = kernel.kernels[p] if separate else kernel
+            inv_ls, variance = kp.inv_lengthscales(D, T, dev), kp.variance.item()
+            if p == 0 or separate:
+                self.se_fill(X, Z, inv_ls, variance, Kfu, kp.kind)
+            A = Kfu
+            wt = self._per_latent(whiten_T, p)
+            if wt is not None:
+                A = self._get("B", (Np, Mp), T)
+                self.trmm(Kfu, self._pad_square(wt, Mp, "pad_Linv"), A, whiten_mode)
+            Tm = self._pad_square(moment_Tm[p], Mp, "pad_Tm1")
+            self.trmm(A, Tm, tile, moment_mode)
+            mean[:, p] = torch.mv(A[:N], gam[:, p])  # gam: [Mp, P], rows >= M zero
+            C = cov[p] if Cw is None else Cw
+            base = dict(X=X, inv_ls=inv_ls, variance=variance, kind=kp.kind)
+            if D > MAX_INPUT_DIM:
+                self.se_fill(X, X, inv_ls, variance, C, kp.kind)  # the GEMM form (its padding is zero: the call below sets it)
+                base = dict(accumulate=True)
+            if two_product:
+                self.cov(A, C, N, sign=-1.0, **base)
+                self.cov(tile, C, N, sign=1.0, accumulate=True)
+            else:
+                self.cov(tile, C, N, sign=-1.0, **base)
+            if Cw is not None:
+                cov[p].copy_(Cw)
+        diag = cov.diagonal(dim1=-2, dim2=-1)[:, :N]
+        nonpos = (~(diag > 0)).sum().to(torch.float64)
+        return mean, (cov if padded else cov[:, :N, :N]), nonpos
+
+    def mc_normals(self, S: int, N: int, C: int, seed: int, draw: int, row_offset: int = 0) -> torch.Tensor:
+        """eps [S, N, C] fp64 of ``tsvgp_mc_normals_f64``: the draw of (seed, draw, row_offset + n, s, c)."""
+        if not (1 <= C <= B.MAX_BATCH):
+            raise ValueError(f"the normal generator takes 1 <= C <= {B.MAX_BATCH} columns, got {C}")
+        if not (1 <= S <= B.MC_MAX_SAMPLES):
+            raise ValueError(f"the normal generator takes 1 <= S <= {B.MC_MAX_SAMPLES} samples, got {S}")
+        if N < 1 or row_offset < 0 or S * N * ((C + 3) // 4) > (2 ** 31 - 1) * 256:
+            raise ValueError(f"the normal generator takes N >= 1, row_offset >= 0 and S N ceil(C / 4) <= (2^31 - 1) 256, got "
+                             f"S = {S}, N = {N}, C = {C}, row_offset = {row_offset}")
+        out = torch.empty((S, N, C), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            B.check(self.lib.tsvgp_mc_normals_f64(out.data_ptr(), int(seed), int(draw), int(row_offset), S, N, C, self._stream()),
+                    "tsvgp_mc_normals")
+        return out
+
     # ------------------------------------------------------------------ per-datum diagonal sites (t_SVGP_sites)
     def project_diag(self, X, Z, kernel, w1, w2):
         """The projection of per-datum sites onto the inducing points (reference src/util.py:188-236 with cholesky=False and

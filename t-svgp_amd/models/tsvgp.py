@@ -82,6 +82,8 @@ class base_SVGP(abc.ABC):
         self.compute_dtype = compute_dtype or default_float()
         self.device = torch.device(device) if device is not None else default_device()
         self._engine = None
+        self._engine64 = None  # predict_f_samples of an fp32 model: see _sample_engine
+        self._sample_draw = 0  # predict_f_samples(draw=None): the next draw number
         self.poll_status = True  # how the step's status read waits for the GPU: see _read_flags
         self.data_parallel = None  # None = automatic: shard-reduce whenever torch.distributed has > 1 rank
 
@@ -122,6 +124,76 @@ class base_SVGP(abc.ABC):
     def get_mean_chol_cov_inducing_posterior(self):
         """Returns the mean and cholesky factor of the covariance matrix of q(u)"""
         raise NotImplementedError
+
+    # -- joint predictions -------------------------------------------------------------------------------------
+    _BOTH_COV = "full_cov and full_output_cov together (the [N, P, N, P] covariance) are not implemented"
+
+    def _joint(self, Xnew, padded=False, engine=None):
+        """(mean [N, P], cov [P, N, N]) of predict_f(full_cov=True); ``padded``: cov as ``EStepEngine.full_cov(padded=True)``;
+        ``engine``: the launcher to use instead of the model's own."""
+        raise NotImplementedError
+
+    def _sample_engine(self):
+        """The launcher behind predict_f_samples(full_cov=True): always one with fp64 arrays.  A joint draw is a function of
+        the Cholesky factor of cov + 1e-6 I, and a smooth kernel leaves that matrix nearly singular (smallest eigenvalue ~1e-11
+        under the 1e-6 jitter): the ~1e-6 absolute error fp32 arrays leave in cov is as large as the jitter and moves the
+        trailing columns of the factor -- and with them a draw for a fixed epsilon -- by O(1e-2), although the distribution is
+        right to 1e-6.  With the covariance from fp64 arrays the draws of an fp32 model are those of an fp64 one."""
+        if self.compute_dtype == torch.float64:
+            return self._get_engine()
+        if self._engine64 is None:
+            from ..estep import EStepEngine
+
+            self._engine64 = EStepEngine(torch.float64, self.device)
+        return self._engine64
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, *, seed=0, draw=None,
+                          epsilon=None):
+        """Draws from the posterior over the latent functions at Xnew [N, D]: [S, N, P], or [N, P] when ``num_samples`` is None.
+        Follows gpflow.models.GPModel.predict_f_samples / gpflow.conditionals.util.sample_mvn of GPflow 2.2.1 [ext] -- recalled,
+        not readable where this was written:
+
+            full_cov=True:   f[s, :, p] = mean[:, p] + chol(cov_p + default_jitter() I) eps[s, :, p]    (joint over the N points)
+            full_cov=False:  f = mean + sqrt(var) eps                                                  (marginals)
+
+        The factorisation is the engine's fp64 ``tsvgp_potrf_f64`` in place on the padded covariance, which is computed with fp64
+        arrays whatever the compute dtype (``_sample_engine``); L eps is a plain matmul (S N^2 work against the N^2 M of the
+        covariance).  eps [S, N, P] comes from ``tsvgp_mc_normals_f64`` as the draw of
+        (seed, draw, row n, sample s, latent p): reproducible, independent of the compute dtype and of the launch geometry.
+        ``draw=None`` uses, and then advances, a counter of this model that starts at 0; ``epsilon`` [S, N, P] replaces the
+        generator (the hook ``Softmax`` offers) and leaves the counter alone.  Both covariance flags together are not defined."""
+        if full_cov and full_output_cov:
+            raise NotImplementedError(self._BOTH_COV)
+        eng = self._sample_engine() if full_cov else self._get_engine()  # (the marginal form needs the generator alone)
+        S = 1 if num_samples is None else int(num_samples)
+        P = int(self.num_latent_gps)
+        if not (1 <= P <= B.MAX_BATCH):
+            raise ValueError(f"predict_f_samples draws for at most {B.MAX_BATCH} latent GPs (TSVGP_MAX_BATCH), got {P}")
+        if not (1 <= S <= B.MC_MAX_SAMPLES):
+            raise ValueError(f"num_samples must lie in [1, {B.MC_MAX_SAMPLES}], got {num_samples}")
+        if full_cov:
+            mean, covp = self._joint(Xnew, padded=True, engine=eng)
+        else:
+            mean, var = self.predict_f(Xnew)  # (full_output_cov: the same draws -- the latents are independent a posteriori)
+        N = mean.shape[0]
+        if epsilon is None:
+            if draw is None:
+                draw = self._sample_draw
+                self._sample_draw = draw + 1
+            eps = eng.mc_normals(S, N, P, seed, draw)
+        else:
+            eps = torch.as_tensor(epsilon, dtype=torch.float64).to(self.device)
+            if tuple(eps.shape) != (S, N, P):
+                raise ValueError(f"epsilon must be [S, N, P] = [{S}, {N}, {P}], got {tuple(eps.shape)}")
+        if full_cov:
+            covp.diagonal(dim1=-2, dim2=-1).add_(default_jitter())  # (the padding's identity block stays definite)
+            L, info = eng.cholesky(covp, overwrite=True)
+            if float(self._read_flags(info.abs().sum().reshape(1).to(torch.float64))[0]) != 0:
+                raise FloatingPointError("Cholesky decomposition was not successful (matrix not positive definite)")
+            f = (mean.t()[:, :, None] + torch.matmul(L[:, :N, :N], eps.permute(2, 1, 0))).permute(2, 1, 0).contiguous()
+        else:
+            f = mean[None] + torch.sqrt(var)[None] * eps
+        return f[0] if num_samples is None else f
 
     def maximum_log_likelihood_objective(self, data):
         return self.elbo(data)
@@ -590,28 +662,42 @@ class t_SVGP(base_SVGP):
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """Posterior prediction at new input Xnew [N, D] (tsvgp.py:97-114): mean = k^T beta, var = knn - |D k|^2 on
         K(Xnew, Z) itself -- the reference's conditional only involves K_uu + 1e-6 I (tsvgp.py:209-211), and so does this
-        form (no factor of K_uu + 1e-9 I, no N-sized whitening)."""
-        if full_cov or full_output_cov:
-            raise NotImplementedError("full covariances are not on the E-step hot path")
+        form (no factor of K_uu + 1e-9 I, no N-sized whitening).
+        With ``full_cov`` the joint covariance over the rows of Xnew, cov [P, N, N] = K(Xnew, Xnew) - (D k)^T (D k) per latent
+        (``EStepEngine.full_cov``); with ``full_output_cov`` [N, P, P], diagonal: the latents are independent a posteriori.  With
+        more than one rank Xnew is local: there is no collective."""
+        if full_cov and full_output_cov:
+            raise NotImplementedError(self._BOTH_COV)
+        if full_cov:
+            return self._joint(Xnew)
         Xnew = self._as_device(Xnew)
         ops = self._site_operands()
         st = self._get_engine().run(Xnew, None, ops["Z"], self.kernel, moment_Tm=ops["D"], moment_mode=ops["moment_mode"],
                                     gamma=ops["beta"], want_moments=True)
         self._check_step(ops, st.nonpos)
-        return st.mean, st.var
+        return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
+
+    def _joint(self, Xnew, padded=False, engine=None):
+        ops = self._site_operands()
+        mean, cov, nonpos = (engine or self._get_engine()).full_cov(self._as_device(Xnew), ops["Z"], self.kernel, moment_Tm=ops["D"],
+                                                        moment_mode=ops["moment_mode"], gamma=ops["beta"], padded=padded)
+        self._check_step(ops, nonpos)
+        return mean, cov
 
     def new_predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """Same moments straight from the sites: var = knn - |D k|^2 (tsvgp.py:215-232, util.py:91-185)."""
-        if full_cov or full_output_cov:
-            raise NotImplementedError("full covariances are not on the E-step hot path")
+        if full_cov and full_output_cov:
+            raise NotImplementedError(self._BOTH_COV)
         if isinstance(self.kernel, SeparateIndependent):
             # "todo : make broadcastable" (tsvgp.py:214): the reference form only covers one shared kernel
             raise NotImplementedError("new_predict_f is not broadcastable over separate kernels in the reference")
+        if full_cov:
+            return self._joint(Xnew)
         ops = self._site_operands()
         st = self._get_engine().run(self._as_device(Xnew), None, ops["Z"], self.kernel, moment_Tm=ops["D"],
                                     moment_mode=ops["moment_mode"], gamma=ops["beta"], want_moments=True)
         self._check_step(ops, st.nonpos)
-        return st.mean, st.var
+        return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
 
     def moments_and_gradients(self, data):
         """The N-sized intermediates of one E-step at the current state, without updating it (tsvgp.py:246-263):

@@ -58,6 +58,7 @@ class t_SVGP_sites(base_SVGP):
     _cond_k6 = t_SVGP_white._cond_k6
     _use_direct = t_SVGP_white._use_direct
     _routed = t_SVGP_white._routed
+    _white_joint = t_SVGP_white._joint
 
     def __init__(self, data, kernel, likelihood, inducing_variable, *, mean_function=None, num_latent_gps: int = 1,
                  lambda_1=None, lambda_2=None, num_latent=1, compute_dtype=None, device=None, projection="auto",
@@ -174,9 +175,12 @@ class t_SVGP_sites(base_SVGP):
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """tsvgp_sites.py:180-191: gpflow conditional(q_mu, q_sqrt = chol S, white=False), which is
-        mean = k^T R^-1 l, var = kff - k^T (K6^-1 - R^-1) k with R = K6 + L + 1e-9 I: t_SVGP_white's moments on (l, L)."""
-        if full_cov or full_output_cov:
-            raise NotImplementedError("full covariances are not on the E-step hot path")
+        mean = k^T R^-1 l, var = kff - k^T (K6^-1 - R^-1) k with R = K6 + L + 1e-9 I: t_SVGP_white's moments on (l, L).
+        ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1]."""
+        if full_cov and full_output_cov:
+            raise NotImplementedError(self._BOTH_COV)
+        if full_cov:
+            return self._joint(Xnew)
         l, L, _ = self._project()
         Xd = self._as_device(Xnew)
 
@@ -184,9 +188,14 @@ class t_SVGP_sites(base_SVGP):
             ops = self._operands(lambda_1=l, lambda_2=L, direct=direct, two_product=two_product)
             st = self._run(Xd, None, ops, B.LIK_NONE, want_moments=True)
             self._check(ops, st.nonpos)
-            return st.mean, st.var
+            return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
 
         return self._routed(go)
+
+    def _joint(self, Xnew, padded=False, engine=None):
+        """t_SVGP_white's joint covariance on the projected (l, L)."""
+        l, L, _ = self._project()
+        return self._white_joint(Xnew, padded, engine, lambda_1=l, lambda_2=L)
 
     def predict_y(self, Xnew):
         return self.likelihood.predict_mean_and_var(*self.predict_f(Xnew))

@@ -283,16 +283,33 @@ class t_SVGP_white(base_SVGP):
         return 0.5 * (log_det + torch.sum(tmp * tmp) - float(A.shape[0]) + torch.sum(torch.square(LA.transpose(-1, -2) @ Rl)))
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
-        """tsvgp_white.py:122-132."""
-        if full_cov or full_output_cov:
-            raise NotImplementedError("full covariances are not on the E-step hot path")
+        """tsvgp_white.py:122-132.  ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1]."""
+        if full_cov and full_output_cov:
+            raise NotImplementedError(self._BOTH_COV)
+        if full_cov:
+            return self._joint(Xnew)
         Xd = self._as_device(Xnew)
 
         def go(direct, two_product):
             ops = self._operands(direct=direct, two_product=two_product)
             st = self._run(Xd, None, ops, B.LIK_NONE, want_moments=True)
             self._check(ops, st.nonpos)
-            return st.mean, st.var
+            return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
+
+        return self._routed(go)
+
+    def _joint(self, Xnew, padded=False, engine=None, lambda_1=None, lambda_2=None):
+        """The joint covariance on the route ``predict_f`` takes: K(X, X) - t t^T with t the moments product of the route (on k
+        for the direct one, on b = U6^-1 k for the whitened one), or the two-product form K(X, X) - b b^T + (T2 b)(T2 b)^T."""
+        Xd = self._as_device(Xnew)
+
+        def go(direct, two_product):
+            ops = self._operands(lambda_1=lambda_1, lambda_2=lambda_2, direct=direct, two_product=two_product)
+            mean, cov, nonpos = (engine or self._get_engine()).full_cov(
+                Xd, ops["Z"], self.kernel, moment_Tm=ops["moment_Tm"], moment_mode=ops["moment_mode"], gamma=ops["gamma"],
+                whiten_T=ops["whiten_T"], whiten_mode=B.TRI_UPPER, two_product=bool(ops.get("two_product")), padded=padded)
+            self._check(ops, nonpos)
+            return mean, cov
 
         return self._routed(go)
 
