@@ -93,6 +93,56 @@ def test_elbo_gradients_isotropic_lengthscale_and_larger_problem():
     assert abs(float(grads["variance"]) - ref_var) < 2e-6 * abs(ref_var)
 
 
+def test_elbo_gradients_two_column_tiles_and_dt16():
+    """M = 520 > 512 and D = 12: the fused gradient kernel's second column tile (partials indexed across tiles) and its
+    16-dimension instantiation with padded dimensions, neither of which the cases above reach.  Matern-5/2, one lengthscale per
+    dimension; variance, every lengthscale, the noise and Z on both sides of the tile edge against central differences."""
+    rng = np.random.RandomState(44)
+    N, M, D = 600, 520, 12
+    X, Y, _ = synthetic(N=N, M=M, D=D, P=1, lik="gaussian", seed=9)
+    Z = rng.randn(M, D) * 1.2
+    ls, var, noise = np.full(D, 3.0), 1.3, 0.2
+    hip, ora = _models("Matern52", "gaussian", 1, Z, ls, var, noise, N)
+    for _ in range(2):
+        hip.natgrad_step((X, Y), lr=0.8)
+        ora.natgrad_step((X, Y), lr=0.8)
+    state = (ora.lambda_1.copy(), ora.lambda_2_sqrt.copy())
+    elbo, grads = hip.elbo_and_grads((X, Y))
+    f = lambda **kw: _oracle_elbo("Matern52", "gaussian", 1, kw.get("Z", Z), kw.get("ls", ls), kw.get("var", var),
+                                  kw.get("noise", noise), N, state, (X, Y))
+    assert abs(float(elbo) - f()) < 1e-9 * abs(f())
+    h = 1e-5
+
+    def fd(key, base, idx=None):
+        step = h * max(1.0, abs(float(base if idx is None else base[idx])))
+        up, dn = np.array(base, dtype=np.float64, copy=True), np.array(base, dtype=np.float64, copy=True)
+        if idx is None:
+            return (f(**{key: float(up + step)}) - f(**{key: float(dn - step)})) / (2 * step)
+        up[idx] += step
+        dn[idx] -= step
+        return (f(**{key: up}) - f(**{key: dn})) / (2 * step)
+
+    ref_var = fd("var", var)
+    scale = max(abs(ref_var), 1.0)
+    print(f"variance: hip {float(grads['variance']):.10e} fd {ref_var:.10e}")
+    assert abs(float(grads["variance"]) - ref_var) < 2e-6 * scale
+    g_ls = grads["lengthscales"].cpu().numpy()
+    assert g_ls.shape == (D,)
+    for d in range(D):
+        ref = fd("ls", ls, d)
+        print(f"lengthscale {d}: hip {g_ls[d]:.10e} fd {ref:.10e}")
+        assert abs(g_ls[d] - ref) < 2e-6 * max(abs(ref), scale), (d, g_ls[d], ref)
+    g_Z = grads["Z"].cpu().numpy()
+    assert g_Z.shape == (M, D)
+    for (m_, d) in [(0, 0), (511, 11), (512, 0), (519, 5)]:
+        ref = fd("Z", Z, (m_, d))
+        print(f"Z[{m_}, {d}]: hip {g_Z[m_, d]:.10e} fd {ref:.10e}")
+        assert abs(g_Z[m_, d] - ref) < 2e-6 * max(abs(ref), scale), (m_, d, g_Z[m_, d], ref)
+    ref = fd("noise", noise)
+    print(f"noise: hip {float(grads['likelihood_variance']):.10e} fd {ref:.10e}")
+    assert abs(float(grads["likelihood_variance"]) - ref) < 2e-6 * max(abs(ref), scale)
+
+
 def test_em_loop_matches_oracle_driven_loop():
     """The E/M loop of the reference's driver (experiments/uci_regression.py:132-160) on the C1-style 1-D problem:
     the HIP loop (analytic gradients) against the same loop driven by the oracle with finite-difference gradients and the
