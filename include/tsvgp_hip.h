@@ -355,6 +355,38 @@ int tsvgp_potrf_solve_f64(double *A, int M, int lda, int batch, int64_t stride, 
 int tsvgp_flip_transpose_f64(const double *src, int lds, int64_t sstride, double *dst, int ldd, int64_t dstride, int M, int batch,
                              void *stream);
 
+/* (6v) t_VGP, the exact N x N model (reference src/models/tvgp.py:72-160), around (6a).  With s = sqrt|lambda_2| (s_n = 0 for
+ *     n >= N), y~ = lambda_1 / lambda_2, K~ = variance * k_kind(X, X) + jitter I (r as tsvgp_kernel_fill_*, same device functions,
+ *     D <= 32) the model factors B = I + s s^T * K~ = L L^T (eigenvalues >= 1: the plain factorisation) and needs
+ *     C = (K~ s) L^-T and z = L^-1 (s y~).  tsvgp_vgp_system_f64 writes, in one launch, the stacked operand of (6a),
+ *     S [(2 Np + 128) x lds] with Np = N rounded up to 128, lds >= Np and even, S on a 16-byte boundary:
+ *        rows [0, Np)         B[i, j] = [i == j] + s_i s_j K~[i, j]: the lower block triangle of 128 x 128 tiles, diagonal tiles in
+ *                             full (what (6) reads; the blocks above the diagonal are NOT written); the padding is the identity block
+ *        rows [Np, 2 Np)      R[n, j] = K~[n, j] s_j, zero for n >= N or j >= N
+ *        rows [2 Np, + 128)   row 0: s_j y~_j (0 for j >= N); the other 127 rows zero
+ *     (columns >= Np of a wider buffer are not touched).  One workgroup per tile of the lower block triangle; the kernel function
+ *     is evaluated once per pair.  TSVGP_VGP_NO_ROWS: rows [0, Np) only (S may then end there) -- for a caller that brings its
+ *     own right-hand sides (predict_f: K(Xnew, X) s by tsvgp_kernel_fill_f64).  After
+ *     tsvgp_potrf_solve_f64(S, Np, lds, 1, (2 Np + 128) lds, info, work, Np + 128, 0, stream) rows [Np, 2 Np) hold C and row 2 Np
+ *     holds z.  lambda_1, lambda_2: [>= N] fp64 (DiagSites' padded state). */
+#define TSVGP_VGP_NO_ROWS 1
+int tsvgp_vgp_system_f64(int kind, const double *X, const double *inv_ls, double variance, double jitter, const double *lambda_1,
+                         const double *lambda_2, double *S, int64_t N, int64_t Np, int D, int64_t lds, int flags, void *stream);
+/*     The sweep over the solved rows (reference src/models/tvgp.py:90-96, :104-107, :146-157), HBM bound: for n < N
+ *        q = sum_{i < K} C[n, i]^2,   mean = sum_{i < K} C[n, i] z[i]  (z == NULL: 0),   var = kdiag - q
+ *     C [Np x ldc] (all Np rows are read), K even and <= ldc, ldc even, C and z on 16-byte boundaries.  lik = TSVGP_LIK_NONE: mean
+ *     and / or var [N] are written, nothing else is read (predict_f's variance: C = K(Xnew, X) s L^-T, z NULL).  lik =
+ *     TSVGP_LIK_GAUSSIAN (lik_param = noise variance) or TSVGP_LIK_BERNOULLI: g0, g1, ve of tsvgp_lik_map_* at (mean, var, Y[n]),
+ *     never cropped (the reference has no crop here); ve and E_q log t = -1/2 lambda_2 ((y~ - mean)^2 + var) of the sites found on
+ *     entry are summed into ve_partial / eqt_partial [Np / 128] (fp64, one per 128 rows); then, when beta != 0, in place
+ *        lambda_1 <- (1 - beta) lambda_1 + beta (g0 - 2 g1 mean),     lambda_2 <- (1 - beta) lambda_2 - 2 beta g1
+ *     (beta == 0 stores nothing: the sites stay bit for bit; 0 <= beta <= 1; z, Y, lambda_1, lambda_2 and both partials required;
+ *     mean, var may be NULL).  nonpos_partial [Np / 128]: rows with var <= 0 or a non-finite mean, g0 or g1.  No atomics, a
+ *     summation order fixed by the shape, 16-byte loads. */
+int tsvgp_vgp_rows_f64(const double *C, int64_t ldc, const double *z, const double *Y, double *lambda_1, double *lambda_2,
+                       double kdiag, int lik, double lik_param, double beta, double *mean, double *var, double *ve_partial,
+                       double *eqt_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, int K, void *stream);
+
 /* (6b) The same factorisation plus the inverse factor: X[b] = inv(L[b]) (lower triangular, exact zeros above) and
  *     Xt[b] = X[b]^T, both [batch x M x M] row-major (leading dimension M).  The inverted diagonal blocks the panel
  *     solve needs anyway are combined by the 2x2 block recursion inv([[A,0],[C,B]]) = [[A^-1,0],[-B^-1 C A^-1, B^-1]]

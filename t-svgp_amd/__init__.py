@@ -9,11 +9,11 @@ from .base import Parameter, default_float, default_jitter
 from .inducing_variables import InducingPoints, SharedIndependentInducingVariables, inducingpoint_wrapper
 from .kernels import Matern32, Matern52, SeparateIndependent, SquaredExponential
 from .likelihoods import Bernoulli, Gaussian, HeteroskedasticTFPConditional, Softmax
-from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white
+from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white, t_VGP
 from .sites import DenseSites, DiagSites, Sites
 
 __all__ = [
-    "t_SVGP", "t_SVGP_white", "t_SVGP_sites", "base_SVGP", "DenseSites", "DiagSites", "Sites", "SquaredExponential", "Gaussian", "Bernoulli", "HeteroskedasticTFPConditional", "Softmax",
+    "t_SVGP", "t_SVGP_white", "t_SVGP_sites", "t_VGP", "base_SVGP", "DenseSites", "DiagSites", "Sites", "SquaredExponential", "Gaussian", "Bernoulli", "HeteroskedasticTFPConditional", "Softmax",
     "InducingPoints",
     "SeparateIndependent", "SharedIndependentInducingVariables", "Matern32", "Matern52",
     "inducingpoint_wrapper", "Parameter", "default_float", "default_jitter", "HipExtensionError", "build_library",

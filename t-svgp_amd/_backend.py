@@ -39,6 +39,7 @@ POTRF_RHS_UPPER = 2  # TSVGP_POTRF_RHS_UPPER
 POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
 POTRF_DIAG_V2 = 8  # TSVGP_POTRF_DIAG_V2
 POTRF_FUSE = 16  # TSVGP_POTRF_FUSE
+VGP_NO_ROWS = 1  # TSVGP_VGP_NO_ROWS
 ABI_VERSION = 5  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
 
 _lib = None
@@ -155,6 +156,10 @@ _PROTOTYPES = {
     "tsvgp_site_accum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "tsvgp_potrf_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "tsvgp_potrf_solve_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "tsvgp_vgp_system_f64": (c_int, [c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                     c_int64, c_int, c_void_p]),
+    "tsvgp_vgp_rows_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_double, c_double,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_flip_transpose_f64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_potrf_inv_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p]),

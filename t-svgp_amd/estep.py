@@ -1420,3 +1420,61 @@ class EStepEngine:
         with torch.cuda.device(dev):
             self._launch("tsvgp_diag_site_step", lambda: self._fn("tsvgp_diag_site_step")(*args))
         return ve_partial.sum(), nonpos_partial.sum().to(torch.float64)
+
+    # ------------------------------------------------------------------ t_VGP: the exact N x N model (models/tvgp.py)
+    def vgp_system(self, X, kernel, l1, l2, jitter: float, rhs_rows=None):
+        """The stacked operand of ``vgp_factor`` (``tsvgp_vgp_system_f64``): B = I + s s^T * (K(X, X) + jitter I) in rows
+        [0, Np) of a cached fp64 buffer S [Np + rhs, Np] and, with ``rhs_rows`` None, the model's own right-hand sides behind it
+        (K~ s in rows [Np, 2 Np), s y~ in row 2 Np; rhs = Np + 128).  ``rhs_rows`` = r: B only (TSVGP_VGP_NO_ROWS) and r rows --
+        a multiple of 128 -- left for the caller to fill.  X [N, D <= 32] fp64 on the device; l1, l2: the padded site state
+        [Np, 1].  Returns (S, Np)."""
+        N, D = X.shape
+        if D > MAX_INPUT_DIM:
+            raise ValueError(f"t_VGP builds its N x N system in one fused kernel: D <= {MAX_INPUT_DIM}, got {D}")
+        Np = B.round_up(N)
+        own = rhs_rows is None
+        rhs = Np + B.TILE if own else int(rhs_rows)
+        if rhs % B.TILE or l1.shape[0] < Np or l2.shape[0] < Np or X.dtype != torch.float64 or not X.is_contiguous():
+            raise ValueError("vgp_system: X fp64 contiguous, sites padded to Np rows, rhs_rows a multiple of 128")
+        S = self._get("vgp_S", (Np + rhs, Np), torch.float64)
+        inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_vgp_system", lambda: self.lib.tsvgp_vgp_system_f64(
+                int(kernel.kind), X.data_ptr(), inv_ls.data_ptr(), kernel.variance.item(), float(jitter), l1.data_ptr(),
+                l2.data_ptr(), S.data_ptr(), N, Np, D, Np, 0 if own else B.VGP_NO_ROWS, self._stream()))
+        return S, Np
+
+    def vgp_factor(self, S, Np: int):
+        """B = L L^T in place and the rows below it -> rows L^-T (``tsvgp_potrf_solve_f64``; B has eigenvalues >= 1: the plain
+        panels).  Returns info [1] int32 (no host synchronisation)."""
+        rows, lds = S.shape
+        info = torch.empty(1, dtype=torch.int32, device=self.device)
+        work = self._get("potrf_work", (1, 128 * 128), torch.float64)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_potrf", lambda: self.lib.tsvgp_potrf_solve_f64(
+                S.data_ptr(), Np, lds, 1, rows * lds, info.data_ptr(), work.data_ptr(), rows - Np, self.potrf_flags, self._stream()))
+        return info
+
+    def vgp_rows(self, C, N: int, kdiag: float, *, z=None, Y=None, l1=None, l2=None, lik_id=B.LIK_NONE, lik_param=0.0, beta=0.0,
+                 want_mean=False, want_var=False):
+        """One launch of ``tsvgp_vgp_rows_f64`` over the solved rows C [Np, ldc] (a view of S): mean = C z, var = kdiag - |C|^2
+        per row, and with a likelihood the sums of ve and of E_q log t and the in-place update of the padded sites l1, l2 by the
+        step ``beta`` (0: the sites are not written).  Returns (mean [N, 1] | None, var [N, 1] | None, ve_sum, eqt_sum, nonpos):
+        fp64 device tensors, the sums as scalars."""
+        Np, K = C.shape
+        nblk = Np // B.TILE
+        mean = torch.empty((N, 1), dtype=torch.float64, device=self.device) if want_mean else None
+        var = torch.empty((N, 1), dtype=torch.float64, device=self.device) if want_var else None
+        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
+        eqt_partial = self._get("eqt_partial", (nblk,), torch.float64)
+        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
+        lik = lik_id != B.LIK_NONE
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_vgp_rows", lambda: self.lib.tsvgp_vgp_rows_f64(
+                C.data_ptr(), C.stride(0), _ptr(z), _ptr(Y), _ptr(l1), _ptr(l2), float(kdiag), int(lik_id), float(lik_param),
+                float(beta), _ptr(mean), _ptr(var), ve_partial.data_ptr() if lik else None, eqt_partial.data_ptr() if lik else None,
+                nonpos_partial.data_ptr(), N, Np, K, self._stream()))
+        nonpos = nonpos_partial.sum().to(torch.float64)
+        if not lik:
+            return mean, var, None, None, nonpos
+        return mean, var, ve_partial.sum(), eqt_partial.sum(), nonpos
