@@ -4,8 +4,10 @@ Y = sin(15 X) + unit noise, SE kernel with variance 0.3 and lengthscale 0.1, M =
 site per datum and factors the N x N system, ``t_SVGP`` projects onto the inducing points.  Five natural-gradient steps of 0.9
 each, as the notebook takes; under a Gaussian likelihood t_VGP's ELBO then sits at the exact log marginal likelihood, which is the
 ceiling of t_SVGP's.  Prints both ELBOs and how far the sparse posterior is from the exact one on a 100-point grid.
+``--train K`` then trains the kernel and the noise variance of the exact model for K iterations of ``training.em_fit_vgp``
+(E-steps on the sites, Adam M-steps on ``t_VGP.elbo_and_grads``) and prints the ELBO per iteration and the parameters found.
 
-    python examples/exact_vgp.py [--steps 5] [--lr 0.9] [--seed 0]
+    python examples/exact_vgp.py [--steps 5] [--lr 0.9] [--seed 0] [--train 0]
 """
 import argparse
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--lr", type=float, default=0.9)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--train", type=int, default=0, help="iterations of em_fit_vgp on the exact model (0: the kernel stays as given)")
     args = ap.parse_args()
     X, Y, Z = regression_1d(seed=args.seed)
     kernel = lambda: gp.SquaredExponential(variance=0.3, lengthscales=0.1)
@@ -43,6 +46,13 @@ def main():
     print(f"t_SVGP ELBO {float(sparse.elbo((X, Y))):.4f}   (M = {Z.shape[0]} inducing points)")
     print(f"on {grid.shape[0]} grid points: max |mean difference| {float((me - ms).abs().max()):.4f}, "
           f"max |sd difference| {float((ve.sqrt() - vs.sqrt()).abs().max()):.4f}")
+    if args.train > 0:
+        from tsvgp_amd import training
+
+        logf, _ = training.em_fit_vgp(exact, args.train, n_e_steps=2, n_m_steps=20, beta=args.lr, adam_lr=0.05)
+        print("t_VGP  ELBO per training iteration: " + " ".join(f"{e:.4f}" for e in logf))
+        print(f"trained: variance {exact.kernel.variance.item():.4f}, lengthscale {float(exact.kernel.lengthscales.value):.4f}, "
+              f"noise variance {exact.likelihood.variance.item():.4f}")
 
 
 if __name__ == "__main__":

@@ -387,6 +387,23 @@ int tsvgp_vgp_rows_f64(const double *C, int64_t ldc, const double *z, const doub
                        double kdiag, int lik, double lik_param, double beta, double *mean, double *var, double *ve_partial,
                        double *eqt_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, int K, void *stream);
 
+/* (6w) The hyperparameter gradient of t_VGP: the contraction of a symmetric N x N weight matrix with d K(X, X) / d theta, formed
+ *     pair by pair (no N x N x D array).  With G[i, j] = W[i, j] + 1/2 (a_i c_j + c_i a_j), x~ = X * inv_ls, s_ij = |x~_i - x~_j|^2
+ *     and K = variance * f(s) (f, f' as tsvgp_kernel_fill_* / tsvgp_kernel_grad_*; kind, D <= 32 as (6v)):
+ *        column 0       sum_ij G[i, j] f(s_ij)                                           = d / d variance  (dK / d variance = f)
+ *        column 1 + d   sum_ij G[i, j] variance f'(s_ij) (-2) (x~_id - x~_jd)^2          = l_d * d / d lengthscale_d
+ *     over all i, j < N -- so the caller divides column 1 + d by lengthscale_d (and adds the columns for one shared lengthscale).
+ *     W [Np x ldw], ldw >= Np and even, on a 16-byte boundary, symmetric: only the lower block triangle of 128 x 128 tiles is read,
+ *     diagonal tiles in full (the convention tsvgp_vgp_system_f64 writes); a tile below the diagonal counts twice.  Rows and
+ *     columns >= N contribute nothing whatever W holds there (NaN included); X [N x D], a, c [>= N] are not read beyond N.
+ *     part [tsvgp_vgp_kernel_grad_parts(Np, D)] doubles = (ntiles + 1) rows of 1 + Dp, ntiles = nt (nt + 1) / 2, nt = Np / 128,
+ *     Dp = D rounded up to 1, 2, 4, 8, 16 or 32: row k < ntiles the weighted sums of tile k (row-major over the lower block
+ *     triangle), row ntiles their totals, added by a second small kernel in an order fixed by ntiles.  No atomics: two calls
+ *     agree bit for bit.  One workgroup per tile, 16-byte row-contiguous loads of W; bound by the one read of W. */
+int64_t tsvgp_vgp_kernel_grad_parts(int64_t Np, int D);
+int tsvgp_vgp_kernel_grad_f64(int kind, const double *X, const double *inv_ls, double variance, const double *W, int64_t ldw,
+                              const double *a, const double *c, int64_t N, int64_t Np, int D, double *part, void *stream);
+
 /* (6b) The same factorisation plus the inverse factor: X[b] = inv(L[b]) (lower triangular, exact zeros above) and
  *     Xt[b] = X[b]^T, both [batch x M x M] row-major (leading dimension M).  The inverted diagonal blocks the panel
  *     solve needs anyway are combined by the 2x2 block recursion inv([[A,0],[C,B]]) = [[A^-1,0],[-B^-1 C A^-1, B^-1]]

@@ -160,6 +160,9 @@ _PROTOTYPES = {
                                      c_int64, c_int, c_void_p]),
     "tsvgp_vgp_rows_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_double, c_double,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "tsvgp_vgp_kernel_grad_parts": (c_int64, [c_int64, c_int]),
+    "tsvgp_vgp_kernel_grad_f64": (c_int, [c_int, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                          c_int, c_void_p, c_void_p]),
     "tsvgp_flip_transpose_f64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_potrf_inv_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p]),

@@ -4879,6 +4879,186 @@ int vgp_rows(const double* C, int64_t ldc, const double* z, const double* Y, dou
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// vgp_kgrad_kernel: the N x N contraction behind d ELBO / d (variance, lengthscales) of t_VGP (models/tvgp.py: elbo_and_grads).
+// With G[i, j] = W[i, j] + 1/2 (a_i c_j + c_i a_j) symmetric, x~ = X / lengthscales, s = |x~_i - x~_j|^2 and K = variance f(s):
+//     part[tile][0]     = weight * sum_{i, j in tile} G[i, j] f(s)                                      (dK / d variance = f)
+//     part[tile][1 + d] = weight * sum_{i, j in tile} G[i, j] variance f'(s) (-2) (x~_id - x~_jd)^2     (= l_d dK / d l_d)
+// over the tiles of the lower block triangle, weight = 2 off the diagonal (G and K are symmetric; only the tiles vgp_system_kernel
+// writes are read), f and f' from kernel_profile_grad as kgrad_kernel.  G is formed in registers: no N x N x D array and no second
+// N x N buffer.  HBM bound on the one read of W: lane l of wave w owns the columns 2 l, 2 l + 1 (16-byte loads, a wave reads one
+// 1 KB row segment per instruction) and the rows w, w + 4, ..; the column panel of x~ sits in LDS, the row's x~ is a wave-uniform
+// LDS read.  A pair with i >= N or j >= N is masked by a select (whatever W holds there, NaN included), a, c and X are not read
+// beyond N.  Every sum has an order fixed by the shape: lane sums, a butterfly, the four waves in order; vgp_kgrad_reduce_kernel
+// then adds the tiles' partials in a fixed order (256 strided chains, a tree over them).  No atomics.
+// DT = D padded to a compile-time size (padded dimensions are zeros on both sides).
+// ---------------------------------------------------------------------------------------------------------------
+struct VgpKgradArgs {
+    const double* X;       // [N x D]
+    const double* inv_ls;  // [D]
+    const double* W;       // [Np x ldw]
+    const double* a;       // [>= N]
+    const double* c;       // [>= N]
+    double* part;          // [(ntiles + 1) x (1 + DT)]
+    double variance;
+    int64_t N, ldw;
+    int D;
+};
+
+template <int KIND, int DT>
+__global__ __launch_bounds__(NTHREADS) void vgp_kgrad_kernel(VgpKgradArgs a) {
+    constexpr int XS = DT + 1;  // odd row stride (DT >= 2): a wave's 64 column reads spread over the banks
+    constexpr int VG_CH = 64;   // rows of x~ staged per pass (with DT = 32 the two full panels would not fit 64 KB of LDS)
+    __shared__ double xj[TILE * XS];
+    __shared__ double xi[VG_CH * DT];  // wave-uniform reads: no padding needed
+    __shared__ double aj[TILE], cj[TILE], ai[TILE], ci[TILE];
+    __shared__ double red[NTHREADS / 64][DT + 1];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int bid = blockIdx.x;
+    int it = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
+    while ((it + 1) * (it + 2) / 2 <= bid) ++it;
+    while (it * (it + 1) / 2 > bid) --it;
+    const int jt = bid - it * (it + 1) / 2;
+    const int64_t i0 = (int64_t)it * TILE, j0 = (int64_t)jt * TILE;
+    const int D = a.D;
+
+    for (int idx = t; idx < TILE * DT; idx += NTHREADS) {
+        const int rr = idx / DT, d = idx - rr * DT;
+        const int64_t nj = j0 + rr;
+        xj[rr * XS + d] = (d < D && nj < a.N) ? a.X[nj * D + d] * a.inv_ls[d] : 0.0;
+    }
+    if (t < TILE) {
+        const int64_t nj = j0 + t, ni = i0 + t;
+        aj[t] = nj < a.N ? a.a[nj] : 0.0;
+        cj[t] = nj < a.N ? a.c[nj] : 0.0;
+        ai[t] = ni < a.N ? a.a[ni] : 0.0;
+        ci[t] = ni < a.N ? a.c[ni] : 0.0;
+    }
+    __syncthreads();
+
+    const int c = 2 * lane;
+    const int64_t gj = j0 + c;
+    const bool live0 = gj < a.N, live1 = gj + 1 < a.N;
+    const double a0 = aj[c], a1 = aj[c + 1], c0 = cj[c], c1 = cj[c + 1];
+    double acc[DT + 1];
+#pragma unroll
+    for (int d = 0; d <= DT; ++d) acc[d] = 0.0;
+    const double m2v = -2.0 * a.variance;
+
+    for (int ch = 0; ch < TILE / VG_CH; ++ch) {
+        if (ch) __syncthreads();  // the previous pass has read its rows
+        for (int idx = t; idx < VG_CH * DT; idx += NTHREADS) {
+            const int rr = idx / DT, d = idx - rr * DT;
+            const int64_t ni = i0 + ch * VG_CH + rr;
+            xi[idx] = (d < D && ni < a.N) ? a.X[ni * D + d] * a.inv_ls[d] : 0.0;
+        }
+        __syncthreads();
+        for (int lr = w; lr < VG_CH; lr += 4) {
+            const int li = ch * VG_CH + lr;
+            const int64_t gi = i0 + li;
+            if (gi >= a.N) break;  // wave-uniform (the rows of a wave ascend); no barrier inside this loop
+            const v2d wv = *reinterpret_cast<const v2d*>(a.W + gi * a.ldw + gj);
+            const double ar = ai[li], cr = ci[li];
+            const double g0 = live0 ? wv[0] + 0.5 * (ar * c0 + cr * a0) : 0.0;
+            const double g1 = live1 ? wv[1] + 0.5 * (ar * c1 + cr * a1) : 0.0;
+            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                const double x = xi[lr * DT + d];
+                const double d0 = x - xj[c * XS + d], d1 = x - xj[(c + 1) * XS + d];
+                s0 += d0 * d0;
+                s1 += d1 * d1;
+            }
+            double f0, df0, f1, df1;
+            kernel_profile_grad<KIND>(s0, f0, df0);
+            kernel_profile_grad<KIND>(s1, f1, df1);
+            acc[0] += g0 * f0 + g1 * f1;
+            const double q0 = g0 * m2v * df0, q1 = g1 * m2v * df1;
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                const double x = xi[lr * DT + d];
+                const double d0 = x - xj[c * XS + d], d1 = x - xj[(c + 1) * XS + d];
+                acc[1 + d] += q0 * (d0 * d0) + q1 * (d1 * d1);
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d <= DT; ++d) {
+        double v = acc[d];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[w][d] = v;
+    }
+    __syncthreads();
+    if (t <= DT) {
+        const double v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+        a.part[(int64_t)bid * (DT + 1) + t] = (it == jt ? 1.0 : 2.0) * v;
+    }
+}
+
+// the totals of the tiles' partials, row ntiles of part: one workgroup per column, thread t the tiles t, t + 256, .. in order
+__global__ __launch_bounds__(NTHREADS) void vgp_kgrad_reduce_kernel(double* part, int64_t ntiles, int cols) {
+    __shared__ double red[NTHREADS];
+    const int t = threadIdx.x, col = blockIdx.x;
+    double v = 0.0;
+    for (int64_t k = t; k < ntiles; k += NTHREADS) v += part[k * cols + col];
+    red[t] = v;
+    __syncthreads();
+    for (int o = NTHREADS / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) part[ntiles * cols + col] = red[0];
+}
+
+inline int vgp_kgrad_dpad(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
+
+template <int KIND>
+void vgp_kgrad_launch(const VgpKgradArgs& a, int DT, dim3 grid, hipStream_t st) {
+    const dim3 block(NTHREADS);
+    switch (DT) {
+        case 1: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 1>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 2>), grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 4>), grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 8>), grid, block, 0, st, a); break;
+        case 16: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 16>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 32>), grid, block, 0, st, a); break;
+    }
+}
+
+int vgp_kernel_grad(int kind, const double* X, const double* inv_ls, double variance, const double* W, int64_t ldw, const double* av,
+                    const double* cv, int64_t N, int64_t Np, int D, double* part, void* stream) {
+    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
+    if (!X || !inv_ls || !W || !av || !cv || !part || N <= 0 || D <= 0 || D > 32) return TSVGP_EINVAL;
+    if (Np < N || Np - N >= TILE || (Np % TILE) || Np / TILE > 32768) return TSVGP_EINVAL;
+    if (ldw < Np || (ldw % 2) != 0 || (reinterpret_cast<uintptr_t>(W) & 15) != 0) return TSVGP_EINVAL;
+    VgpKgradArgs a{};
+    a.X = X;
+    a.inv_ls = inv_ls;
+    a.W = W;
+    a.a = av;
+    a.c = cv;
+    a.part = part;
+    a.variance = variance;
+    a.N = N;
+    a.ldw = ldw;
+    a.D = D;
+    const int DT = vgp_kgrad_dpad(D);
+    const int64_t nt = Np / TILE, ntiles = nt * (nt + 1) / 2;
+    const dim3 grid((unsigned)ntiles);
+    hipStream_t st = (hipStream_t)stream;
+    if (kind == TSVGP_KERNEL_SE)
+        vgp_kgrad_launch<TSVGP_KERNEL_SE>(a, DT, grid, st);
+    else if (kind == TSVGP_KERNEL_MATERN32)
+        vgp_kgrad_launch<TSVGP_KERNEL_MATERN32>(a, DT, grid, st);
+    else
+        vgp_kgrad_launch<TSVGP_KERNEL_MATERN52>(a, DT, grid, st);
+    if (hipGetLastError() != hipSuccess) return TSVGP_ELAUNCH;
+    hipLaunchKernelGGL(vgp_kgrad_reduce_kernel, dim3((unsigned)(DT + 1)), dim3(NTHREADS), 0, st, part, ntiles, DT + 1);
+    return launch_status();
+}
+
 // M-step gradient for input dimensions beyond kgrad_kernel's compile-time sizes (D > 16): the contraction with dK/d(theta, Z)
 // in the same GEMM form as the fill above.  With s = |x~|^2 + |z~|^2 - 2 G (G = x~ z~^T from the BLAS library), V = g0 beta^T -
 // 2 g1 * U and W = -2 variance V * k'(s), everything N-sized that is left is
@@ -5651,6 +5831,16 @@ int tsvgp_vgp_rows_f64(const double* C, int64_t ldc, const double* z, const doub
                        double* eqt_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, int K, void* stream) {
     return vgp_rows(C, ldc, z, Y, lambda_1, lambda_2, kdiag, lik, lik_param, beta, mean, var, ve_partial, eqt_partial,
                     nonpos_partial, N, Np, K, stream);
+}
+// part: one row of 1 + Dp doubles per tile of the lower block triangle, and one more for the totals
+int64_t tsvgp_vgp_kernel_grad_parts(int64_t Np, int D) {
+    if (Np <= 0 || (Np % TILE) || Np / TILE > 32768 || D <= 0 || D > 32) return -1;
+    const int64_t nt = Np / TILE;
+    return (nt * (nt + 1) / 2 + 1) * (1 + vgp_kgrad_dpad(D));
+}
+int tsvgp_vgp_kernel_grad_f64(int kind, const double* X, const double* inv_ls, double variance, const double* W, int64_t ldw,
+                              const double* a, const double* c, int64_t N, int64_t Np, int D, double* part, void* stream) {
+    return vgp_kernel_grad(kind, X, inv_ls, variance, W, ldw, a, c, N, Np, D, part, stream);
 }
 int tsvgp_flip_transpose_f64(const double* src, int lds, int64_t sstride, double* dst, int ldd, int64_t dstride, int M, int batch,
                              void* stream) {

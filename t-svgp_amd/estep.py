@@ -1422,18 +1422,22 @@ class EStepEngine:
         return ve_partial.sum(), nonpos_partial.sum().to(torch.float64)
 
     # ------------------------------------------------------------------ t_VGP: the exact N x N model (models/tvgp.py)
-    def vgp_system(self, X, kernel, l1, l2, jitter: float, rhs_rows=None):
+    def vgp_system(self, X, kernel, l1, l2, jitter: float, rhs_rows=None, extra_rows: int = 0):
         """The stacked operand of ``vgp_factor`` (``tsvgp_vgp_system_f64``): B = I + s s^T * (K(X, X) + jitter I) in rows
         [0, Np) of a cached fp64 buffer S [Np + rhs, Np] and, with ``rhs_rows`` None, the model's own right-hand sides behind it
         (K~ s in rows [Np, 2 Np), s y~ in row 2 Np; rhs = Np + 128).  ``rhs_rows`` = r: B only (TSVGP_VGP_NO_ROWS) and r rows --
         a multiple of 128 -- left for the caller to fill.  X [N, D <= 32] fp64 on the device; l1, l2: the padded site state
-        [Np, 1].  Returns (S, Np)."""
+        [Np, 1].  ``extra_rows`` (a multiple of 128): that many further rows behind the model's own, left for the caller to fill
+        (``vgp_grad_operands``: diag(s)).  Returns (S, Np)."""
         N, D = X.shape
         if D > MAX_INPUT_DIM:
             raise ValueError(f"t_VGP builds its N x N system in one fused kernel: D <= {MAX_INPUT_DIM}, got {D}")
         Np = B.round_up(N)
         own = rhs_rows is None
         rhs = Np + B.TILE if own else int(rhs_rows)
+        if extra_rows % B.TILE or extra_rows < 0:
+            raise ValueError("vgp_system: extra_rows a non-negative multiple of 128")
+        rhs += int(extra_rows)
         if rhs % B.TILE or l1.shape[0] < Np or l2.shape[0] < Np or X.dtype != torch.float64 or not X.is_contiguous():
             raise ValueError("vgp_system: X fp64 contiguous, sites padded to Np rows, rhs_rows a multiple of 128")
         S = self._get("vgp_S", (Np + rhs, Np), torch.float64)
@@ -1478,3 +1482,60 @@ class EStepEngine:
         if not lik:
             return mean, var, None, None, nonpos
         return mean, var, ve_partial.sum(), eqt_partial.sum(), nonpos
+
+    def vgp_grad_operands(self, X, kernel, l1, l2, jitter: float):
+        """The factorisation of ``vgp_system`` / ``vgp_factor`` with diag(s), s = sqrt|lambda_2|, riding as Np further plain
+        right-hand-side rows behind the model's own: they come out as V = diag(s) L^-T (V V^T = (K~ + |Lambda|^-1)^-1).  One
+        stacked buffer S [(3 Np + 128) x Np]; L, C and z are where ``vgp_system`` + ``vgp_factor`` leave them.  Returns
+        (S, Np, info, V [Np, Np], a view of rows [2 Np + 128, 3 Np + 128))."""
+        N = X.shape[0]
+        S, Np = self.vgp_system(X, kernel, l1, l2, jitter, extra_rows=B.round_up(N))
+        V = S[2 * Np + B.TILE:]
+        V.zero_()
+        torch.diagonal(V)[:N] = torch.sqrt(torch.abs(l2[:N, 0]))
+        return S, Np, self.vgp_factor(S, Np), V
+
+    def lik_grads(self, mean, var, Y, lik_id, lik_param):
+        """g0 = d ve / d mean, g1 = d ve / d var [N] at (mean, var, Y) [N, 1] fp64, never cropped (``tsvgp_lik_map_f64`` with
+        TSVGP_LIK_NOCROP): the gradients of the bound, not the site update's."""
+        N = mean.shape[0]
+        Np = B.round_up(N)
+        nblk = Np // B.TILE
+        g0, g1 = self._get("vgp_g0", (Np, 1), torch.float64), self._get("vgp_g1", (Np, 1), torch.float64)
+        ve_partial = self._get("vgp_lik_ve", (nblk,), torch.float64)
+        nonpos_partial = self._get("vgp_lik_nonpos", (nblk,), torch.int32)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_lik_map", lambda: self.lib.tsvgp_lik_map_f64(
+                mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id) | B.LIK_NOCROP, float(lik_param), g0.data_ptr(),
+                g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, 1, self._stream()))
+        return g0[:N, 0], g1[:N, 0]
+
+    def vgp_kernel_grad(self, X, kernel, W, a, c):
+        """sum_ij G[i, j] dK(X, X)[i, j] / d theta, G = W + 1/2 (a c^T + c a^T), for theta = variance and the lengthscales
+        (``tsvgp_vgp_kernel_grad_f64``).  X [N, D <= 32] fp64; W [Np, ldw] fp64 symmetric, of which the lower block triangle of
+        128 x 128 tiles is read; a, c [>= N] fp64.  Returns (dvar 0-dim, dls [D]): dls[d] is the derivative with respect to
+        lengthscale d of an ARD kernel; for one shared lengthscale the caller adds them up."""
+        N, D = X.shape
+        if D > MAX_INPUT_DIM:
+            raise ValueError(f"vgp_kernel_grad: D <= {MAX_INPUT_DIM}, got {D}")
+        Np = B.round_up(N)
+        if (W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] < Np or W.shape[1] < Np or W.stride(1) != 1 or W.stride(0) % 2
+                or X.dtype != torch.float64 or not X.is_contiguous()):
+            raise ValueError("vgp_kernel_grad: X fp64 contiguous, W fp64 [Np, >= Np] with unit column stride and an even row stride")
+        a = a.reshape(-1).to(torch.float64).contiguous()
+        c = c.reshape(-1).to(torch.float64).contiguous()
+        if a.shape[0] < N or c.shape[0] < N:
+            raise ValueError("vgp_kernel_grad: a, c need N entries")
+        size = int(self.lib.tsvgp_vgp_kernel_grad_parts(Np, D))
+        if size <= 0:
+            raise ValueError(f"vgp_kernel_grad: no partials layout for Np = {Np}, D = {D}")
+        part = self._get("vgp_kgrad_part", (size,), torch.float64)
+        inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_vgp_kernel_grad", lambda: self.lib.tsvgp_vgp_kernel_grad_f64(
+                int(kernel.kind), X.data_ptr(), inv_ls.data_ptr(), kernel.variance.item(), W.data_ptr(), W.stride(0), a.data_ptr(),
+                c.data_ptr(), N, Np, D, part.data_ptr(), self._stream()))
+        nt = Np // B.TILE
+        cols = size // (nt * (nt + 1) // 2 + 1)
+        total = part[size - cols:]
+        return total[0].clone(), total[1:1 + D] * inv_ls

@@ -20,7 +20,19 @@ Deviations from the reference: alpha is recomputed from the CURRENT sites (cache
 parameters) where the reference predicts with whatever the last ``elbo`` / update left in ``q_alpha``, i.e. the alpha of the sites
 BEFORE its last update; a failed factorisation or a non-positive posterior variance raises FloatingPointError and leaves the sites
 as they were; ``full_cov=True`` returns [1, N*, N*] as the sibling models do.  One latent GP, the Zero mean function, one
-stationary kernel with D <= 32 and a likelihood over one latent; hyperparameter gradients are not implemented.
+stationary kernel with D <= 32 and a likelihood over one latent.
+
+``elbo_and_grads`` differentiates that ELBO with respect to the kernel variance, the lengthscales and the Gaussian noise variance
+with the sites held fixed (reference tests/models/test_tvgp.py: test_gradient_wrt_hyperparameters; TensorFlow autodiff there).
+With V = diag(s) L^-T (diag(s) rides through the factorisation as Np further right-hand-side rows), P = V V^T =
+(K~ + |Lambda|^-1)^-1, alpha = V z and A^T = I - K~ P = I - C V^T, the posterior moves by dm = A^T dK~ alpha and dv_n = a_n^T dK~ a_n
+(a_n column n of A).  With g0, g1 = d ve / d (m, v), never cropped, h0 = g0 - lambda_2 (y~ - m), h1 = g1 + 1/2 lambda_2, u = A h0 and
+c = 1/2 alpha + u:
+
+    d ELBO / d K~ = G = W + 1/2 (alpha c^T + c alpha^T),   W = A diag(h1) A^T - 1/2 P,   d ELBO / d theta = sum_ij G_ij dK_ij / d theta
+
+The two N^3 products go through the BLAS library; the contraction with dK / d theta is ``tsvgp_vgp_kernel_grad_f64``, which forms G
+in registers from W, alpha and c.  At a fixed point of the sites h0 = h1 = 0 and G = 1/2 (alpha alpha^T - P).
 """
 from __future__ import annotations
 
@@ -130,8 +142,70 @@ class t_VGP:
     def maximum_log_likelihood_objective(self, *args, **kwargs) -> torch.Tensor:
         return self.elbo()
 
+    def elbo_and_grads(self):
+        """The ELBO at the current sites and its gradient with respect to the kernel variance, the lengthscales and (Gaussian
+        likelihood) the noise variance, with the sites held fixed (module docstring).  Returns (elbo, {"variance",
+        "lengthscales", "likelihood_variance" (Gaussian only)}): gradients of the ELBO with respect to the constrained parameter
+        values, ``lengthscales`` in the parameter's own shape -- the names and conventions of ``t_SVGP.elbo_and_grads``.  The
+        sites are not modified; a failed factorisation or a non-positive variance raises FloatingPointError."""
+        eng = self._get_engine()
+        X, Y = self.data
+        N = self.num_data
+        k, lik = self.kernel, self.likelihood
+        l1, l2 = self.sites.padded()
+        jitter = default_jitter()
+        S, Np, info, V = eng.vgp_grad_operands(X, k, l1, l2, jitter)
+        self._judge_info(info)
+        z = S[2 * Np, :N]
+        log_Z = -0.5 * torch.dot(z, z) - torch.sum(torch.log(torch.diagonal(S[:N, :N])))
+        mean, var, ve, eqt, nonpos = eng.vgp_rows(S[Np:2 * Np], N, k.variance.item() + jitter, z=S[2 * Np], Y=Y, l1=l1, l2=l2,
+                                                  lik_id=lik.lik_id, lik_param=lik.lik_param, beta=0.0, want_mean=True,
+                                                  want_var=True)
+        bad = float(nonpos)
+        if bad:
+            raise FloatingPointError(f"non-positive posterior variance or non-finite moments at {bad:.0f} point(s)")
+        elbo = log_Z - eqt + ve
+        g0, g1 = eng.lik_grads(mean, var, Y, lik.lik_id, lik.lik_param)
+        lam1, lam2, m, v = l1[:N, 0], l2[:N, 0], mean[:, 0], var[:, 0]
+        h0 = g0 - lam2 * (lam1 / lam2 - m)
+        h1 = g1 + 0.5 * lam2
+        Vn, C = V[:N, :N], S[Np:Np + N, :N]
+        alpha = Vn @ z
+        At = C @ Vn.transpose(0, 1)  # A^T = I - C V^T
+        At.neg_()
+        torch.diagonal(At).add_(1.0)
+        c = 0.5 * alpha + At.transpose(0, 1) @ h0
+        W = eng._get("vgp_W", (Np, Np), default_float())  # rows and columns >= N are never read as values
+        Wn = W[:N, :N]
+        Wn.addmm_(At.transpose(0, 1), h1[:, None] * At, beta=0.0)  # A diag(h1) A^T
+        Wn.addmm_(Vn, Vn.transpose(0, 1), alpha=-0.5)  # - 1/2 P
+        dvar, dls = eng.vgp_kernel_grad(X, k, W, alpha, c)
+        ls_shape = tuple(k.lengthscales.value.shape)
+        grads = {"variance": dvar, "lengthscales": dls.sum().reshape(ls_shape) if k.lengthscales.value.numel() == 1
+                 else dls.reshape(ls_shape)}
+        if lik.lik_id == B.LIK_GAUSSIAN:
+            s2 = lik.lik_param
+            res = Y[:, 0] - m
+            grads["likelihood_variance"] = torch.sum(-0.5 / s2 + 0.5 * (res * res + v) / (s2 * s2))
+        return elbo, grads
+
     def training_loss(self) -> torch.Tensor:
         return -self.elbo()
+
+    def training_loss_closure(self, *, compile=False):
+        """``gpflow.models.InternalDataTrainingLossMixin.training_loss_closure`` [ext]: a zero-argument callable returning the
+        negative ELBO (the model owns its data).  ``compile`` is accepted and ignored: there is no tracing compiler here."""
+        return self.training_loss
+
+    @property
+    def trainable_parameters(self):
+        """The parameters an M-step trains: kernel variance and lengthscales and the likelihood's parameters; the sites are not
+        trainable and there is no inducing variable."""
+        out = [par for par in (self.kernel.variance, self.kernel.lengthscales) if par.trainable]
+        out += [par for par in vars(self.likelihood).values() if hasattr(par, "trainable") and par.trainable]
+        return tuple(out)
+
+    trainable_variables = trainable_parameters  # GPflow's name for the unconstrained counterparts
 
     def update_variational_parameters(self, beta=0.05) -> None:
         """One natural-gradient step on every datum's sites (tvgp.py:114-160), in place; the kernel and likelihood parameters are

@@ -54,19 +54,22 @@ def trainable_parameters(model) -> dict:
             out[f"kernels.{p}.lengthscales"] = (k.lengthscales, 0.0)
     else:
         out = {"variance": (kern.variance, 0.0), "lengthscales": (kern.lengthscales, 0.0)}
-    out["Z"] = (model.inducing_variable.Z, None)
+    if getattr(model, "inducing_variable", None) is not None:  # t_VGP has none
+        out["Z"] = (model.inducing_variable.Z, None)
     if hasattr(model.likelihood, "variance"):
         out["likelihood_variance"] = (model.likelihood.variance, VARIANCE_LOWER_BOUND)
     return out
 
 
-def m_step(model, data, optimizer: Adam, steps: int = 1):
+def m_step(model, data=None, optimizer: Adam = None, steps: int = 1):
     """``steps`` Adam steps on the negative ELBO with the sites fixed (experiments/uci_regression.py:159-160).
-    Returns the ELBO seen at the last gradient evaluation."""
+    ``data`` None: the model owns its data (``t_VGP``).  Returns the ELBO seen at the last gradient evaluation."""
+    if optimizer is None:
+        raise ValueError("m_step needs an optimizer (training.Adam)")
     params = trainable_parameters(model)
     elbo = None
     for _ in range(steps):
-        elbo, grads = model.elbo_and_grads(data)
+        elbo, grads = model.elbo_and_grads() if data is None else model.elbo_and_grads(data)
         u, gu = {}, {}
         for name, (par, lower) in params.items():
             theta = par.value.detach().to(torch.float64)
@@ -96,4 +99,21 @@ def em_fit(model, data, iterations: int, n_e_steps: int = 8, n_m_steps: int = 20
         if test_data is not None:
             nlpd.append(-float(torch.mean(model.predict_log_density(test_data))))
         m_step(model, data, optimizer, n_m_steps)
+    return logf, nlpd
+
+
+def em_fit_vgp(model, iterations: int, n_e_steps: int = 8, n_m_steps: int = 20, beta: float = 0.8, adam_lr: float = 0.1,
+               test_data=None, optimizer: Adam = None):
+    """``em_fit`` for a model that owns its data (``t_VGP``): per iteration ``n_e_steps`` calls of
+    ``update_variational_parameters(beta)``, the ELBO (and test NLPD) logged, then ``n_m_steps`` M-steps on the kernel and
+    likelihood parameters.  Returns (logf, nlpd)."""
+    optimizer = optimizer or Adam(adam_lr)
+    logf, nlpd = [], []
+    for _ in range(iterations):
+        for _ in range(n_e_steps):
+            model.update_variational_parameters(beta)
+        logf.append(float(model.elbo()))
+        if test_data is not None:
+            nlpd.append(-float(torch.mean(model.predict_log_density(test_data))))
+        m_step(model, None, optimizer, n_m_steps)
     return logf, nlpd
