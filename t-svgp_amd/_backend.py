@@ -19,7 +19,8 @@ HEADER_PATH = os.path.join(_ROOT, "include", "tsvgp_hip.h")
 SOURCES = [os.path.join(CSRC, "tsvgp_kernels.hip"), os.path.join(CSRC, "tsvgp_chol.hip")]
 HEADERS = [HEADER_PATH, os.path.join(CSRC, "tsvgp_chol.h")]
 # per-source compiler switches: the small-matrix kernels keep their MFMA accumulators in VGPRs (the AGPR form the compiler
-# picks for a one-wave-per-SIMD kernel ran the panel kernel's dependent MFMA chains ~1.5x slower, tools/diag2_lab.hip)
+# picks for a one-wave-per-SIMD kernel ran the panel kernel's dependent MFMA chains ~1.5x slower in a stamped lab build of that
+# kernel, since removed: code in git history, its other results in profiles/r05_potrf_diag_lab.txt)
 SOURCE_FLAGS = {"tsvgp_chol.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 TILE = 128
@@ -58,7 +59,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I", os.path.join(_ROOT, "include"), "-I", CSRC]
-    flags += os.environ.get("TSVGP_HIPCC_FLAGS", "").split()  # experiment builds (tools/): extra -D switches
+    flags += os.environ.get("TSVGP_HIPCC_FLAGS", "").split()  # A/B builds (tools/ab_builds.sh): extra compiler flags
     # build beside the target and rename: a concurrent loader (several ranks of one job) never maps a half-written file
     tag = f"{os.getpid()}.tmp"
     objs = [f"{src}.{tag}.o" for src in SOURCES]

@@ -31,7 +31,8 @@
 // and the inverted 16 x 16 diagonal tiles also go to `work` in the register layout for chol_panel2_kernel (below), which
 // solves the panel rows by substitution over the eight 16-wide column blocks -- MFMAs on tile registers again.
 // tools/emul_diag2.py is the lane-level NumPy model of this file (index algebra and barrier placement checked against
-// numpy.linalg); tools/diag2_lab.hip times the kernel alone with in-kernel stamps.
+// numpy.linalg).  The timings quoted below come from a stamped lab build of the kernel alone (removed; code in git history,
+// result in profiles/r05_potrf_diag_lab.txt).
 
 #include "tsvgp_chol.h"
 
@@ -47,9 +48,7 @@ constexpr int NTILES = NTC * (NTC + 1) / 2;  // lower tiles of the block
 constexpr int D2_THREADS = 512;
 constexpr size_t D2_LDS_BYTES = ((size_t)NTILES * 4 * 64 + 4 * 64) * sizeof(double);  // 36 tiles + 4 operands: 75 776
 
-#ifndef TSVGP_CHOL_PRIO
 #define TSVGP_CHOL_PRIO 3
-#endif
 
 __device__ __forceinline__ v4d mfma(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 
@@ -89,7 +88,7 @@ __device__ __forceinline__ v4d tile_identity(int n, int G) {
 // Global traffic of a tile goes as whole rows -- lane l moves the two doubles (row l / 8 + 8 h, columns 2 (l % 8), + 1), 16 bytes,
 // eight 128-byte row segments per wave instruction -- and changes layout in LDS.  In the register layout itself (lane (n, G): 16
 // rows x 32 bytes per 8-byte instruction) a tile's four loads or stores took ~160-240 cycles EACH to issue and queued on the
-// CU's one address path: 10 us of staging and ~1 us per block column in front of the pivot wave (tools/diag2_lab.hip).
+// CU's one address path: 10 us of staging and ~1 us per block column in front of the pivot wave (profiles/r05_potrf_diag_lab.txt).
 typedef double v2d_ __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int tile_word(int row, int c) { return (c >> 2) * 64 + row + 16 * (c & 3); }  // [n][c] in the image
 // tile (i, j), i >= j, of the block whose lower triangle is stored at Ab -> LDS image tp; a diagonal tile is mirrored
@@ -136,13 +135,6 @@ __device__ __forceinline__ void tile_zero_global(double* __restrict__ Ab, int ld
     for (int h = 0; h < 2; ++h)
         *reinterpret_cast<v2d_*>(Ab + (size_t)(16 * i + (lane >> 3) + 8 * h) * lda + 16 * j + 2 * (lane & 7)) = v2d_{0.0, 0.0};
 }
-
-#ifdef TSVGP_DIAG_D2  // tools/diag2_lab.hip: s_memtime stamps of the pivot wave, 16 per block column + 8
-__device__ unsigned long long* g_d2_dbg = nullptr;
-#define D2_STAMP(i) { if (w == 0 && g_d2_dbg) { const unsigned long long tt_ = __builtin_amdgcn_s_memtime(); if (lane == 0) g_d2_dbg[i] = tt_; } }
-#else
-#define D2_STAMP(i)
-#endif
 
 // v shifted up by SH lanes inside every row of 16 lanes (DPP row_shr: lane l reads lane l - SH), zeros shifted in
 template <int SH>
@@ -294,7 +286,6 @@ __global__ __launch_bounds__(D2_THREADS) void potrf_diag2_kernel(double* __restr
     double* Wb = work + (size_t)b * NB * NB;
     const int sel_s = n < 4 ? (n > G ? 4 * n + G : 4 * G + n) : -1;
     const bool lower = G <= n;
-    D2_STAMP(0)
     v4d D, X;
     Helper h;
     int bad = 0;
@@ -323,7 +314,6 @@ __global__ __launch_bounds__(D2_THREADS) void potrf_diag2_kernel(double* __restr
         h.t = tile_read(tile_ptr(S, 0, w), lane);
     }
     for (int s = 0; s < NTC; ++s) {
-        D2_STAMP(8 + 16 * s + 0)
         if (w == NTC - 1) X = tile_identity(n, G);  // (the inverse tile rides in wave 7: one MFMA per group off the pivot wave)
 #define D2_GROUP(Q)                                                               \
         if (w == 0) {                                                             \
@@ -335,8 +325,7 @@ __global__ __launch_bounds__(D2_THREADS) void potrf_diag2_kernel(double* __restr
         }                                                                         \
         lds_barrier(); /* G(s, Q) */                                                \
         if (w != 0) helper_group<Q>(h, S, aopbuf, Ab, lda, Wb, s, w, lane, n, G); \
-        if (w == NTC - 1) tile_step<Q>(X, aopbuf[Q * 64 + lane]);                 \
-        D2_STAMP(8 + 16 * s + 1 + Q)
+        if (w == NTC - 1) tile_step<Q>(X, aopbuf[Q * 64 + lane]);
         D2_GROUP(0)
         D2_GROUP(1)
         D2_GROUP(2)
@@ -355,9 +344,7 @@ __global__ __launch_bounds__(D2_THREADS) void potrf_diag2_kernel(double* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) Wb[(size_t)NTILES * 256 + s * 256 + (4 * r + G) * 16 + n] = X[r];
         }
-        D2_STAMP(8 + 16 * s + 5)
         lds_barrier();  // E(s)
-        D2_STAMP(8 + 16 * s + 6)
         if (w != 0) {
             // column s is complete in LDS: its tiles go to the matrix, one per helper (tile (s + u, s) by wave 1 + u % 7), and the
             // phase's fourth trailing job runs -- both in the shadow of the next column's first pivot chain
@@ -375,10 +362,8 @@ __global__ __launch_bounds__(D2_THREADS) void potrf_diag2_kernel(double* __restr
                 h.la = v4d{0.0, 0.0, 0.0, 0.0};
             }
         }
-        D2_STAMP(8 + 16 * s + 7)
     }
     if (t == 0 && (k == 0 || (bad != 0 && info[b] == 0))) info[b] = bad != 0 ? k * NB + bad : 0;  // (block 0 initialises the status word)
-    D2_STAMP(1)
 }
 
 // Panel rows below the diagonal block (and the right-hand-side rows that ride along, tsvgp_potrf_solve_f64):
@@ -425,7 +410,7 @@ __device__ __forceinline__ void p2_stage(v4d (&U)[NTC], const P2Ops<S>& o) {
 // Strip I/O: a strip's 16 rows x 128 columns travel as whole 512-byte row halves (16 bytes per lane, two rows per
 // instruction) and change layout in LDS -- read straight in the register layout (lane (n, G), tile s, register r <->
 // [n][16 s + 4 r + G]: 16 x 32-byte pieces per 8-byte wave load) a strip took 6.2 us to load and 3.2 us to store, more than
-// its 144 MFMAs (tools/diag2_lab.hip).  One 64-column half at a time through a private [16][66] image per wave: row stride
+// its 144 MFMAs (profiles/r05_potrf_diag_lab.txt).  One 64-column half at a time through a private [16][66] image per wave: row stride
 // 66 doubles = 4 banks (mod 64 dwords), so the 8-byte register-layout accesses of a half wave hit 32 different bank pairs.
 constexpr int P2_LD = 66;
 typedef double v2d_ __attribute__((ext_vector_type(2)));
@@ -480,12 +465,6 @@ __global__ __launch_bounds__(P2_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     if (strip >= nstrips) return;
     double* Arow0 = A + (size_t)blockIdx.y * stride + (size_t)((k + 1) * NB + 16 * strip) * lda + (size_t)k * NB;
     const double* Wb = work + (size_t)blockIdx.y * NB * NB;
-#ifdef TSVGP_DIAG_D2
-#define P2_STAMP(i) { if (g_d2_dbg && strip == 0 && blockIdx.y == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long tt_ = __builtin_amdgcn_s_memtime(); if (lane == 0) g_d2_dbg[200 + i] = tt_; } }
-#else
-#define P2_STAMP(i)
-#endif
-    P2_STAMP(0)
     P2Ops<0> o0;
     P2Ops<1> o1;
     P2Ops<2> o2;
@@ -499,9 +478,7 @@ __global__ __launch_bounds__(P2_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     strip_load(U, Arow0, lda, imgs[w], lane, n, G);
     p2_load(o1, Wb, lane, n, G);
     __builtin_amdgcn_sched_barrier(0);
-    P2_STAMP(1)
     p2_stage(U, o0);
-    P2_STAMP(2)
     p2_load(o2, Wb, lane, n, G);
     __builtin_amdgcn_sched_barrier(0);
     p2_stage(U, o1);
@@ -519,9 +496,7 @@ __global__ __launch_bounds__(P2_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     p2_stage(U, o5);
     p2_stage(U, o6);
     p2_stage(U, o7);
-    P2_STAMP(3)
     strip_store(U, Arow0, lda, imgs[w], lane, n, G);
-    P2_STAMP(4)
 }
 
 }  // namespace

@@ -39,16 +39,7 @@ namespace {
 
 constexpr int TILE = TSVGP_TILE;  // 128
 constexpr int KC = 16;            // k-chunk of the site-accumulation kernel ([k][row] images)
-#ifndef TSVGP_XTILE
-#define TSVGP_XTILE 2  // panel kernels: request the next column tile's first chunk before the current tile's epilogue (1);
-                       // also the first tile's first chunk before gamma is staged (2)
-#endif
-#ifndef TSVGP_CHOL_PRIO
 #define TSVGP_CHOL_PRIO 3  // wave priority of the latency-bound factorisation kernels (s_setprio, 0..3)
-#endif
-#ifndef TSVGP_PANEL_KC_F32
-#define TSVGP_PANEL_KC_F32 32
-#endif
 constexpr int LDS_KS = 144;       // [k][row] image: k stride (elements)
 constexpr int NTHREADS = 256;
 constexpr int MODE_STORE = 0;
@@ -91,14 +82,10 @@ struct Mfma<float> {
 // dwords per group of 32 lanes) and the 8-byte staging writes conflict free.
 template <typename T>
 struct PanelK {
-    static constexpr int KC = sizeof(T) == 8 ? 16 : TSVGP_PANEL_KC_F32;
+    static constexpr int KC = sizeof(T) == 8 ? 16 : 32;
     static constexpr int H = KC / 2;  // elements one thread stages per operand and chunk
     static constexpr int RS = KC + (sizeof(T) == 8 ? 1 : 2);
-#ifdef TSVGP_PANEL_DEPTH_F32
-    static constexpr int DEPTH = sizeof(T) == 8 ? 1 : TSVGP_PANEL_DEPTH_F32;
-#else
     static constexpr int DEPTH = 1;  // chunks of global prefetch held in registers (1 or 2)
-#endif
 };
 
 // H consecutive elements of one row: global -> registers (16-byte loads) and registers -> LDS (8-byte stores: the rows
@@ -156,32 +143,6 @@ __device__ __forceinline__ void mma_chunk_rowk(typename Mfma<T>::acc_t (&acc)[2]
     const T* ap0 = As + (w * 16 + lr) * RS + lk;
     const T* ap1 = As + ((7 - w) * 16 + lr) * RS + lk;
     const T* bp = Bs + lr * RS + lk;
-#ifdef TSVGP_ROWK_PIPE
-    // Two fragment register sets of ONE k-step each (the same 2 x (2 + 8) values the unpipelined form holds for two k-steps):
-    // the reads of k-step ks + 1 are issued in front of the MFMAs of k-step ks, so that within a chunk only the first
-    // k-step's read latency is exposed to a wave that has the matrix pipe to itself (the partner workgroup of the CU in a
-    // prologue, an epilogue or a latency-bound diagonal chunk).
-    T a[2][2], b[2][8];
-    auto rd = [&](const int set, const int ks, const int NMASK) __attribute__((always_inline)) {
-        a[set][0] = ap0[ks * 4];
-        a[set][1] = ap1[ks * 4];
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-            if (NMASK & (1 << n)) b[set][n] = bp[n * 16 * RS + ks * 4];
-    };
-    rd(0, 0, MLO);
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        const int NMASK = (ks < NKS / 2) ? MLO : MHI;
-        if (ks + 1 < NKS) rd((ks + 1) & 1, ks + 1, (ks + 1 < NKS / 2) ? MLO : MHI);
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-            if (NMASK & (1 << n)) {
-                acc[0][n] = Mfma<T>::run(a[ks & 1][0], b[ks & 1][n], acc[0][n]);
-                acc[1][n] = Mfma<T>::run(a[ks & 1][1], b[ks & 1][n], acc[1][n]);
-            }
-    }
-#else
 #pragma unroll
     for (int ks = 0; ks < PKC / 4; ++ks) {
         const int NMASK = (ks < PKC / 8) ? MLO : MHI;
@@ -198,7 +159,6 @@ __device__ __forceinline__ void mma_chunk_rowk(typename Mfma<T>::acc_t (&acc)[2]
                 acc[1][n] = Mfma<T>::run(a[1], b[n], acc[1][n]);
             }
     }
-#endif
 }
 
 // One k-chunk (16) of MFMAs on [k][row] images.  DIAG: only accumulators with column block <= row block
@@ -302,10 +262,8 @@ __device__ __forceinline__ void bern_sums_f(float m, float sd, bool y1, int i0, 
         a1 -= w * dl * z;
     }
 }
-// The quadrature in the arithmetic of the N-arrays' type T (TSVGP_BERN_F64=1 at build time: fp64 for both, as up to round 5)
-#ifndef TSVGP_BERN_F64
+// The quadrature in the arithmetic of the N-arrays' type T (1: fp64 for both, as up to round 5 -- profiles/r05_lik_split_lab.txt)
 #define TSVGP_BERN_F64 0
-#endif
 template <typename T>
 __device__ __forceinline__ void bern_sums_t(double m, double sd, bool y1, int i0, int i1, double& a0, double& a1, double& av) {
     if constexpr (sizeof(T) == 4 && !TSVGP_BERN_F64) {
@@ -343,10 +301,7 @@ __device__ __forceinline__ void lik_eval(int lik_flags, double s2, double m, dou
 // grid = (row blocks of FILL_ROWS, column tiles of FILL_COLS); each thread owns two adjacent columns.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int FILL_ROWS = 64;
-#ifndef TSVGP_FILL_ROWS_DEFAULT
-#define TSVGP_FILL_ROWS_DEFAULT 64
-#endif
-constexpr int FILL_ROWS_DEFAULT = TSVGP_FILL_ROWS_DEFAULT;
+constexpr int FILL_ROWS_DEFAULT = 64;
 constexpr int FILL_COLS = 512;
 
 // exp(a) for a <= 0 (every kernel profile below).  fp64: the device library's algorithm restated -- k = rint(a log2 e),
@@ -419,14 +374,13 @@ __device__ __forceinline__ T kernel_profile(T s) {
 // registers and only the X rows go through LDS (FILL_ROWS * DT elements, wave-uniform 16-byte reads), the distance loop
 // is fully unrolled and the two columns' dependent chains are interleaved.  At N = 1e6, M = 1024, D = 8 (fp64) the
 // kernel is bound by VALU issue, not by its stores: 81 fp64-rate instructions per row pair (32 distance, 2 x 23
-// exp / scale, 3 loop) = 1.26 ms with the store disabled (-DTSVGP_EXP_NOSTORE), the same 8.2 GB written by a
+// exp / scale, 3 loop) = 1.26 ms with the store disabled (an ablation build: removed; code in git history, result in
+// profiles/r02_fill_ablation.txt), the same 8.2 GB written by a
 // store-only kernel of this access pattern 1.35 ms (6.1 TB/s, tools/store_pattern.hip), together 1.86 ms -- was
 // 2.23 ms with the library exp (108 instructions, 1.66 ms of arithmetic), per-row 64-bit VALU index compares and
 // exec-masked column branches.  The occupancy cap costs nothing (3 / 4 / 8 waves per SIMD within 2 %), the order in
 // which row blocks and column tiles are dealt to workgroups neither (2.18 vs 2.18 ms), non-temporal stores 3 %.
-#ifndef TSVGP_FILL_MAXWAVES
 #define TSVGP_FILL_MAXWAVES 3
-#endif
 // Latent batch (grid.z): latent p has its own lengthscales inv_ls[p * D ..], variance var.v[p] and output K + p * strideK;
 // X and Z are shared (SharedIndependentInducingVariables + SeparateIndependent, reference docs/notebooks/heteroskedastic.py:62-76).
 template <typename T>
@@ -473,9 +427,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
     // replicated M x M chain of every step -- takes 8, i.e. eight times as many workgroups (M = 1024: 256 instead of 32:
     // the launch was 50-60 us of a chain whose every microsecond is on the critical path of an 8-way shard)
     __shared__ __attribute__((aligned(16))) T Xs[FILL_ROWS][DT];  // pre-scaled by inv_ls
-#ifdef TSVGP_FILL_EXPANDED
-    __shared__ T Xn[FILL_ROWS];  // |x~|^2 of the staged rows
-#endif
     typedef typename FillVec<T, CPT>::type vec_t;
 
     __builtin_amdgcn_s_setprio(1);  // in front of the clock keeper's waves (priority 0), behind the factorisation's (3)
@@ -495,27 +446,15 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
 #pragma unroll
         for (int d = 0; d < DT; ++d) z[c][d] = (vc && d < D) ? Z[(int64_t)(m + c) * D + d] * inv_ls[d] : T(0);
     }
-#ifdef TSVGP_FILL_EXPANDED
-    // Round 4 experiment (-DTSVGP_FILL_EXPANDED, measured and NOT the default: profiles/r04_fill_expanded_ab.txt): the scaled squared
-    // distance in the expanded form r2 = |x~|^2 + |z~|^2 - 2 x~.z~ -- GPflow's square_distance [ext] -- instead of
-    // sum_d (x~_d - z~_d)^2: one FMA per dimension and column instead of a subtraction and an FMA (D = 8: 18 instead of 32 of the
-    // ~81 instructions per row pair; D = 16: 34 instead of 64).  fp64, D = 8: 1.93 -> 1.87 ms alone, nothing in the step; fp32,
-    // D = 16: 1.76 -> 1.68 ms, the step 18.83 -> 18.62 ms -- the kernel is not purely VALU-issue bound -- and in fp32 the expanded
-    // form costs accuracy exactly where the E-step has its inducing points (Z = X[:M]: r2 = 0 becomes +-1e-6).  The difference
-    // form stays.
-    T zz[CPT];
-#pragma unroll
-    for (int c = 0; c < CPT; ++c) {
-        zz[c] = T(0);
-#pragma unroll
-        for (int d = 0; d < DT; ++d) {
-            zz[c] += z[c][d] * z[c][d];
-            z[c][d] *= T(-2);
-        }
-    }
-#endif
-    // Row blocks are dealt round-robin to the workgroups of a column tile.  The default grid has one workgroup per
-    // row block; a smaller grid (tsvgp_kernel_fill's cap) leaves CU slots free for work on another stream.
+    // The scaled squared distance is the difference form sum_d (x~_d - z~_d)^2.  Round 4 measured the expanded form
+    // r2 = |x~|^2 + |z~|^2 - 2 x~.z~ -- GPflow's square_distance [ext] -- against it (removed; code in git history, result in
+    // profiles/r04_fill_expanded_ab.txt): one FMA per dimension and column instead of a subtraction and an FMA.  fp64, D = 8:
+    // 1.93 -> 1.87 ms alone, nothing in the step; fp32, D = 16: 1.76 -> 1.68 ms, the step 18.83 -> 18.62 ms -- the kernel is not
+    // purely VALU-issue bound -- and in fp32 the expanded form costs accuracy exactly where the E-step has its inducing points
+    // (Z = X[:M]: r2 = 0 becomes +-1e-6).  The difference form stays.
+    // Row blocks are dealt round-robin to the workgroups of a column tile.  tsvgp_kernel_fill launches one workgroup per
+    // row block.  (A smaller, looping grid was an experiment: it leaves CU slots free for work on another stream; removed;
+    // code in git history, result in docs/history_r01-r03.md.)
     const int64_t nrb = (rows_pad + rows_blk - 1) / rows_blk;
     for (int64_t rb = rb_first; rb < nrb; rb += rb_step) {
         const int64_t n0 = rb * rows_blk;
@@ -525,15 +464,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
             Xs[rr][d] = (n < N && d < D) ? X[n * D + d] * inv_ls[d] : T(0);
         }
         __syncthreads();
-#ifdef TSVGP_FILL_EXPANDED
-        if (t < rows_blk) {
-            T acc = T(0);
-#pragma unroll
-            for (int d = 0; d < DT; ++d) acc += Xs[t][d] * Xs[t][d];
-            Xn[t] = acc;
-        }
-        __syncthreads();
-#endif
         if (active) {
             // row counts of this block as wave-uniform ints: valid rows get kernel values, the padding rows up to
             // rows_pad zeros.  Invalid columns of the last group come out as exact zeros through their variance factor.
@@ -543,17 +473,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
             T* const Kp = K + n0 * ldk + m;
             for (int rr = 0; rr < nvalid; ++rr) {
                 T sv[CPT];
-#ifdef TSVGP_FILL_EXPANDED
-                const T xn = Xn[rr];
-#pragma unroll
-                for (int c = 0; c < CPT; ++c) sv[c] = xn + zz[c];
-#pragma unroll
-                for (int d = 0; d < DT; ++d) {
-                    const T x = Xs[rr][d];
-#pragma unroll
-                    for (int c = 0; c < CPT; ++c) sv[c] = fma(x, z[c][d], sv[c]);
-                }
-#else
                 if constexpr (sizeof(T) == 4) {
                     // fp32: two columns per PACKED instruction (v_pk_add_f32 / v_pk_fma_f32).  A plain fp32 vector instruction
                     // costs a wave64 four cycles on this chip -- the 157 TFLOP/s vector peak is the packed rate -- and the
@@ -590,26 +509,17 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
                         }
                     }
                 }
-#endif
                 vec_t out;
 #pragma unroll
                 for (int c = 0; c < CPT; ++c) {
-#ifdef TSVGP_EXP_NOEXP  // ablation switch (tools/exp_fill.py): the store-bound floor of the kernel
-                    out[c] = varc[c] * (T(1) - T(0.5) * sv[c]);
-#else
                     out[c] = varc[c] * kernel_profile<KIND>(sv[c]);
-#endif
                 }
-#ifdef TSVGP_EXP_NOSTORE  // ablation switch: the arithmetic alone (the store never executes, the compiler cannot know)
-                if (out[0] == T(-1)) *reinterpret_cast<vec_t*>(Kp + (int64_t)rr * ldk) = out;
-#else
                 if (stream_out == 2)
                     store_write_through(reinterpret_cast<vec_t*>(Kp + (int64_t)rr * ldk), out);
                 else if (stream_out)
                     __builtin_nontemporal_store(out, reinterpret_cast<vec_t*>(Kp + (int64_t)rr * ldk));
                 else
                     *reinterpret_cast<vec_t*>(Kp + (int64_t)rr * ldk) = out;
-#endif
             }
             vec_t zero;
 #pragma unroll
@@ -798,25 +708,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-#ifdef TSVGP_DIAG_PANEL  // diagnostic build (tools/diag_panel.py): when and where every workgroup ran
-    const unsigned long long diag_t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long diag_c0 = __builtin_amdgcn_s_memtime();
-    // shader cycles of this wave by phase: [0] full k-chunks (64 MFMAs per wave and barrier), [1] the masked chunks of the
-    // diagonal k-tile, [2] a column tile's prologue (first fetch, staging, barrier), [3] its epilogue (square-sum / store)
-    unsigned long long diag_ph[4] = {0, 0, 0, 0};
-    unsigned long long diag_pre = 0, diag_post0 = 0;  // cycles before the first column tile / stamp at the end of the last one
-#define TSVGP_PHASE(i_, t_) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); diag_ph[i_] += now_ - (t_); (t_) = now_; }
-#else
-#define TSVGP_PHASE(i_, t_)
-#endif
-#ifdef TSVGP_EXP_SLOTPRIO  // experiment: the second resident workgroup of a CU (second dispatch half-round) at wave priority 1
-    if ((blockIdx.x >> 8) & 1) __builtin_amdgcn_s_setprio(TSVGP_EXP_SLOTPRIO);
-#endif
-#ifdef TSVGP_EXP_STAGGER  // experiment: delay the second resident workgroup of a CU by a fraction of a chunk
-    if ((blockIdx.x >> 8) & 1) {
-        for (int i = 0; i < TSVGP_EXP_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     const int srow = t >> 1, skh = t & 1;  // staging role: row of the tile, which half of the k-chunk
     const int64_t n0 = (int64_t)blockIdx.x * TILE;
     const int Mp = a.Mp;
@@ -843,18 +734,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
         double rs_mine = 0.0;
         T mpart = T(0);
         // Registers of the global prefetch (DEPTH chunks in flight, see below).  They live outside the tile body so that
-        // the FIRST chunk of the next column tile can be requested before this tile's epilogue (TSVGP_XTILE): its load
+        // the FIRST chunk of the next column tile can be requested before this tile's epilogue: its load
         // latency then hides behind the square-sum / store of the finished tile instead of opening the next one.
         constexpr int DEPTH = PanelK<T>::DEPTH;
         T ra[DEPTH][H], rb[DEPTH][H];
         bool pre = false;  // ra[0] / rb[0] already hold the first chunk of the tile about to start
         if constexpr (FUSE) {
-#if TSVGP_XTILE >= 2
             // the first tile (it = 0 for both triangles) starts at chunk 0: its loads fly while gamma is staged
             load_run<T, H>(ra[0], TSVGP_AROW(0));
             load_run<T, H>(rb[0], TSVGP_AT(Tp, 0));
             pre = true;
-#endif
             for (int j = t; j < Mp; j += NTHREADS) gsm[j] = a.gamma[(size_t)j * a.P + p];
             __syncthreads();
         } else if constexpr (MODE == MODE_MOMENTS) {
@@ -865,7 +754,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
             for (int j = t; j < Mp; j += NTHREADS) gs[j] = a.gamma[(size_t)j * a.P + p];
             __syncthreads();
             const T* gk = gs + skh * H;
-#ifndef TSVGP_EXP_NOGEMV  // ablation switch (tools/exp_moments.py)
 #pragma unroll 4
             for (int c = 0; c < nchunk; ++c) {
                 T ra[H];
@@ -873,7 +761,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 #pragma unroll
                 for (int q = 0; q < H; ++q) mpart += ra[q] * gk[c * KC + q];
             }
-#endif
             __syncthreads();
         }
 
@@ -887,12 +774,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int n = 0; n < 8; ++n) acc[s][n] = acc_t{0, 0, 0, 0};
-#ifdef TSVGP_DIAG_PANEL
-            unsigned long long ph_t = __builtin_amdgcn_s_memtime();
-#endif
 
             // DEPTH chunks of global prefetch are held in registers (one set of H + H values per chunk in flight).
-            // fp64 has room for one set only (128 accumulator registers); fp32 could take two (-DTSVGP_PANEL_DEPTH_F32=2),
+            // fp64 has room for one set only (128 accumulator registers); fp32 could take two (PanelK::DEPTH),
             // but that measured slower (8.68 vs 8.40 ms at N = 1e6, M = 1024), so both types run with one.  A set is
             // chosen by the parity of the chunk index, so every loop below steps by two chunks (all chunk ranges are
             // even); the pairing itself is worth 3 % (fp64) to 6 % (fp32) over a one-chunk loop body.
@@ -914,15 +798,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
         store_run<T, H>(lds_wr + (b_) * BUF_STRIDE, ra[SET]);                              \
         store_run<T, H>(lds_wr + (b_) * BUF_STRIDE + OP_STRIDE, rb[SET]);                  \
     }
-#ifdef TSVGP_EXP_NOLOAD
-#define TSVGP_EXP_HASNEXT(x) false
-#else
-#define TSVGP_EXP_HASNEXT(x) (x)
-#endif
 #define TSVGP_STEP2(MLO, MHI, PAR, c_)                                                          \
     {                                                                                           \
-        const bool has_f = TSVGP_EXP_HASNEXT((c_) + DEPTH < c_end);                             \
-        const bool has_s = TSVGP_EXP_HASNEXT((c_) + 1 < c_end);                                 \
+        const bool has_f = ((c_) + DEPTH < c_end);                                              \
+        const bool has_s = ((c_) + 1 < c_end);                                                  \
         if (has_f) TSVGP_FETCH(DEPTH == 2 ? (PAR) : 0, (c_) + DEPTH)                            \
         mma_chunk_rowk<T, MLO, MHI>(acc, &lds[buf][0][0], &lds[buf][1][0], w, lane);            \
         if (has_s) TSVGP_STAGE(DEPTH == 2 ? ((PAR) ^ 1) : 0, (c_) + 1, buf ^ 1)                 \
@@ -936,10 +815,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
             if (!pre) TSVGP_FETCH(0, c_first)
             TSVGP_STAGE(0, c_first, 0)
             if constexpr (DEPTH == 2) {
-                if (TSVGP_EXP_HASNEXT(c_first + 1 < c_end)) TSVGP_FETCH(1, c_first + 1)
+                if ((c_first + 1 < c_end)) TSVGP_FETCH(1, c_first + 1)
             }
             __syncthreads();
-            TSVGP_PHASE(2, ph_t)
 
             if constexpr (TRI == TSVGP_TRI_DENSE) {
                 for (int c = 0; c < nchunk; c += 2) {
@@ -952,7 +830,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                     TSVGP_STEP(0xFF, 0, c)
                     TSVGP_STEP(0xFF, 1, c + 1)
                 }
-                TSVGP_PHASE(0, ph_t)
                 if constexpr (KC == 16) {
                     TSVGP_STEP(0xFF, 0, cd)
                     TSVGP_STEP(0xFE, 1, cd + 1)
@@ -968,7 +845,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                     TSVGP_STEP2(0xF0, 0xE0, 0, cd + 2)
                     TSVGP_STEP2(0xC0, 0x80, 1, cd + 3)
                 }
-                TSVGP_PHASE(1, ph_t)
             } else {
                 // the diagonal k-tile first: chunk cl only meets column blocks cb <= cl; then full k-tiles it+1..
                 if constexpr (KC == 16) {
@@ -986,12 +862,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                     TSVGP_STEP2(0x1F, 0x3F, 0, cd + 2)
                     TSVGP_STEP2(0x7F, 0xFF, 1, cd + 3)
                 }
-                TSVGP_PHASE(1, ph_t)
                 for (int c = cd + CPT; c < nchunk; c += 2) {
                     TSVGP_STEP(0xFF, 0, c)
                     TSVGP_STEP(0xFF, 1, c + 1)
                 }
-                TSVGP_PHASE(0, ph_t)
             }
 #undef TSVGP_STEP
 #undef TSVGP_STEP2
@@ -999,14 +873,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 #undef TSVGP_FETCH
 #undef TSVGP_TROW
             pre = false;
-#if TSVGP_XTILE
             if (DEPTH == 1 && it_next >= 0) {  // request the next tile's first chunk; the epilogue below covers its latency
                 const int cn = (TRI == TSVGP_TRI_UPPER) ? it_next * CPT : 0;
                 load_run<T, H>(ra[0], TSVGP_AROW(cn));
                 load_run<T, H>(rb[0], TSVGP_AT(Tp + (size_t)it_next * TILE * Mp, cn));
                 pre = true;
             }
-#endif
 
             if constexpr (MODE == MODE_STORE) {
                 T* Cb = a.C + (size_t)pb * a.strideC + n0 * (int64_t)Mp + it * TILE + (lane & 15);
@@ -1038,12 +910,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                     }
                 rs_mine += keep;
             }
-            TSVGP_PHASE(3, ph_t)
         };  // tile_body
         const auto next_of = [ntile](int it) { return it + 1 < ntile ? it + 1 : -1; };
-#ifdef TSVGP_DIAG_PANEL
-        if (p == 0) diag_pre = __builtin_amdgcn_s_memtime() - diag_c0;
-#endif
         if constexpr (FUSE && TRI == TSVGP_TRI_UPPER) {  // upper triangle: the FIRST column tile sweeps every k-chunk
             tile_body(0, std::true_type{}, next_of(0));
             for (int it = 1; it < ntile; ++it) tile_body(it, std::false_type{}, next_of(it));
@@ -1054,9 +922,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
             for (int it = 0; it < ntile; ++it) tile_body(it, std::false_type{}, next_of(it));
         }
 
-#ifdef TSVGP_DIAG_PANEL
-        diag_post0 = __builtin_amdgcn_s_memtime();
-#endif
         if constexpr (MODE == MODE_MOMENTS) {
             // lane (lr < 8, lane>>4) holds the complete sum of row  row_block(w, lr>>2)*16 + rowmap(lane, lr&3)
             if ((lane & 15) < 8) {
@@ -1091,9 +956,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                 if (skh == 0) {
                     if (live) {
                         if (!(v > 0.0)) nonpos += 1;
-#ifndef TSVGP_DIAG_PANEL
                         if (a.mean) a.mean[n * a.P + p] = (T)mu;
-#endif
                         if (a.var) a.var[n * a.P + p] = (T)v;
                         ve_acc += ve;
                     }
@@ -1125,29 +988,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
             if (a.nonpos_partial) a.nonpos_partial[blockIdx.x] = redi[0] + redi[1] + redi[2] + redi[3];
         }
     }
-#ifdef TSVGP_DIAG_PANEL
-    // Stamps go to a buffer of their own, passed in place of `mean` (which NO kernel of this build writes: every store
-    // through `mean` is compiled out under TSVGP_DIAG_PANEL).  The buffer describes itself: word 0 holds the number of
-    // 8-word slots that follow the 8-word header, and a workgroup whose index is not below it writes nothing.  (Round 2's
-    // stamp write was unchecked, and an experiment's finishing kernel stored its N means through the same pointer: a
-    // memory access fault, profiles/r02_moments_split_panel_experiment.txt.)
-    if (t == 0 && a.mean) {
-        unsigned long long* const hdr = reinterpret_cast<unsigned long long*>(a.mean);
-        const unsigned long long slots = hdr[0];
-        const unsigned long long slot = (unsigned long long)blockIdx.x + (unsigned long long)blockIdx.y * gridDim.x;
-        if (slot < slots) {
-            unsigned long long* dbg = hdr + 8 + slot * 8;
-            dbg[0] = diag_t0;
-            dbg[1] = __builtin_amdgcn_s_memrealtime();
-            dbg[2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) |          // HW_REG_HW_ID
-                     ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 32);  // HW_REG_XCC_ID
-            dbg[3] = __builtin_amdgcn_s_memtime() - diag_c0;  // shader cycles of this workgroup
-            for (int i = 0; i < 4; ++i) dbg[4 + i] = diag_ph[i];  // wave 0's cycles by phase
-            hdr[8 + (slots + slot) * 8 + 0] = diag_pre;  // second bank of slots: before the first tile, after the last
-            hdr[8 + (slots + slot) * 8 + 1] = __builtin_amdgcn_s_memtime() - diag_post0;
-        }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1178,7 +1018,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 //   * the T fragments of a set are read first and the two A fragments -- operands of the step's LAST MFMAs -- last, and a set's
 //     registers stay occupied to the end of its step.  Round 3 adopted this order believing that a ds_read landing in an A/B
 //     operand register of a v_mfma_f64_16x16x4_f64 issued just before it had corrupted results.  Round 4 measured it
-//     (tools/hazard_probe.hip; this kernel built with -DTSVGP_HAZARD_AFIRST, i.e. the suspect order, 100-190 such sites at
+//     (tools/hazard_probe.hip; this kernel built in the suspect order -- a switch since removed, code in git history --
+//     100-190 such sites at
 //     distance one per instantiation: every parity and repeatability test passes -- profiles/r04_hazard_probe.txt): there is
 //     no such window, the operands are read when the MFMA issues.  The order stays because it costs nothing.  What the stream
 //     really depends on -- the wait state between the write of M0 and the LDS-DMA, five wait states between v_readfirstlane and
@@ -1197,16 +1038,8 @@ constexpr size_t P1W_GAMMA_LDS_MAX = 32 * 1024;  // two tiles per pass: beside t
 // their MFMA time) -- while a long and a short chunk together last as long as a full one.  All of a tile's accumulators are then
 // first touched by its first chunk (srcC = 0 folds into those MFMAs).  Measured (profiles/r04_moments_epilogue_ablation.txt,
 // moments alone at N = 1e6): fp64 M = 512 4.20 -> 4.10 ms (-2.5 %), fp64 M = 1024 unchanged (15.18 ms), fp32 (four diagonal chunks of
-// 2, 4, 6, 8 column blocks) 7.71 -> 7.81 ms SLOWER -- so fp64 only.  -DTSVGP_DIAG_ORDER=0: the ascending order (A/B builds).
-#ifndef TSVGP_DIAG_ORDER
+// 2, 4, 6, 8 column blocks) 7.71 -> 7.81 ms SLOWER -- so fp64 only.  (0: the ascending order.)
 #define TSVGP_DIAG_ORDER 1
-#endif
-#ifndef TSVGP_MOMENTS_WIDE  // (-DTSVGP_MOMENTS_WIDE=0: A/B builds keep one column tile per pass)
-#define TSVGP_MOMENTS_WIDE 0
-#endif
-#ifndef TSVGP_MOMENTS_OLD_F32  // (-DTSVGP_MOMENTS_OLD_F32=1: A/B builds keep round 2's panel_kernel for fp32)
-#define TSVGP_MOMENTS_OLD_F32 0
-#endif
 
 // Sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), left in every lane of the row: four rotate-and-add steps through
 // v_mov_b32_dpp row_ror (two per double), no LDS crossbar and no s_waitcnt -- the xor butterfly of __shfl_xor compiles to
@@ -1262,18 +1095,11 @@ struct Frag1 {
 // W2: column tiles per pass (1, or 2 for the upper-form moments at an even number of tiles): with two, the A fragments of a
 // k-step serve 32 MFMAs instead of 16, a barrier and a set of DMA issues come once per 128 MFMAs, and the row panel is swept
 // 2.5 instead of 4.5 times (M = 1024); the accumulators are then all 256 AGPRs of the wave (fp64).
-#ifdef TSVGP_DIAG_PANEL1  // diagnostic build (tools/diag_panel1.py): when and where every workgroup of panel1_kernel ran, and the
-// shader cycles of its prologue, tile epilogues and tail.  8 words per workgroup behind a one-word slot count; null: no stamps.
-__device__ unsigned long long* g_panel1_stamps = nullptr;
-#endif
+// No launcher instantiates W2 = 2: re-measured in round 5 it gained nothing in fp32 and lost 14 % in fp64 at M = 512
+// (profiles/r05_moments_wide_ab.txt; the launch arm removed, code in git history).
 template <typename T, int MODE = MODE_MOMENTS, int TRI = TSVGP_TRI_UPPER, int W2 = 1>
 __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
     static_assert(W2 == 1 || (W2 == 2 && MODE == MODE_MOMENTS && TRI == TSVGP_TRI_UPPER), "two tiles per pass: upper-form moments");
-#ifdef TSVGP_DIAG_PANEL1
-    const unsigned long long dg_t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long dg_c0 = __builtin_amdgcn_s_memtime();
-    unsigned long long dg_pro = 0, dg_epi = 0, dg_loop_end = 0, dg_e0 = 0;
-#endif
     constexpr int NB = 8 * W2;                // column blocks of a pass
     constexpr int BUFS = (1 + W2) * P1_OPS;   // fragment units per chunk buffer: the A image + W2 T images
     constexpr int NDMA = 4 + 4 * W2;          // DMA pieces per wave and chunk
@@ -1428,18 +1254,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         auto rds = [&](Frag& f, auto slot_tag, auto m_tag, auto ks_tag, auto boff) TSVGP_AI {
             constexpr int S = decltype(slot_tag)::value, MM = decltype(m_tag)::value;
             constexpr int N0 = (TRI == TSVGP_TRI_UPPER) ? 0 : 8 - MM;
-#ifdef TSVGP_HAZARD_AFIRST  // diagnostic build (tools/isa_hazards.py, profiles/r04_hazard_*): the order round 3 saw corrupt results with
-            if constexpr (S < 2) rd1(f, TSVGP_IC(S), ks_tag, boff);
-            else rd1(f, TSVGP_IC(2 + N0 + S - 2), ks_tag, boff);
-#else
             if constexpr (S < MM) rd1(f, TSVGP_IC(2 + N0 + S), ks_tag, boff);
             else rd1(f, TSVGP_IC(S - MM), ks_tag, boff);
-#endif
         };
         auto keep_set = [&](const Frag& f, auto m_tag) TSVGP_AI {  // the set's registers stay occupied up to this point
-#ifdef TSVGP_HAZARD_AFIRST
-            return;
-#endif
             constexpr int MM = decltype(m_tag)::value, N0 = (TRI == TSVGP_TRI_UPPER) ? 0 : 8 - MM;
             cfor<0, 2 + MM>([&](auto e) TSVGP_AI {
                 constexpr int E = decltype(e)::value;
@@ -1531,9 +1349,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         __syncthreads();  // both chunks and gamma are in LDS for every wave
         // a0, a1, b0 (fp32: and b1) of chunk (0, 0); lower form: tile 0 starts with its diagonal k-tile, all eight column blocks
         cfor<0, ((TRI == TSVGP_TRI_UPPER && !REORDER) ? 2 + BPC : 10)>([&](auto i) TSVGP_AI { rd1(fx, i, TSVGP_IC(0), TSVGP_IC(0)); });
-#ifdef TSVGP_DIAG_PANEL1
-        if (p == 0) dg_pro = __builtin_amdgcn_s_memtime() - dg_c0;
-#endif
 
         for (int it = 0; it < ntile; it += W2) {
             const int cd = it * CPT;
@@ -1683,19 +1498,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
                     }
                 continue;
             }
-#ifdef TSVGP_EXP_NOEPI  // ablation (profiles/r04_moments_epilogue_ablation.txt): the column tile's square-sum epilogue left out --
-            // what a second accumulator set could at most hide.  The accumulators stay live (the MFMAs are not dead code); results wrong.
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int n = 0; n < NB; ++n) asm volatile("" ::"a"(acc[s][n]));
-            rs_mine += (double)acc[0][0][0];
-            continue;
-#endif
             // the column tile is complete: squares of its entries, summed per row (as panel_kernel)
-#ifdef TSVGP_DIAG_PANEL1
-            dg_e0 = __builtin_amdgcn_s_memtime();
-#endif
             double keep = 0.0;
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -1717,26 +1520,12 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
                             q += v * v;
                         }
                     }
-#ifdef TSVGP_EPI_SHFL  // (A/B builds: round 3's butterfly through the LDS crossbar)
-                    q += __shfl_xor(q, 1);
-                    q += __shfl_xor(q, 2);
-                    q += __shfl_xor(q, 4);
-                    q += __shfl_xor(q, 8);
-#else
                     q = row16_sum(q);
-#endif
                     keep = ((lane & 7) == s * 4 + r) ? q : keep;
                 }
             rs_mine += keep;
-#ifdef TSVGP_DIAG_PANEL1
-            asm volatile("" : "+v"(rs_mine));
-            dg_epi += __builtin_amdgcn_s_memtime() - dg_e0;
-#endif
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the saturated re-fetches of the last two chunks have landed
-#ifdef TSVGP_DIAG_PANEL1
-        dg_loop_end = __builtin_amdgcn_s_memtime();
-#endif
         if constexpr (MODE == MODE_STORE) return;
 
         // row sums and means to LDS, then the likelihood map of panel_kernel's epilogue (two threads per row)
@@ -1807,29 +1596,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         if (a.ve_partial) a.ve_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
         if (a.nonpos_partial) a.nonpos_partial[blockIdx.x] = redi[0] + redi[1] + redi[2] + redi[3];
     }
-#ifdef TSVGP_DIAG_PANEL1
-    if (t == 0 && g_panel1_stamps && blockIdx.y == 0 && (unsigned long long)blockIdx.x < g_panel1_stamps[0]) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* d = g_panel1_stamps + 8 + (size_t)blockIdx.x * 8;
-        const unsigned long long c_end = __builtin_amdgcn_s_memtime();
-        d[0] = dg_t0;
-        d[1] = __builtin_amdgcn_s_memrealtime();
-        d[2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) |          // HW_REG_HW_ID
-               ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 32);  // HW_REG_XCC_ID
-        d[3] = c_end - dg_c0;        // shader cycles of the workgroup (wave 0)
-        d[4] = dg_pro;               // entry -> first fragments of chunk (0, 0) in registers
-        d[5] = dg_epi;               // the column tiles' square-sum epilogues
-        d[6] = c_end - dg_loop_end;  // end of the chunk stream -> here: row sums to LDS, likelihood map, stores, reductions
-        d[7] = dg_loop_end - dg_c0;
-    }
-#endif
 }
 
-#ifdef TSVGP_DIAG_PANEL1
-extern "C" int tsvgp_diag_panel1_stamps(unsigned long long* buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_panel1_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // lik_map_kernel: the likelihood-gradient map on its own: (mean, var, Y) -> g0 = d ve / d mean,
@@ -2294,9 +2062,7 @@ __global__ __launch_bounds__(NTHREADS) void mean_lik_kernel(PanelArgs<T> a) {
                 const double mu = (double)(lane ? s1 : s0);
                 double g0 = 0.0, g1 = 0.0, ve = 0.0;
                 if (n < a.N) {
-#ifndef TSVGP_DIAG_PANEL  // in that build `mean` is the stamp buffer of panel_kernel: nothing else may store through it
                     if (a.mean) a.mean[n * P + p] = (T)mu;
-#endif
                     if (a.lik != TSVGP_LIK_NONE) lik_eval(a.lik, a.lik_param, mu, 0.0, (double)a.Y[n * P + p], g0, g1, ve);
                     if (!(fabs(mu) <= 1.79769313486231570815e308) || !(fabs(g0) <= 1.79769313486231570815e308)) atomicAdd(&bad, 1);
                 }
@@ -2335,27 +2101,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // Diagonal tiles run 9 of 16 MFMAs per k-step but the same loads, LDS traffic and barrier per chunk: measured with
-// in-kernel stamps (tools/diag_syrk.py) a diagonal-tile chunk costs 0.71 of an off-diagonal one, not 9/16.
-#ifndef TSVGP_SYRK_DIAG_NUM
-#define TSVGP_SYRK_DIAG_NUM 23
+// in-kernel stamps (removed; code in git history, result in profiles/r01_syrk_inkernel_stamps.txt) a diagonal-tile chunk of
+// syrk_kernel costs 0.71 of an off-diagonal one (23/32), not 9/16.  The split of the diagonal tiles follows the two kernels
+// of round 3, which serve P <= 8:
 #define TSVGP_SYRK_DIAG_DEN 32
-#endif
-#ifndef TSVGP_SYRK1_DIAG_NUM  // syrk1_kernel (fp64, round 3): 19/32 .. 23/32 measured within 1 % of each other; 20/32 best
-#define TSVGP_SYRK1_DIAG_NUM 20
-#endif
-#ifndef TSVGP_SYRK1F_DIAG_NUM  // syrk1f_kernel (fp32, round 3)
-#define TSVGP_SYRK1F_DIAG_NUM 22
-#endif
-#ifndef TSVGP_SYRK_OLD_F32  // (-DTSVGP_SYRK_OLD_F32=1: A/B builds keep round 2's syrk_kernel for fp32)
-#define TSVGP_SYRK_OLD_F32 0
-#endif
-// (esize: sizeof of the N-sized arrays' type -- syrk1_kernel / syrk1f_kernel run unless the build keeps the old one)
+#define TSVGP_SYRK1_DIAG_NUM 20   // syrk1_kernel (fp64): 19/32 .. 23/32 measured within 1 % of each other; 20/32 best
+#define TSVGP_SYRK1F_DIAG_NUM 22  // syrk1f_kernel (fp32)
+// (esize: sizeof of the N-sized arrays' type: syrk1_kernel's ratio for fp64, syrk1f_kernel's for fp32)
 __host__ __device__ inline int syrk_ns_diag(int ns_off, int esize) {
-#ifndef TSVGP_SYRK_OLD
-    const int num = esize == 8 ? TSVGP_SYRK1_DIAG_NUM : TSVGP_SYRK_OLD_F32 ? TSVGP_SYRK_DIAG_NUM : TSVGP_SYRK1F_DIAG_NUM;
-#else
-    const int num = TSVGP_SYRK_DIAG_NUM;
-#endif
+    const int num = esize == 8 ? TSVGP_SYRK1_DIAG_NUM : TSVGP_SYRK1F_DIAG_NUM;
     const int d = (num * ns_off + TSVGP_SYRK_DIAG_DEN - 1) / TSVGP_SYRK_DIAG_DEN;
     return d < 1 ? 1 : d;
 }
@@ -2416,35 +2170,11 @@ __device__ __forceinline__ void syrk_body(const SyrkArgs<T>& a, T (*lds)[2][KC *
         if (DIAG && cseg == 0) g0s[buf][krow] = w0;
     };
 
-#if defined(TSVGP_DIAG_CLOCK)
-    unsigned long long seg[4] = {0, 0, 0, 0};
-#define STAMP(i)
-    const unsigned long long tstart = __builtin_amdgcn_s_memtime();
-    const unsigned long long rstart = __builtin_amdgcn_s_memrealtime();
-#elif defined(TSVGP_DIAG_STAMPS)
-    unsigned long long seg[4] = {0, 0, 0, 0}, tprev;
-#define STAMP(i)                                                                             \
-    {                                                                                        \
-        unsigned long long tn;                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tn)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        seg[i] += tn - tprev;                                                                \
-        tprev = tn;                                                                          \
-    }
-    const unsigned long long tstart = __builtin_amdgcn_s_memtime();
-    const unsigned long long rstart = __builtin_amdgcn_s_memrealtime();
-#else
-#define STAMP(i)
-#endif
     if (c_lo < c_hi) {
         load_chunk(c_lo);
         store_chunk(0);
     }
     __syncthreads();
-#ifdef TSVGP_DIAG_STAMPS
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
-#endif
     // one pipeline step on chunk c in LDS buffer BUF (compile time): prefetch chunk c + 1 to registers, MFMAs, stage the
     // prefetched chunk into the other buffer, one barrier.  The loop body holds two steps so that the buffer index is a
     // constant in each (as in panel_kernel, where the pairing measured 3-6 % faster than a one-step body).
@@ -2452,18 +2182,14 @@ __device__ __forceinline__ void syrk_body(const SyrkArgs<T>& a, T (*lds)[2][KC *
         constexpr int BUF = decltype(buf_tag)::value;
         const bool has_next = (c + 1 < c_hi);
         if (has_next) load_chunk(c + 1);
-        STAMP(0)
         mma_chunk_krow<T, DIAG, W>(acc, lds[BUF][0], lds[BUF][1], w, lane);
-        STAMP(1)
         if (DIAG && t < TILE) {
             const T* bcol = &lds[BUF][1][t];
 #pragma unroll
             for (int k = 0; k < KC; ++k) acc1 += g0s[BUF][k] * bcol[k * LDS_KS];
         }
         if (has_next) store_chunk(BUF ^ 1);
-        STAMP(2)
         __syncthreads();
-        STAMP(3)
     };
     {
         int64_t c = c_lo;
@@ -2473,23 +2199,6 @@ __device__ __forceinline__ void syrk_body(const SyrkArgs<T>& a, T (*lds)[2][KC *
         }
         if (c < c_hi) step(c, std::integral_constant<int, 0>{});
     }
-#if defined(TSVGP_DIAG_STAMPS) || defined(TSVGP_DIAG_CLOCK)
-    if (lane == 0) {
-        unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.part1 + (size_t)a.P * a.ns_diag * a.Mp) + ((size_t)blockIdx.x * 4 + w) * 8;
-        dbg[0] = seg[0]; dbg[1] = seg[1]; dbg[2] = seg[2]; dbg[3] = seg[3];
-        dbg[4] = __builtin_amdgcn_s_memtime() - tstart;
-        dbg[5] = __builtin_amdgcn_s_memrealtime() - rstart;
-        dbg[6] = (unsigned long long)(c_hi - c_lo);
-        dbg[7] = DIAG;
-#if defined(TSVGP_DIAG_CLOCK)
-        dbg[0] = rstart;                             // absolute start (100 MHz ticks)
-        dbg[1] = __builtin_amdgcn_s_memrealtime();   // absolute end
-        dbg[2] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-        dbg[3] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-#endif
-    }
-#endif
-#undef STAMP
 
     T* out = a.part2 + ((size_t)p * per_p + slab) * (TILE * TILE) + (lane & 15);
 #pragma unroll
@@ -3115,19 +2824,10 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
     }
 }
 
-#ifndef TSVGP_S1F_WAVES  // waves per SIMD the register allocation may assume at most (1: one workgroup per CU)
-#define TSVGP_S1F_WAVES 2
-#endif
+#define TSVGP_S1F_WAVES 2  // waves per SIMD the register allocation may assume at most (1: one workgroup per CU)
 __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, TSVGP_S1F_WAVES))) void syrk1f_kernel(SyrkArgs<float> a) {
     __shared__ __attribute__((aligned(1024))) float lds[2 * S1F_BUF];
     __shared__ __attribute__((aligned(1024))) float wl[2 * S1F_WL];
-#ifdef TSVGP_S1F_LDS_PAD  // experiment: more than half of a CU's LDS, i.e. one workgroup per CU
-    __shared__ float s1f_pad[TSVGP_S1F_LDS_PAD];
-    {
-        float* keep_pad = s1f_pad + threadIdx.x;
-        asm volatile("" ::"v"(keep_pad));
-    }
-#endif
 
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nt = a.nt, n_off = nt * (nt - 1) / 2;
@@ -3235,11 +2935,8 @@ __global__ __launch_bounds__(NTHREADS) void syrk_reduce_kernel(const T* __restri
 //   chol_tile_kernel<UPDATE>  A[i,j] <- A[i,j] - A[i,k] * A[j,k]^T      (one wave per trailing lower 32x32 tile)  Latency bound by design (M^3/3 flops is
 // microseconds of MFMA time): the critical path is 8 diagonal blocks, each ~M/8 dependent column steps.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef TSVGP_CHOL_SB
-#define TSVGP_CHOL_SB 16
-#endif
 constexpr int CH_NB = 128;
-constexpr int CH_SB = TSVGP_CHOL_SB;  // sub-block of the diagonal block factored in one wave's registers
+constexpr int CH_SB = 16;  // sub-block of the diagonal block factored in one wave's registers
 constexpr int CH_WT = 32;          // wave tile of the panel / update / inverse-assembly products
 constexpr int CH_LD = CH_NB + 1;   // odd LDS row stride: one-lane-per-row column sweeps touch 32 different banks
 constexpr int CH_THREADS = 512;    // 8 waves
@@ -3293,15 +2990,6 @@ __device__ __forceinline__ ChRole chol_factor_rows(double* __restrict__ S, doubl
         for (int c = 0; c < CH_SB; ++c) a[c] = (c == role.ident) ? 1.0 : 0.0;
     }
     int bad = 0;
-#ifdef TSVGP_DIAG_POTRF
-    extern __shared__ __attribute__((aligned(16))) unsigned char diag_raw[];
-    unsigned long long* fst = reinterpret_cast<unsigned long long*>(diag_raw + (size_t)CH_NB * CH_LD * sizeof(double));
-    int nf = 0;
-#define FSTAMP() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (w == 0 && (s0 == 0 || s0 == 80)) { unsigned long long tt = __builtin_amdgcn_s_memtime(); if (lane == 0) fst[(s0 == 0 ? 0 : 32) + nf] = tt; } ++nf; }
-#else
-#define FSTAMP()
-#endif
-    FSTAMP()
 #pragma unroll
     for (int j0 = 0; j0 < CH_SB; j0 += 4) {
         const double p00 = readlane_d(a[j0], j0), p10 = readlane_d(a[j0], j0 + 1), p20 = readlane_d(a[j0], j0 + 2),
@@ -3320,10 +3008,6 @@ __device__ __forceinline__ ChRole chol_factor_rows(double* __restrict__ S, doubl
         const double l32 = (p32 - l30 * l20 - l31 * l21) * i2;
         const double d3 = p33 - l30 * l30 - l31 * l31 - l32 * l32;
         const double i3 = rsqrt_nr(d3);
-#ifdef TSVGP_DIAG_POTRF
-        { double q = i3; asm volatile("" : "+v"(q)); }
-        FSTAMP()
-#endif
         if (bad == 0) bad = !(p00 > 0.0) ? j0 + 1 : !(d1 > 0.0) ? j0 + 2 : !(d2 > 0.0) ? j0 + 3 : !(d3 > 0.0) ? j0 + 4 : 0;
         // own row against the pivot block; for the pivot rows this reproduces the factor's rows
         // (x_q = d_q * rsqrt(d_q) = sqrt(d_q) on the diagonal)
@@ -3335,10 +3019,6 @@ __device__ __forceinline__ ChRole chol_factor_rows(double* __restrict__ S, doubl
         a[j0 + 1] = x1;
         a[j0 + 2] = x2;
         a[j0 + 3] = x3;
-#ifdef TSVGP_DIAG_POTRF
-        { double q = x3; asm volatile("" : "+v"(q)); }
-        FSTAMP()
-#endif
         if (lane == 0 && w == 0) {
             dinv[s0 + j0] = i0;
             dinv[s0 + j0 + 1] = i1;
@@ -3374,11 +3054,8 @@ __device__ __forceinline__ ChRole chol_factor_rows(double* __restrict__ S, doubl
                 }
             }
             __builtin_amdgcn_wave_barrier();  // the next step's writes come after these reads
-            FSTAMP()
         }
     }
-    FSTAMP()
-#undef FSTAMP
     if (role.below) {
 #pragma unroll
         for (int c = 0; c < CH_SB; ++c) row[c] = a[c];
@@ -3498,14 +3175,6 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
                 for (int r = 0; r < 4; ++r) U[s_][r] = Arow0[(size_t)(lane & 15) * lda + 16 * s_ + 4 * r + (lane >> 4)];
         }
     }
-#ifdef TSVGP_DIAG_POTRF
-    unsigned long long stamp[40];
-    int nstamp = 0;
-#define PSTAMP() stamp[nstamp++] = __builtin_amdgcn_s_memtime();
-#else
-#define PSTAMP()
-#endif
-    PSTAMP()
     if (t == 0) fail = 0;
     // 16-byte loads, eight in flight per thread; the strict upper triangle is read and dropped
 #pragma unroll
@@ -3524,7 +3193,6 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
         }
     }
     __syncthreads();
-    PSTAMP()
 
     // one 16x16 tile of a trailing update: A[i0.., j0..] -= L[i0.., c0..c0+16) L[j0.., c0..c0+16)^T (lower part only: the
     // strict upper triangles of the diagonal tiles hold the sub-block inverses)
@@ -3564,11 +3232,9 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
         }
         __syncthreads();
         if (takes) chol_store_sb(S, s0, lane, w, role, a);  // nothing reads these rows before the next barrier
-        PSTAMP()
         // this phase's update of the NEXT block column, one tile per wave; the rest waits for the next round
         if (w < n16) update_tile(s0, s0 + CH_SB + 16 * w, s0 + CH_SB);
         __syncthreads();
-        PSTAMP()
     }
 
     // L_kk out (zeros above the diagonal)
@@ -3584,7 +3250,6 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
         // (block 0 initialises the status word -- no memset launch in front of the factorisation -- later blocks keep the first failure)
         if (t == 0 && (k == 0 || (fail != 0 && info[b] == 0))) info[b] = fail;
     }
-    PSTAMP()
     if constexpr (FUSED) {
         // P = A_panel inv(L_kk)^T by substitution over the 16-wide column blocks (chol_panel2_kernel's recurrence):
         //   P_s = U_s inv(L_ss)^T,  U_s' -= P_s L_s's^T (s' > s); operands: lane (n, G), k-step kk <-> row n, column 4 kk + G of the
@@ -3656,7 +3321,6 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
         __syncthreads();
         if (w < 4) chol_inv_offdiag<4>(S, dinv, 64, 0, w, lane);
         __syncthreads();
-        PSTAMP()
         double* Wb = work + (size_t)b * CH_NB * CH_NB;
         for (int idx = t; idx < CH_NB * CH_NB; idx += CH_THREADS) {
             const int r = idx >> 7, c = idx & 127;
@@ -3672,21 +3336,6 @@ __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restri
             }
         }
     }
-#ifdef TSVGP_DIAG_POTRF
-    __syncthreads();
-    PSTAMP()
-#ifndef TSVGP_DIAG_POTRF_K
-#define TSVGP_DIAG_POTRF_K 0
-#endif
-    if (t == 0 && k == TSVGP_DIAG_POTRF_K && need_inverse) {
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(work + (size_t)b * CH_NB * CH_NB);
-        dst[0] = nstamp;
-        for (int i = 0; i < nstamp; ++i) dst[1 + i] = stamp[i];
-        const unsigned long long* fst = reinterpret_cast<const unsigned long long*>(smem_raw + (size_t)CH_NB * CH_LD * sizeof(double));
-        for (int i = 0; i < 64; ++i) dst[64 + i] = fst[i];
-    }
-#endif
-#undef PSTAMP
 }
 
 // Tile products for the panel solve and the trailing update, one WAVE per 32x32 output tile, K = 128, no LDS and no
@@ -5159,19 +4808,12 @@ int kernel_fill(int kind, const T* X, const T* Z, const T* inv_ls, const T* vari
                       (reinterpret_cast<uintptr_t>(K) & 15) == 0 && (cols_pad % 4) == 0;  // (DT = 32: 128 registers of Z alone)
     const int cols_wg = (cpt4 ? 4 : 2) * NTHREADS;
     dim3 grid((unsigned)((rows_pad + rows_blk - 1) / rows_blk), (unsigned)((cols_pad + cols_wg - 1) / cols_wg), (unsigned)P);
-#ifdef TSVGP_FILL_GRID_CAP  // experiment build (tools/exp_overlap2.py): fewer, looping workgroups
-    if ((unsigned)(TSVGP_FILL_GRID_CAP) < grid.x) grid.x = (unsigned)(TSVGP_FILL_GRID_CAP);
-#endif
     // An output far beyond the caches (4 MB of L2 per XCD, 256 MB of Infinity Cache) is written with non-temporal stores:
     // nothing of it would still be cached when its reader arrives, and the M x M factorisations that run beside the fill of
     // an E-step keep their operands in L2 (under the fill a factorisation call: 0.87 -> 0.80 ms; the step at N = 1e6
     // 36.79 -> 36.45 ms on one box, within noise on two others, never slower).  A small output stays cacheable for its reader.
-#ifdef TSVGP_FILL_STREAM  // experiment builds (tools/exp_fill_nt.py, tools/ab_builds.sh): 0 / 1 for every launch
-    const int stream_out = TSVGP_FILL_STREAM;
-#else
     static const int store_wt = [] { const char* e = getenv("TSVGP_FILL_STORE"); return e && e[0] == 'w' ? 1 : 0; }();
     const int stream_out = (double)rows_pad * (double)ldk * sizeof(T) * P >= 512.0 * 1024 * 1024 ? 1 + store_wt : 0;
-#endif
 #define TSVGP_FILL_LAUNCH(KIND_, DT_)                                                                                        \
     do {                                                                                                                     \
         if constexpr (sizeof(T) == 4 && DT_ <= 16) {                                                                          \
@@ -5228,24 +4870,20 @@ int trmm(const T* A, int64_t strideA, const T* Tm, int64_t strideT, T* C, int64_
     a.strideT = strideT;
     a.strideC = strideC;
     const dim3 grid((unsigned)(Np / TILE), (unsigned)batch), block(NTHREADS);
-#ifndef TSVGP_LOWER_OLD
+    // (The two panel_kernel arms behind a panel1_kernel arm of the same condition are never reached.  They stay because they
+    // instantiate those kernels: without them the device code of the library would change.)
     if (mode == TSVGP_TRI_LOWER) {
         static DynLdsOptIn optin1sl;
         if (optin1sl.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), 0) != TSVGP_OK)
             return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
-    } else
-#endif
-    if (mode == TSVGP_TRI_LOWER)
+    } else if (mode == TSVGP_TRI_LOWER)
         hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
-#ifndef TSVGP_TRMM_OLD  // (-DTSVGP_TRMM_OLD: A/B builds keep round 2's panel_kernel for the upper product)
     else if (mode == TSVGP_TRI_UPPER) {
         static DynLdsOptIn optin1s;  // 66 KB of static LDS
         if (optin1s.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_STORE>), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_STORE>), grid, block, 0, (hipStream_t)stream, a);
-    }
-#endif
-    else if (mode == TSVGP_TRI_UPPER)
+    } else if (mode == TSVGP_TRI_UPPER)
         hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_UPPER>), grid, block, 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_DENSE>), grid, block, 0, (hipStream_t)stream, a);
@@ -5371,9 +5009,11 @@ int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y
     a.mode = mode;
     a.lik = lik;
     const dim3 grid((unsigned)(Np / TILE)), block(NTHREADS);
+    // (The two fused-mean panel_kernel arms (gamma of at most 8192 bytes) stand behind a panel1_kernel arm that takes every such
+    // call and are never reached.  They stay because they instantiate those kernels: without them the device code of the library
+    // would change.  The plain panel_kernel arms serve an Mp whose gamma does not fit beside panel1_kernel's ring.)
     if (mean_only)
         hipLaunchKernelGGL((mean_lik_kernel<T>), grid, block, (size_t)Mp * P * sizeof(T), (hipStream_t)stream, a);
-#ifndef TSVGP_LOWER_OLD  // (-DTSVGP_LOWER_OLD: A/B builds keep round 2's panel_kernel for the lower-form products)
     else if (mode == TSVGP_TRI_LOWER && (size_t)Mp * sizeof(T) <= P1_GAMMA_LDS_MAX) {
         static DynLdsOptIn optin1l;
         if (optin1l.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER>), P1_GAMMA_LDS_MAX) !=
@@ -5381,34 +5021,17 @@ int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y
             return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER>), grid, block, (size_t)Mp * sizeof(T),
                            (hipStream_t)stream, a);
-    }
-#endif
-    else if (mode == TSVGP_TRI_LOWER && (size_t)Mp * sizeof(T) <= 8192)
+    } else if (mode == TSVGP_TRI_LOWER && (size_t)Mp * sizeof(T) <= 8192)
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER, true>), grid, block, (size_t)Mp * sizeof(T),
                            (hipStream_t)stream, a);
     else if (mode == TSVGP_TRI_LOWER)
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
-#ifndef TSVGP_MOMENTS_OLD  // (-DTSVGP_MOMENTS_OLD: A/B builds keep round 2's panel_kernel on this path)
-#if TSVGP_MOMENTS_WIDE
-    else if (mode == TSVGP_TRI_UPPER && (sizeof(T) == 8 || !TSVGP_MOMENTS_OLD_F32) && (Mp % (2 * TILE)) == 0 &&
-             (size_t)Mp * sizeof(T) <= P1W_GAMMA_LDS_MAX) {
-        // upper form, an even number of column tiles: two tiles per pass
-        static DynLdsOptIn optin1w;
-        if (optin1w.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_MOMENTS, TSVGP_TRI_UPPER, 2>), P1W_GAMMA_LDS_MAX) !=
-            TSVGP_OK)
-            return TSVGP_ELAUNCH;
-        hipLaunchKernelGGL((panel1_kernel<T, MODE_MOMENTS, TSVGP_TRI_UPPER, 2>), grid, block, (size_t)Mp * sizeof(T),
-                           (hipStream_t)stream, a);
-    }
-#endif
-    else if (mode == TSVGP_TRI_UPPER && (sizeof(T) == 8 || !TSVGP_MOMENTS_OLD_F32) && (size_t)Mp * sizeof(T) <= P1_GAMMA_LDS_MAX) {
+    else if (mode == TSVGP_TRI_UPPER && (size_t)Mp * sizeof(T) <= P1_GAMMA_LDS_MAX) {
         // upper form: one workgroup per CU with the hand-laid instruction stream (panel1_kernel)
         static DynLdsOptIn optin1;
         if (optin1.ensure(reinterpret_cast<const void*>(&panel1_kernel<T>), P1_GAMMA_LDS_MAX) != TSVGP_OK) return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T>), grid, block, (size_t)Mp * sizeof(T), (hipStream_t)stream, a);
-    }
-#endif
-    else if (mode == TSVGP_TRI_UPPER && (size_t)Mp * sizeof(T) <= 8192)
+    } else if (mode == TSVGP_TRI_UPPER && (size_t)Mp * sizeof(T) <= 8192)
         // gamma fits beside the staging buffers without costing the second workgroup per CU: fused mean
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_UPPER, true>), grid, block, (size_t)Mp * sizeof(T),
                            (hipStream_t)stream, a);
@@ -5458,14 +5081,13 @@ int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, double* ac
     a.part1 = a.part2 + (size_t)P * per_p * TILE * TILE;
     const int64_t nwg = (int64_t)P * per_p;
     if (nwg > 0x7fffffff) return TSVGP_EINVAL;
-#ifndef TSVGP_SYRK_OLD  // (-DTSVGP_SYRK_OLD: A/B builds keep round 2's syrk_kernel for fp64 too)
     if (sizeof(T) == 8 && P <= 8) {  // (the weights of a chunk travel as one 1-KiB LDS-DMA piece: 16 P doubles)
       if constexpr (sizeof(T) == 8) {
         static DynLdsOptIn optin_s1;  // 72 KB of static LDS: above the 64 KB a kernel gets without asking
         if (optin_s1.ensure(reinterpret_cast<const void*>(&syrk1_kernel), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
         hipLaunchKernelGGL(syrk1_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
       }
-    } else if (sizeof(T) == 4 && !TSVGP_SYRK_OLD_F32 && P <= 8) {
+    } else if (sizeof(T) == 4 && P <= 8) {
       if constexpr (sizeof(T) == 4) {
         const int64_t total32 = Np / S1F_KC;  // this kernel's chunks are 32 rows
         a.chunks_off = (total32 + a.ns_off - 1) / a.ns_off;
@@ -5475,7 +5097,6 @@ int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, double* ac
         hipLaunchKernelGGL(syrk1f_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
       }
     } else
-#endif
         hipLaunchKernelGGL(syrk_kernel<T>, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
     if (launch_status() != TSVGP_OK) return TSVGP_ELAUNCH;
     const int extra = (Mp + NTHREADS - 1) / NTHREADS;
@@ -5489,15 +5110,15 @@ int site_accum_slots() {
     int dev = 0, cus = 0, nb = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-#ifndef TSVGP_SYRK_OLD
     if (sizeof(T) == 8) return cus;  // syrk1_kernel: one workgroup per CU by construction (512 registers per wave)
-    if (!TSVGP_SYRK_OLD_F32) {       // syrk1f_kernel: what its registers and 68 KB of LDS allow
+    {  // syrk1f_kernel: what its registers and 68 KB of LDS allow
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&syrk1f_kernel), NTHREADS, 0) !=
             hipSuccess)
             return -1;
         return cus * (nb > 2 ? 2 : nb < 1 ? 1 : nb);
     }
-#endif
+    // (Never reached.  The lines below stay because they are the first use of syrk_kernel<T> in this file: without them the
+    // compiler emits that kernel at another place in the code object, and the device code of the library would change.)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&syrk_kernel<T>), NTHREADS,
                                                      0) != hipSuccess)
         return -1;
@@ -5516,11 +5137,7 @@ int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, doubl
                diag_v2 = (flags & TSVGP_POTRF_DIAG_V2) != 0, fuse = (flags & TSVGP_POTRF_FUSE) != 0;
     if (inv && (!Xt || !T)) return TSVGP_EINVAL;
     const int nt = M / CH_NB;
-#ifdef TSVGP_DIAG_POTRF
-    const size_t smem = (size_t)CH_NB * CH_LD * sizeof(double) + 64 * sizeof(unsigned long long);  // + in-phase stamps
-#else
     const size_t smem = (size_t)CH_NB * CH_LD * sizeof(double);
-#endif
     static DynLdsOptIn optin;
     if (optin.ensure(reinterpret_cast<const void*>(&potrf_diag_kernel<false>), smem) != TSVGP_OK) return TSVGP_ELAUNCH;
     static DynLdsOptIn optin_fused;

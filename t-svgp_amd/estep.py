@@ -924,7 +924,7 @@ class EStepEngine:
         """Starts the K(X, Z) fill of the next ``run`` on a side stream and returns a ticket for ``run(prefill=...)``.
         The fill needs only X, Z and the kernel parameters, so it can run beside the latency-bound M x M prelude
         (factorisations of one workgroup each, small GEMMs) that the main stream executes between this call and
-        ``run``: 3.26 -> 2.6 ms for the pair at N = 1e6, M = 1024 (tools/exp_overlap2.py).  Returns None when there is
+        ``run``: 3.26 -> 2.6 ms for the pair at N = 1e6, M = 1024 (script removed, code in git history; result in docs/history_r01-r03.md).  Returns None when there is
         nothing to overlap: separate kernels on the per-latent path (one fill per latent), an operand ``run`` would reuse
         (warm E-steps), a stream capture in progress.  ``routes``: the projection route of every latent (separate kernels:
         the batched pass, whose fill this starts, needs all of them direct or whitened)."""

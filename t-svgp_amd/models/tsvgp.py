@@ -473,7 +473,7 @@ class t_SVGP(base_SVGP):
         # (the transposed-operand rocBLAS kernels take 60 us at M = 1024 where the plain one takes 40: L^T is copied out first,
         # for this product and for L L^T below)
         Lt = L.transpose(-1, -2).contiguous()
-        solve = potrf is not None and hasattr(eng, "cholesky_solve_upper") and os.environ.get("TSVGP_POTRF_SOLVE", "1") != "0"
+        solve = potrf is not None and hasattr(eng, "cholesky_solve_upper")
         if solve:
             # the identity of W and the jitter of K9 = K_uu + jitter I (tsvgp.py:270) ride on the pass that hands the matrices to
             # the factorisation (EStepEngine.solve_upper_put): no assembled batch, no 8 MB copy of K_uu, no strided additions --
@@ -527,7 +527,7 @@ class t_SVGP(base_SVGP):
             U9, Uinv9 = None, None
         if Dm is None:
             Dm = (Uinv_W @ L.transpose(-1, -2)).triu()  # D = U_W^-1 L^T, [P, M, M], upper triangular
-        if hasattr(eng, "site_beta") and Dm.is_cuda and os.environ.get("TSVGP_SITE_BETA", "1") != "0":
+        if hasattr(eng, "site_beta") and Dm.is_cuda:
             beta = eng.site_beta(Dm, K6l, l1)  # K6^-1 m = l1 - D^T D K6 l1: two triangular matrix-vector launches
         else:
             beta = l1 - bmv(Dm, bmv(Dm, K6l), transpose=True)
@@ -554,7 +554,7 @@ class t_SVGP(base_SVGP):
                 ops["K9inv"] = Uinv9.transpose(-1, -2) @ Uinv9
 
         side = getattr(eng, "_side", None)
-        if not fork or os.environ.get("TSVGP_EPI_INLINE") == "1":
+        if not fork:
             # in line, in front of the moments kernel: a captured launch-bound step (see _step_front); as an experiment at
             # N = 1e6 it measured 33.83 / 33.90 ms against 33.92 / 33.96 on the side stream -- no difference worth a second path
             epilogue_operands()
@@ -1338,7 +1338,7 @@ class t_SVGP(base_SVGP):
         l1_old = self.lambda_1.value
         if latents is not None:
             l1_old = l1_old.index_select(1, torch.as_tensor(list(latents), device=l1_old.device))
-        fused = hasattr(eng, "site_update") and G1.is_cuda and os.environ.get("TSVGP_SITE_UPDATE", "1") != "0"
+        fused = hasattr(eng, "site_update") and G1.is_cuda
         if fused:
             # symmetrisation, the matrix of the final factorisation, the chain rule of util.py:429-438 and the convex update of
             # lambda_1 (tsvgp.py:284-297) in ONE launch (tsvgp_site_update_f64; it was a kernel, a gemv and ~10 elementwise launches)

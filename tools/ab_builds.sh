@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B of alternative builds of the kernel library on ONE box (box-to-box spread is larger than most effects).
-#   here:        tools/ab_builds.sh build old=<git-rev> nt="-DTSVGP_FILL_NT" ...   -> ab/lib<name>.so
-#                (name=<git-rev> builds that revision's sources AGAINST THAT REVISION'S header, name="-D..." the working tree
-#                with extra flags; a revision whose TSVGP_ABI_VERSION differs from the working tree's is refused at load time
+#   here:        tools/ab_builds.sh build old=<git-rev> o2="-O2" ...   -> ab/lib<name>.so
+#                (name=<git-rev> builds that revision's sources AGAINST THAT REVISION'S header, name="-..." the working tree
+#                with extra compiler flags; a revision whose TSVGP_ABI_VERSION differs from the working tree's is refused at load time
 #                by t-svgp_amd/_backend.py -- check out that revision's Python side to run it)
 #   on the box:  gpurun -- 'bash tools/ab_builds.sh run 1000000 125000 -- ab/libold.so t-svgp_amd/csrc/libtsvgp_hip.so'
 #                -> gpurun_out/ab/ab.txt: the K(X,Z) fill alone per build, then bench lines alternating over the builds

@@ -16,7 +16,7 @@ And one REPORT (``scan``), no longer a rule: MFMA-operand write-after-read sites
 in an A / B operand register of a ``v_mfma_f64_16x16x4_f64`` issued just before it corrupted results, and kept such reads apart
 by convention.  Round 4 measured it (tools/hazard_probe.hip, profiles/r04_hazard_probe.txt): no window exists -- not with an
 idle pipe, not behind one to three MFMAs in flight, not in a dependent accumulator chain, AGPR or VGPR accumulators, fp64 or
-fp32 -- and a build of panel1_kernel with the A fragments read FIRST and the registers released at once (-DTSVGP_HAZARD_AFIRST:
+fp32 -- and a build of panel1_kernel with the A fragments read FIRST and the registers released at once (a switch since removed, code in git history:
 100-190 sites at distance 1 in every instantiation) passes every kernel parity test and the bitwise-repeatability check.  The
 operands are read when the MFMA issues.  The scan stays as a report so that a future anomaly can be correlated with it.
 
