@@ -52,6 +52,8 @@ extern "C" {
                                  tsvgp_lik_map_hetero_* only (the moments kernels and tsvgp_lik_map_* reject it) */
 #define TSVGP_LIK_SOFTMAX 4   /* gpflow.likelihoods.Softmax(C) (a MonteCarloLikelihood) over C coupled latents:
                                  tsvgp_lik_map_softmax_* only */
+#define TSVGP_LIK_STUDENT_T 5 /* gpflow.likelihoods.StudentT(scale, df), 20-pt Gauss-Hermite: tsvgp_lik_map_scalar_* only */
+#define TSVGP_LIK_POISSON 6   /* gpflow.likelihoods.Poisson(binsize), exp link, closed form: tsvgp_lik_map_scalar_* only */
 #define TSVGP_LIK_NOCROP 0x100 /* OR-ed into the selector: leave g1 = d ve/d var uncropped (reference
                                   src/models/tsvgp_white.py:188-191 has no crop; src/models/tsvgp.py:262-263 has) */
 #define TSVGP_LIK_MEANONLY 0x200 /* OR-ed into the selector (NONE or GAUSSIAN only): skip the variance product.  Under a
@@ -224,6 +226,26 @@ int tsvgp_lik_map_hetero_f64(const double *mean, const double *var, const double
                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 int tsvgp_lik_map_hetero_f32(const float *mean, const float *var, const float *Y, int flags, float *g0, float *g1,
                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+
+/* (4b') The scalar likelihoods without an arm in the moments kernels (GPflow 2.2.1 [ext]), one latent column per call, behind the
+ *     moments like (4b): lik = TSVGP_LIK_STUDENT_T (param0 = scale > 0, param1 = df > 0) or TSVGP_LIK_POISSON (param0 = binsize > 0,
+ *     exp link; param1 ignored), optionally | TSVGP_LIK_NOCROP.
+ *        StudentT  log p(y | f) = lgamma((df+1)/2) - lgamma(df/2) - 1/2 log(df pi) - log scale - (df+1)/2 log1p(((y-f)/scale)^2 / df);
+ *                  ve by 20-point Gauss-Hermite, g0 = sum_i w_i l'(f_i), g1 = sum_i w_i l'(f_i) z_i / (2 sqrt(var)), f_i = mean + sqrt(var) z_i
+ *                  (the derivative of the quadrature sum, what tf.GradientTape returns at reference src/models/tsvgp.py:256-259)
+ *        Poisson   ve = y (mean + log b) - b exp(mean + var/2) - lgamma(y + 1),  g0 = y - b exp(mean + var/2),  g1 = -1/2 b exp(mean + var/2)
+ *     mean, var, Y: row n at element n * in_stride (a column of an [N x P] array: in_stride = P), read for n < N only;
+ *     g0, g1: row n at element n * out_stride, written for every n < Np (rows >= N zero; g1 cropped at -1e-8 unless
+ *     TSVGP_LIK_NOCROP, a NaN stays NaN); ve_partial [Np / 128] (fp64 per-128-row sums of ve); dparam_partial [Np / 128] or NULL
+ *     (StudentT only: per-128-row sums of d ve / d scale, for the M-step; must be NULL for Poisson); nonpos_partial [Np / 128]:
+ *     rows with var <= 0 or a non-finite mean.  Arithmetic in fp64 for either array type; the log-gamma terms that no row changes
+ *     are taken once on the host.  No atomics, a summation order fixed by the shape: two calls agree bit for bit. */
+int tsvgp_lik_map_scalar_f64(const double *mean, const double *var, const double *Y, int64_t in_stride, int lik, double param0,
+                             double param1, double *g0, double *g1, int64_t out_stride, double *ve_partial, double *dparam_partial,
+                             int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+int tsvgp_lik_map_scalar_f32(const float *mean, const float *var, const float *Y, int64_t in_stride, int lik, double param0,
+                             double param1, float *g0, float *g1, int64_t out_stride, double *ve_partial, double *dparam_partial,
+                             int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
 /* (4c) The per-datum site step of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-148) fused with the likelihood map of
  *     (4): mean, var, Y [N x P] -> g0, g1 as tsvgp_lik_map_* (never cropped: TSVGP_LIK_NOCROP semantics whatever lik says), then

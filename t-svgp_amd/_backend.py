@@ -29,6 +29,9 @@ LIK_NONE, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_HETERO = 3  # two coupled latents: tsvgp_lik_map_hetero_* only
 LIK_SOFTMAX = 4  # C coupled latents, Monte Carlo: tsvgp_lik_map_softmax_* only
 COUPLED_LIKS = (LIK_HETERO, LIK_SOFTMAX)  # likelihoods whose row couples its latents (Y [N, 1])
+LIK_STUDENT_T, LIK_POISSON = 5, 6  # one latent per target column, no arm in the moments kernels: tsvgp_lik_map_scalar_* only
+SCALAR_MAP_LIKS = (LIK_STUDENT_T, LIK_POISSON)
+MAPPED_LIKS = COUPLED_LIKS + SCALAR_MAP_LIKS  # likelihoods whose map runs behind the moments, not in their epilogue
 LIK_NOCROP = 0x100
 LIK_MEANONLY = 0x200
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 2, 3
@@ -141,6 +144,10 @@ _PROTOTYPES = {
                                          c_void_p]),
     "tsvgp_lik_map_hetero_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                          c_void_p]),
+    "tsvgp_lik_map_scalar_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_scalar_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_diag_site_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_diag_site_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <type_traits>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1733,6 +1734,86 @@ __global__ __launch_bounds__(TILE) void lik_map_hetero_kernel(const T* __restric
     __syncthreads();
     if (t == 0) {
         ve_partial[blockIdx.x] = red[0] + red[1];
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// lik_map_scalar_kernel: the scalar likelihoods that have no arm in the moments kernels' epilogue -- gpflow.likelihoods.StudentT
+// and gpflow.likelihoods.Poisson (exp link) [ext], GPflow 2.2.1 -- as a map of their own behind the moments, one latent column
+// per launch: (mean, var, Y) with element stride istride -> g0 = d ve / d mean, g1 = d ve / d var with element stride ostride
+// (rows >= N zero; g1 cropped at -1e-8 unless TSVGP_LIK_NOCROP, a NaN stays NaN as under np.minimum), per-128-row sums of ve and
+// (StudentT, dparam_partial != nullptr) of d ve / d scale, and the count of rows with var <= 0 or a non-finite mean.
+//   StudentT (p0 = scale s, p1 = df nu, c0 = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log s from the host):
+//     log p(y | f) = c0 - (nu+1)/2 log1p(r^2 / nu),  r = (y - f) / s;  ve and the derivative OF THE 20-point Gauss-Hermite sum:
+//     g0 = sum_i w_i l'(f_i),  g1 = sum_i w_i l'(f_i) z_i / (2 sqrt v),  f_i = m + sqrt(v) z_i,  l' = (nu+1) r / (s nu (1 + r^2/nu)),
+//     d l / d s = ((nu+1) u / (1 + u) - 1) / s with u = r^2 / nu.
+//   Poisson (p0 = binsize b, c0 = log b): the closed form GPflow takes under the exp link,
+//     ve = y (m + log b) - b exp(m + v/2) - lgamma(y + 1),  g0 = y - b exp(m + v/2),  g1 = -1/2 b exp(m + v/2).
+// fp64 arithmetic for either array type (the map moves 5 N elements and is bound by them).  One thread per row, one workgroup per
+// 128 rows; the sums are wave-reduced and written once per workgroup, no atomics: two calls agree bit for bit.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(TILE) void lik_map_scalar_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                              const T* __restrict__ Y, int64_t istride, int lik, double p0,
+                                                              double p1, double c0, T* __restrict__ g0o, T* __restrict__ g1o,
+                                                              int64_t ostride, double* __restrict__ ve_partial,
+                                                              double* __restrict__ dparam_partial,
+                                                              int32_t* __restrict__ nonpos_partial, int64_t N) {
+    __shared__ double red[TILE / 64], redp[TILE / 64];
+    __shared__ int redi[TILE / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n = (int64_t)blockIdx.x * TILE + t;
+    const bool live = n < N;
+    double g0 = 0.0, g1 = 0.0, ve = 0.0, dp = 0.0;
+    int bad = 0;
+    if (live) {
+        const double m = (double)mean[n * istride], v = (double)var[n * istride], y = (double)Y[n * istride];
+        if ((lik & 0xFF) == TSVGP_LIK_STUDENT_T) {
+            const double sd = sqrt(v), inv_s = 1.0 / p0, nu1 = p1 + 1.0, inv_nu = 1.0 / p1;
+            double a0 = 0.0, a1 = 0.0;
+#pragma unroll 2
+            for (int i = 0; i < 10; ++i) {  // node pairs +-z
+                const double z = GH_X[i], wi = GH_W[i];
+                const double rp = (y - (m + sd * z)) * inv_s, rm = (y - (m - sd * z)) * inv_s;
+                const double up = rp * rp * inv_nu, um = rm * rm * inv_nu;
+                const double dlp = nu1 * rp * inv_nu * inv_s / (1.0 + up), dlm = nu1 * rm * inv_nu * inv_s / (1.0 + um);
+                ve += wi * ((c0 - 0.5 * nu1 * log1p(up)) + (c0 - 0.5 * nu1 * log1p(um)));
+                a0 += wi * (dlp + dlm);
+                a1 += wi * z * (dlp - dlm);
+                dp += wi * ((nu1 * up / (1.0 + up) - 1.0) + (nu1 * um / (1.0 + um) - 1.0));
+            }
+            g0 = a0;
+            g1 = a1 / (2.0 * sd);
+            dp *= inv_s;
+        } else {  // TSVGP_LIK_POISSON
+            const double e = p0 * exp(m + 0.5 * v);
+            ve = y * (m + c0) - e - lgamma(y + 1.0);
+            g0 = y - e;
+            g1 = -0.5 * e;
+        }
+        if (!(lik & TSVGP_LIK_NOCROP) && g1 > -1e-8) g1 = -1e-8;  // reference tsvgp.py:262-263
+        bad = (v > 0.0 && isfinite(m)) ? 0 : 1;
+    }
+    g0o[n * ostride] = (T)g0;  // rows >= N of the padded outputs: zeros
+    g1o[n * ostride] = (T)g1;
+    double s = ve, d = dp;
+    int c = bad;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        d += __shfl_xor(d, o);
+        c += __shfl_xor(c, o);
+    }
+    if (lane == 0) {
+        red[w] = s;
+        redp[w] = d;
+        redi[w] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = red[0] + red[1];
+        if (dparam_partial) dparam_partial[blockIdx.x] = redp[0] + redp[1];
         nonpos_partial[blockIdx.x] = redi[0] + redi[1];
     }
 }
@@ -4931,6 +5012,31 @@ int lik_map_hetero(const T* mean, const T* var, const T* Y, int flags, T* g0, T*
 }
 
 template <typename T>
+int lik_map_scalar(const T* mean, const T* var, const T* Y, int64_t in_stride, int lik, double param0, double param1, T* g0, T* g1,
+                   int64_t out_stride, double* ve_partial, double* dparam_partial, int32_t* nonpos_partial, int64_t N, int64_t Np,
+                   void* stream) {
+    if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
+    if (in_stride < 1 || out_stride < 1) return TSVGP_EINVAL;
+    if (lik & ~(0xFF | TSVGP_LIK_NOCROP)) return TSVGP_EINVAL;
+    const int base = lik & 0xFF;
+    double c0;
+    if (base == TSVGP_LIK_STUDENT_T) {
+        if (!(param0 > 0.0) || !(param1 > 0.0) || !std::isfinite(param0) || !std::isfinite(param1)) return TSVGP_EINVAL;
+        // the terms of log p that no row changes, once, on the host
+        c0 = std::lgamma(0.5 * (param1 + 1.0)) - std::lgamma(0.5 * param1) - 0.5 * std::log(param1 * 3.14159265358979323846) -
+             std::log(param0);
+    } else if (base == TSVGP_LIK_POISSON) {
+        if (!(param0 > 0.0) || !std::isfinite(param0) || dparam_partial) return TSVGP_EINVAL;
+        c0 = std::log(param0);
+    } else {
+        return TSVGP_EINVAL;
+    }
+    hipLaunchKernelGGL(lik_map_scalar_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(TILE), 0, (hipStream_t)stream, mean, var, Y,
+                       in_stride, lik, param0, param1, c0, g0, g1, out_stride, ve_partial, dparam_partial, nonpos_partial, N);
+    return launch_status();
+}
+
+template <typename T>
 int lik_map_softmax(const T* mean, const T* var, const T* Y, int flags, int C, int S, const int64_t* rng_state, int64_t row_offset,
                     const T* epsilon, T* g0, T* g1, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
     if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
@@ -5361,6 +5467,18 @@ int tsvgp_diag_site_step_f32(const float* mean, const float* var, const float* Y
     if (!lambda_1_f32 || !lambda_2_f32) return TSVGP_EINVAL;
     return diag_site_step<float>(mean, var, Y, lik, lik_param, lr, lambda_1, lambda_2, lambda_1_f32, lambda_2_f32, ve_partial,
                                  nonpos_partial, N, Np, P, stream);
+}
+int tsvgp_lik_map_scalar_f64(const double* mean, const double* var, const double* Y, int64_t in_stride, int lik, double param0,
+                             double param1, double* g0, double* g1, int64_t out_stride, double* ve_partial, double* dparam_partial,
+                             int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_scalar<double>(mean, var, Y, in_stride, lik, param0, param1, g0, g1, out_stride, ve_partial, dparam_partial,
+                                  nonpos_partial, N, Np, stream);
+}
+int tsvgp_lik_map_scalar_f32(const float* mean, const float* var, const float* Y, int64_t in_stride, int lik, double param0,
+                             double param1, float* g0, float* g1, int64_t out_stride, double* ve_partial, double* dparam_partial,
+                             int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_scalar<float>(mean, var, Y, in_stride, lik, param0, param1, g0, g1, out_stride, ve_partial, dparam_partial,
+                                 nonpos_partial, N, Np, stream);
 }
 int tsvgp_lik_map_softmax_f64(const double* mean, const double* var, const double* Y, int flags, int C, int S,
                               const int64_t* rng_state, int64_t row_offset, const double* epsilon, double* g0, double* g1,

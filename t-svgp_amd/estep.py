@@ -19,7 +19,8 @@ A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``L
 the moments kernels' per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then its map
 (``tsvgp_lik_map_hetero`` / ``tsvgp_lik_map_softmax``) on them, then the site sums of the route -- ``run`` with P = latent_dim on
 one kernel, ``_run_batched`` on separate kernels, and a two-sweep form on the one-pass-per-latent path
-(``_run_separate_coupled``).
+(``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments kernels (``LIK_STUDENT_T``, ``LIK_POISSON``;
+Y [N x P], one column per latent) take the same passes with ``tsvgp_lik_map_scalar`` as their map, one launch per column.
 """
 from __future__ import annotations
 
@@ -52,6 +53,7 @@ class EStepStats:
     g0: Optional[torch.Tensor] = None  # [N, P]
     g1: Optional[torch.Tensor] = None  # [N, P]
     tile: Optional[torch.Tensor] = None  # [Np, Mp] the stored triangular product t_n = Tm k_n (run(keep_tile=True))
+    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d (likelihood parameter) over the rows (LIK_STUDENT_T: scale)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -111,6 +113,7 @@ class EStepEngine:
         self._side = None  # side stream of start_fill
         self.last_batched = False  # the last pass over separate kernels ran as batched launches
         self.last_trmm_batch = 1  # latents per whitening launch of that pass
+        self.last_dparam = None  # sum of d ve / d scale of the last ``_scalar_map`` (LIK_STUDENT_T), a device scalar
         self.profile = None  # set to a dict to record (start, stop) HIP events per kernel launch on the launch stream
         self.profile_only = None  # a set of kernel names: bracket only these launches
         # A/B switch (tools/dev_diag2.py): round 4's diagonal-block kernel instead of round 5's (TSVGP_POTRF_DIAG_V1)
@@ -561,6 +564,8 @@ class EStepEngine:
         nblk = Np // B.TILE
         P = mean.shape[1]
         g0, g1 = self._get("coupled_g0", (Np, P), T), self._get("coupled_g1", (Np, P), T)
+        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
+            return self._scalar_map(mean, var, Y, lik_id, N, Np, lik_param, g0, g1)
         ve_partial = self._get("ve_partial", (nblk,), torch.float64)
         nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
         if (lik_id & 0xFF) == B.LIK_SOFTMAX:
@@ -578,6 +583,40 @@ class EStepEngine:
                 mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(),
                 nonpos_partial.data_ptr(), N, Np, self._stream()))
         return g0, g1, ve_partial, nonpos_partial
+
+    def _scalar_map(self, mean, var, Y, lik_id, N, Np, lik_param, g0, g1):
+        """``tsvgp_lik_map_scalar_*`` (LIK_STUDENT_T, LIK_POISSON) on mean, var, Y [N, P] in the compute dtype: one launch per
+        column, each with its own run of the partial buffers [P, Np / 128].  ``lik_param`` = (param0, param1) of the likelihood
+        object.  Returns (g0, g1, ve_partial, nonpos_partial) as ``_coupled_map`` and leaves the sum of d ve / d scale (StudentT;
+        None otherwise) in ``self.last_dparam`` for the caller to put into its statistics."""
+        nblk = Np // B.TILE
+        P = mean.shape[1]
+        if tuple(Y.shape) != tuple(mean.shape) or tuple(var.shape) != tuple(mean.shape):
+            raise ValueError(f"mean, var and Y must share one shape [N, P], got {tuple(mean.shape)}, {tuple(var.shape)}, {tuple(Y.shape)}")
+        if not (mean.is_contiguous() and var.is_contiguous() and Y.is_contiguous()):
+            raise ValueError("the scalar likelihood map reads contiguous [N, P] arrays")
+        p0, p1 = (float(x) for x in lik_param)
+        student = (lik_id & 0xFF) == B.LIK_STUDENT_T
+        ve_partial = self._get("scalar_ve_partial", (P, nblk), torch.float64)
+        nonpos_partial = self._get("scalar_nonpos_partial", (P, nblk), torch.int32)
+        dpar = self._get("scalar_dparam_partial", (P, nblk), torch.float64) if student else None
+        fn = self._fn("tsvgp_lik_map_scalar")
+        esz = mean.element_size()
+        with torch.cuda.device(self.device):
+            for p in range(P):
+                off = p * esz
+                self._launch("tsvgp_lik_map_scalar", lambda: fn(
+                    mean.data_ptr() + off, var.data_ptr() + off, Y.data_ptr() + off, P, int(lik_id), p0, p1, g0.data_ptr() + off,
+                    g1.data_ptr() + off, P, ve_partial[p].data_ptr(), dpar[p].data_ptr() if student else None,
+                    nonpos_partial[p].data_ptr(), N, Np, self._stream()))
+        self.last_dparam = dpar.sum() if student else None
+        return g0, g1, ve_partial, nonpos_partial
+
+    @staticmethod
+    def _fused_param(lik_id, lik_param) -> float:
+        """The parameter of a likelihood fused into the moments kernel.  A pass with no likelihood (predictions) ignores
+        ``lik_param``: models hand over their likelihood's whatever the pass, and a mapped likelihood's is no float."""
+        return 0.0 if (lik_id & 0xFF) == B.LIK_NONE else float(lik_param)
 
     @staticmethod
     def _check_y(Y, N, P, lik_id, lik_param=None):
@@ -743,7 +782,7 @@ class EStepEngine:
         N, M, P = X.shape[0], Z.shape[0], moment_Tm.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         need_g = lik_id != B.LIK_NONE
-        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
+        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
         if need_g:
             Y = Y.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -803,9 +842,11 @@ class EStepEngine:
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
                     KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, kdiag, lik_flags,
-                    float(lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
+                    self._fused_param(lik_id, lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
                     nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
         stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
+        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
+            stats.dparam = self.last_dparam
         if want_moments:  # (the coupled path's mean / var are cached buffers: copies)
             stats.mean = mean.to(torch.float64, copy=coupled)
             stats.var = None if var is None else var.to(torch.float64, copy=coupled)
@@ -837,7 +878,7 @@ class EStepEngine:
         if len(kernel.kernels) != P:
             raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
         lik_id = kw.get("lik_id", B.LIK_NONE)
-        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
+        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
         if coupled or Y is not None:
             self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"))
         if X.shape[0] > 0:
@@ -905,6 +946,8 @@ class EStepEngine:
         Yc = Y.to(device=dev, dtype=T).contiguous()
         g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Yc, lik_id, N, Np, lik_param)
         out = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
+        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
+            out.dparam = self.last_dparam
         if want_moments:
             out.mean, out.var = mean.to(torch.float64, copy=True), var.to(torch.float64, copy=True)
         if want_grads:
@@ -1030,7 +1073,8 @@ class EStepEngine:
         Gaussian g0, g1 do not depend on it; ``var`` is then None and ``ve_sum`` NaN.
         lik_id LIK_HETERO (P = 2, Y [N, 1]) or LIK_SOFTMAX (P = C, Y [N, 1], ``lik_param`` = the Softmax object): moments of all
         latents with no likelihood, then the coupled map (``tsvgp_lik_map_hetero_*`` / ``tsvgp_lik_map_softmax_*``), then the
-        site sums.
+        site sums.  lik_id LIK_STUDENT_T / LIK_POISSON (Y [N, P], ``lik_param`` = the likelihood's (param0, param1)): the same
+        sequence with ``tsvgp_lik_map_scalar_*``, one launch per column; ``stats.dparam`` = sum d ve / d scale (StudentT).
         site_grads (lik_id NONE, one kernel): (g0, g1) [Np, P] in the compute dtype, rows >= N zero -- the site sums (and with
         ``keep_tile`` the stored product) of this pass with gradients a coupled map made elsewhere; the moments product then
         runs only for ``want_moments`` / ``keep_tile``, and ``ve_sum`` / ``nonpos`` are zero (the map's call counts them).
@@ -1067,7 +1111,7 @@ class EStepEngine:
             return st
         if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != D:
             raise ValueError(f"X must be [N, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
-        coupled = (lik_id & 0xFF) in B.COUPLED_LIKS
+        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
         if lik_id != B.LIK_NONE:
             self._check_y(Y, N, P, lik_id, lik_param)
             Y = Y.to(device=dev, dtype=T).contiguous()
@@ -1123,6 +1167,8 @@ class EStepEngine:
         if keep_tile:
             if P != 1 or mean_only or whiten_T is not None or not need_g:
                 raise ValueError("keep_tile: one latent, a likelihood, no whitening")
+            if coupled:
+                raise ValueError("keep_tile: a likelihood whose map runs behind the moments comes in through site_grads")
             tile = self._get("Tt", (Np, Mp), T)
             self.trmm(A, Tm[0], tile, moment_mode)
             mean = torch.mv(A[:N], gam[:, 0]).reshape(N, 1)  # gam: [Mp, 1], rows >= M zero
@@ -1151,7 +1197,7 @@ class EStepEngine:
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
                     A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if lik_id != B.LIK_NONE else None, variance, lik_flags,
-                    float(lik_param), _ptr(mean), _ptr(var), None if site_grads is not None else _ptr(g0),
+                    self._fused_param(lik_id, lik_param), _ptr(mean), _ptr(var), None if site_grads is not None else _ptr(g0),
                     None if site_grads is not None else _ptr(g1), ve_partial.data_ptr(),
                     nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
         if site_grads is not None:
@@ -1159,6 +1205,8 @@ class EStepEngine:
             stats = EStepStats(n_rows=N, ve_sum=zero, nonpos=zero.clone())
         else:
             stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
+            if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
+                stats.dparam = self.last_dparam
         stats.tile = tile
         if want_moments:
             stats.mean, stats.var = mean.to(torch.float64), (None if var is None else var.to(torch.float64))
@@ -1224,10 +1272,15 @@ class EStepEngine:
             ve_partial = self._get("ve_partial", (nblk,), torch.float64)
             nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
             g0, g1 = self._get("g0", (Np, 1), T), self._get("g1", (Np, 1), T)
-            with torch.cuda.device(dev):
-                B.check(self._fn("tsvgp_lik_map")(mean_t.data_ptr(), var_t.data_ptr(), Yc.data_ptr(), lik_id, float(lik_param),
-                                                   g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(),
-                                                   N, Np, 1, self._stream()), "tsvgp_lik_map")
+            if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
+                self._check_y(Yc, N, 1, lik_id, lik_param)
+                g0, g1, ve_partial, nonpos_partial = self._scalar_map(mean_t, var_t, Yc, lik_id, N, Np, lik_param, g0, g1)
+                stats.dparam = self.last_dparam
+            else:
+                with torch.cuda.device(dev):
+                    B.check(self._fn("tsvgp_lik_map")(mean_t.data_ptr(), var_t.data_ptr(), Yc.data_ptr(), lik_id, float(lik_param),
+                                                       g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(),
+                                                       N, Np, 1, self._stream()), "tsvgp_lik_map")
             stats.ve_sum = ve_partial.sum()
             stats.nonpos = nonpos_partial.sum().to(torch.float64)
             if sites:

@@ -1,6 +1,7 @@
 """Likelihood objects of the hot path: ``Gaussian``, ``Bernoulli`` (probit, 20-point Gauss-Hermite),
-``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite) and ``Softmax`` (C latents,
-Monte Carlo with an in-kernel counter-based generator: ``tsvgp_lik_map_softmax_*``).
+``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite), ``Softmax`` (C latents,
+Monte Carlo with an in-kernel counter-based generator: ``tsvgp_lik_map_softmax_*``), ``StudentT`` (20-point Gauss-Hermite) and
+``Poisson`` (exp link, closed form): the last two one latent per target column, ``tsvgp_lik_map_scalar_*`` behind the moments.
 
 Their N-sized maps -- variational expectations and the (mean, var) gradients the E-step needs
 (reference src/models/tsvgp.py:256-263) -- run inside the fused HIP moments kernel
@@ -57,6 +58,106 @@ class Bernoulli:
     def predict_log_density(self, Fmu, Fvar, Y):
         p = self.invlink(Fmu / torch.sqrt(1 + Fvar))
         return torch.sum(torch.log(torch.where(Y == 1, p, 1 - p)), dim=-1)
+
+
+def _gh_nodes(ref: torch.Tensor, n: int = 20):
+    """(z [n] = hermgauss nodes * sqrt(2), log(w / sqrt(pi)) [n]) in the dtype and on the device of ``ref``."""
+    z, w = np.polynomial.hermite.hermgauss(n)
+    return (torch.as_tensor(z * math.sqrt(2.0), dtype=ref.dtype, device=ref.device),
+            torch.as_tensor(np.log(w / math.sqrt(math.pi)), dtype=ref.dtype, device=ref.device))
+
+
+class StudentT:
+    """gpflow.likelihoods.StudentT(scale, df) [ext] (GPflow 2.2.1): ``scale`` a trainable positive parameter, ``df`` a plain
+    float; Y [N, P], one independent column per latent.  The variational expectations and their gradients run on the GPU
+    (``tsvgp_lik_map_scalar_*``, 20-point Gauss-Hermite); the predictive helpers here take the same 20 nodes.  ``t_SVGP`` and
+    ``t_SVGP_white`` take it; ``t_SVGP_sites`` and ``t_VGP``, whose likelihood is fused into another kernel, do not."""
+
+    lik_id = B.LIK_STUDENT_T
+    latent_dim = 1
+    num_gauss_hermite_points = 20
+
+    def __init__(self, scale=1.0, df=3.0):
+        if not float(df) > 0.0 or not math.isfinite(float(df)):
+            raise ValueError(f"StudentT: df must be positive and finite, got {df!r}")
+        if not float(scale) > 0.0:
+            raise ValueError(f"StudentT: scale must be positive, got {scale!r}")
+        self.df = float(df)
+        self.scale = Parameter(scale)
+
+    @property
+    def lik_param(self):
+        """(scale, df): the two scalars ``tsvgp_lik_map_scalar_*`` takes."""
+        return (self.scale.item(), self.df)
+
+    def graph_key(self):
+        """What a captured step bakes in beside the stamped ``scale``: ``df`` is a plain attribute."""
+        return (self.df,)
+
+    def log_prob(self, F, Y):
+        s, nu = self.scale.value.to(F.device, F.dtype), self.df
+        const = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)
+        return const - torch.log(s) - 0.5 * (nu + 1.0) * torch.log1p(torch.square((Y - F) / s) / nu)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        if self.df <= 2.0:
+            raise ValueError(f"StudentT: the predictive variance is not finite for df <= 2, got df = {self.df}")
+        s = self.scale.value.to(Fmu.device, Fmu.dtype)
+        return Fmu, Fvar + s * s * (self.df / (self.df - 2.0))
+
+    def predict_log_density(self, Fmu, Fvar, Y):
+        """log sum_i w_i p(y | f_i) over the 20 nodes, in log space, summed over the columns; [N]."""
+        z, logw = _gh_nodes(Fmu, self.num_gauss_hermite_points)
+        F = Fmu[..., None] + torch.sqrt(Fvar)[..., None] * z
+        return torch.sum(torch.logsumexp(self.log_prob(F, Y[..., None]) + logw, dim=-1), dim=-1)
+
+
+class Poisson:
+    """gpflow.likelihoods.Poisson(binsize) [ext] (GPflow 2.2.1) with its default exp inverse link -- the one under which GPflow
+    takes the variational expectations in closed form; any other ``invlink`` raises NotImplementedError.  Y [N, P] counts, one
+    independent column per latent.  The E-step's map runs on the GPU (``tsvgp_lik_map_scalar_*``); the predictive helpers take
+    20-point Gauss-Hermite as GPflow's ``ScalarLikelihood`` does.  ``t_SVGP`` and ``t_SVGP_white`` take it; ``t_SVGP_sites`` and
+    ``t_VGP``, whose likelihood is fused into another kernel, do not."""
+
+    lik_id = B.LIK_POISSON
+    latent_dim = 1
+    num_gauss_hermite_points = 20
+
+    def __init__(self, binsize=1.0, invlink=None, **kwargs):
+        if invlink is not None and invlink is not torch.exp and invlink is not np.exp and not _named(invlink, "exp"):
+            raise NotImplementedError(f"Poisson: only the exp inverse link is implemented, got {invlink!r}")
+        if kwargs:
+            raise NotImplementedError(f"Poisson: unsupported arguments {sorted(kwargs)}")
+        if not float(binsize) > 0.0 or not math.isfinite(float(binsize)):
+            raise ValueError(f"Poisson: binsize must be positive and finite, got {binsize!r}")
+        self.binsize = float(binsize)
+
+    @property
+    def lik_param(self):
+        """(binsize, 0): the two scalars ``tsvgp_lik_map_scalar_*`` takes."""
+        return (self.binsize, 0.0)
+
+    def graph_key(self):
+        return (self.binsize,)
+
+    def log_prob(self, F, Y):
+        return Y * (F + math.log(self.binsize)) - self.binsize * torch.exp(F) - torch.lgamma(Y + 1.0)
+
+    def _nodes(self, Fmu, Fvar):
+        z, logw = _gh_nodes(Fmu, self.num_gauss_hermite_points)
+        return Fmu[..., None] + torch.sqrt(Fvar)[..., None] * z, logw
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        """E[y] = E_q[b e^f], Var[y] = E_q[b e^f + (b e^f)^2] - E[y]^2 over the 20 nodes."""
+        F, logw = self._nodes(Fmu, Fvar)
+        w = torch.exp(logw)
+        rate = self.binsize * torch.exp(F)
+        ey = torch.sum(w * rate, dim=-1)
+        return ey, torch.sum(w * (rate + rate * rate), dim=-1) - ey * ey
+
+    def predict_log_density(self, Fmu, Fvar, Y):
+        F, logw = self._nodes(Fmu, Fvar)
+        return torch.sum(torch.logsumexp(self.log_prob(F, Y[..., None]) + logw, dim=-1), dim=-1)
 
 
 def _named(obj, name: str) -> bool:

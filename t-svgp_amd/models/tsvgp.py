@@ -316,6 +316,11 @@ class t_SVGP(base_SVGP):
         target column)."""
         return getattr(self.likelihood, "lik_id", None) in B.COUPLED_LIKS
 
+    def _mapped(self) -> bool:
+        """The likelihood's map runs behind the moments (``EStepEngine._coupled_map``): the coupled likelihoods and the scalar ones
+        without an arm in the moments kernels (StudentT, Poisson; Y [N, P] as for Gaussian)."""
+        return getattr(self.likelihood, "lik_id", None) in B.MAPPED_LIKS
+
     def _check_targets(self, X, Y):
         """Y [N, 1] under the coupled likelihood (the engine checks Y [N, P] for the others)."""
         if self._coupled() and (Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != X.shape[0]):
@@ -750,7 +755,8 @@ class t_SVGP(base_SVGP):
         which splits into an N-sized contraction with dK_fu (HIP: fill, moments, the site sums a1 = sum g0 k,
         A2 = sum g1 k k^T, U = K_fu Q, and ``tsvgp_kernel_grad``) and an M x M part in which a1, A2 are constants
         (torch autograd over K_uu(theta, Z), its factorisations and the KL).
-        Returns (elbo, {"variance", "lengthscales", "Z", "likelihood_variance" (Gaussian only)}), gradients of the ELBO
+        Returns (elbo, {"variance", "lengthscales", "Z", "likelihood_variance" (Gaussian only), "likelihood_scale" (StudentT
+        only: the sum of d ve / d scale comes out of the likelihood map's own pass)}), gradients of the ELBO
         with respect to the constrained parameter values; with one kernel per latent (``SeparateIndependent``) the kernel
         entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales".  With more than one rank ``data`` is this
         rank's shard."""
@@ -775,9 +781,10 @@ class t_SVGP(base_SVGP):
         # The TRUE d ve / d var here: the crop of tsvgp.py:262-263 belongs to the site update, not to the ELBO (with the
         # 1e-3 jitter of the probit link log p is not log-concave in the far tails, so some g1 are positive)
         parts = []
-        coupled = self._coupled()
+        coupled = self._mapped()
         if coupled:
-            # A likelihood that couples the latents cannot ride on a per-kernel pass: one pass over all latents maps the
+            # A likelihood that couples the latents cannot ride on a per-kernel pass (and the scalar maps behind the moments do not
+            # ride on the stored-tile form of one): one pass over all latents maps the
             # moments of all of them to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
             # their columns as given (``site_grads``) for the site sums and the kernel-gradient contraction.
             stc = eng.run(X, Y, ops["Z"], self.kernel, moment_Tm=Dm, moment_mode=ops["moment_mode"], gamma=beta,
@@ -828,6 +835,9 @@ class t_SVGP(base_SVGP):
             st.acc2, st.acc1 = torch.cat([s_.acc2 for s_ in parts], dim=0), torch.cat([s_.acc1 for s_ in parts], dim=0)
         if coupled:
             st.ve_sum, st.nonpos = stc.ve_sum, stc.nonpos
+        student = self.likelihood.lik_id == B.LIK_STUDENT_T
+        if student:  # sum_n d ve_n / d scale, summed over the ranks with the residual's slot (Gaussian only: free here)
+            res = stc.dparam
         extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1)])
         acc2, acc1, ve_sum, nonpos, rows, tail = D_.reduce_stats(st, P, M, True, self._reduce(), eng, extra=extra)
         o = 0
@@ -896,6 +906,8 @@ class t_SVGP(base_SVGP):
         if gaussian:
             s2 = self.likelihood.lik_param
             grads["likelihood_variance"] = scale * (-0.5 * rows * P / s2 + 0.5 * res / (s2 * s2))
+        if student:
+            grads["likelihood_scale"] = scale * res
         elbo = ve_sum * scale - kl
         return elbo, grads
 

@@ -45,7 +45,9 @@ from .tsvgp_white import t_SVGP_white
 
 
 class t_SVGP_sites(base_SVGP):
-    """Class for the t-SVGP model with sites (reference src/models/tsvgp_sites.py:20-191)."""
+    """Class for the t-SVGP model with sites (reference src/models/tsvgp_sites.py:20-191).  Likelihoods: Gaussian and Bernoulli,
+    the arms of the fused site step (``tsvgp_diag_site_step_*``); ``StudentT`` and ``Poisson``, whose map is a kernel of its own
+    behind the moments of ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here."""
 
     # the M x M algebra and the route logic are t_SVGP_white's, on the projected (l, L) in place of its state
     DIRECT_MAX_COND = t_SVGP_white.DIRECT_MAX_COND
@@ -64,6 +66,10 @@ class t_SVGP_sites(base_SVGP):
                  lambda_1=None, lambda_2=None, num_latent=1, compute_dtype=None, device=None, projection="auto",
                  skip_unused_variance=False):
         x_data, y_data = data
+        if getattr(likelihood, "lik_id", None) in B.SCALAR_MAP_LIKS:
+            raise NotImplementedError(f"t_SVGP_sites does not take the {type(likelihood).__name__} likelihood: its likelihood map is "
+                                      "fused into tsvgp_diag_site_step_*, which has Gaussian and Bernoulli arms only; use t_SVGP or "
+                                      "t_SVGP_white")
         super().__init__(kernel, likelihood, inducing_variable, mean_function=mean_function, num_latent_gps=num_latent_gps,
                          num_data=int(x_data.shape[0]), compute_dtype=compute_dtype, device=device)
         if projection not in ("auto", "whitened", "direct"):

@@ -47,7 +47,9 @@ from ..sites import DiagSites
 
 
 class t_VGP:
-    """Class for the t-VGP model (reference src/models/tvgp.py:18-193)."""
+    """Class for the t-VGP model (reference src/models/tvgp.py:18-193).  Likelihoods: Gaussian and Bernoulli, the arms of the fused
+    row sweep (``tsvgp_vgp_rows_f64``); ``StudentT`` and ``Poisson``, whose map is a kernel of its own behind the moments of
+    ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here."""
 
     def __init__(self, data, kernel, likelihood, mean_function=None, num_latent=1, *, device=None):
         x_data, y_data = data
@@ -58,6 +60,9 @@ class t_VGP:
         if getattr(likelihood, "lik_id", None) in B.COUPLED_LIKS or getattr(likelihood, "latent_dim", 1) != 1:
             raise ValueError("t_VGP is defined for a likelihood over one latent GP (tvgp.py:85: sW sW^T * K), got "
                              f"{type(likelihood).__name__}")
+        if getattr(likelihood, "lik_id", None) in B.SCALAR_MAP_LIKS:
+            raise NotImplementedError(f"t_VGP does not take the {type(likelihood).__name__} likelihood: its likelihood map is fused "
+                                      "into tsvgp_vgp_rows_f64, which has Gaussian and Bernoulli arms only; use t_SVGP or t_SVGP_white")
         self.device = torch.device(device) if device is not None else default_device()
         X = to_tensor(x_data, dtype=default_float(), device=self.device).contiguous()
         Y = to_tensor(y_data, dtype=default_float(), device=self.device).contiguous()
