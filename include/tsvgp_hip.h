@@ -54,6 +54,8 @@ extern "C" {
                                  tsvgp_lik_map_softmax_* only */
 #define TSVGP_LIK_STUDENT_T 5 /* gpflow.likelihoods.StudentT(scale, df), 20-pt Gauss-Hermite: tsvgp_lik_map_scalar_* only */
 #define TSVGP_LIK_POISSON 6   /* gpflow.likelihoods.Poisson(binsize), exp link, closed form: tsvgp_lik_map_scalar_* only */
+#define TSVGP_LIK_MULTICLASS 7 /* gpflow.likelihoods.MultiClass(C) with the RobustMax link over C coupled latents, 20-pt
+                                  Gauss-Hermite over the labelled latent: tsvgp_lik_map_robustmax_* only */
 #define TSVGP_LIK_NOCROP 0x100 /* OR-ed into the selector: leave g1 = d ve/d var uncropped (reference
                                   src/models/tsvgp_white.py:188-191 has no crop; src/models/tsvgp.py:262-263 has) */
 #define TSVGP_LIK_MEANONLY 0x200 /* OR-ed into the selector (NONE or GAUSSIAN only): skip the variance product.  Under a
@@ -226,6 +228,28 @@ int tsvgp_lik_map_hetero_f64(const double *mean, const double *var, const double
                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 int tsvgp_lik_map_hetero_f32(const float *mean, const float *var, const float *Y, int flags, float *g0, float *g1,
                              double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+
+/* (4b'') The MultiClass likelihood map with the RobustMax inverse link (gpflow.likelihoods.MultiClass(C), GPflow 2.2.1 [ext]): C
+ *     coupled latents, deterministic.  With y the row's label, s_c = sqrt(max(var_c, 1e-10)), (x_i, w_i) = hermgauss(20),
+ *        X_i  = mean_y + x_i sqrt(max(2 var_y, 1e-10)),   d_ci = (X_i - mean_c) / s_c,
+ *        F_ci = 1/2 (1 + erf(d_ci / sqrt 2)) (1 - 2e-4) + 1e-4,   P_i = prod_{c != y} F_ci,   p = sum_i w_i / sqrt(pi) P_i,
+ *        ve   = p log(1 - epsilon) + (1 - p) log(epsilon / (C - 1))
+ *     and g0 = d ve / d mean, g1 = d ve / d var of that quadrature sum (reference src/models/tsvgp.py:256-263); with
+ *     kappa = log(1 - epsilon) - log(epsilon / (C - 1)), r_ci = (1 - 2e-4) N(d_ci) / F_ci, z_i = sqrt(2) x_i:
+ *        c != y:  g0_c = -kappa sum_i w_i/sqrt(pi) P_i r_ci / s_c,   g1_c = -kappa sum_i w_i/sqrt(pi) P_i r_ci d_ci / (2 var_c)
+ *        c == y:  g0_y = kappa sum_i w_i/sqrt(pi) P_i sum_{c != y} r_ci / s_c,   g1_y = the same sum with z_i / (2 s_y) inside.
+ *     The derivative through an active clip (var_c < 1e-10, 2 var_y < 1e-10) is zero, as under tf.clip_by_value.
+ *     mean, var [N x C]; Y [N x 1] class labels 0 .. C-1 in the array type (never used as an address; a label that is not an
+ *     integer in [0, C) makes its row's ve, g0, g1 NaN); flags = TSVGP_LIK_MULTICLASS, optionally | TSVGP_LIK_NOCROP;
+ *     2 <= C <= TSVGP_MAX_BATCH; 0 < epsilon < 1.  g0, g1 [Np x C] (rows >= N zero; g1 cropped at -1e-8 unless
+ *     TSVGP_LIK_NOCROP, a NaN stays NaN), ve_partial [Np / 128] (fp64 per-128-row sums of ve), nonpos_partial [Np / 128]: rows
+ *     with any var_c <= 0 or a non-finite mean.  Arithmetic in fp64 for either array type.  No atomics, a summation order fixed
+ *     by the shape: two calls agree bit for bit. */
+int tsvgp_lik_map_robustmax_f64(const double *mean, const double *var, const double *Y, int flags, int C, double epsilon,
+                                double *g0, double *g1, double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np,
+                                void *stream);
+int tsvgp_lik_map_robustmax_f32(const float *mean, const float *var, const float *Y, int flags, int C, double epsilon, float *g0,
+                                float *g1, double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
 /* (4b') The scalar likelihoods without an arm in the moments kernels (GPflow 2.2.1 [ext]), one latent column per call, behind the
  *     moments like (4b): lik = TSVGP_LIK_STUDENT_T (param0 = scale > 0, param1 = df > 0) or TSVGP_LIK_POISSON (param0 = binsize > 0,

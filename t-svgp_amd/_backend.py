@@ -28,7 +28,8 @@ MAX_BATCH = 32  # TSVGP_MAX_BATCH: latents per launch of the *_batched entry poi
 LIK_NONE, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_HETERO = 3  # two coupled latents: tsvgp_lik_map_hetero_* only
 LIK_SOFTMAX = 4  # C coupled latents, Monte Carlo: tsvgp_lik_map_softmax_* only
-COUPLED_LIKS = (LIK_HETERO, LIK_SOFTMAX)  # likelihoods whose row couples its latents (Y [N, 1])
+LIK_MULTICLASS = 7  # C coupled latents, RobustMax link, 20-point Gauss-Hermite: tsvgp_lik_map_robustmax_* only
+COUPLED_LIKS = (LIK_HETERO, LIK_SOFTMAX, LIK_MULTICLASS)  # likelihoods whose row couples its latents (Y [N, 1])
 LIK_STUDENT_T, LIK_POISSON = 5, 6  # one latent per target column, no arm in the moments kernels: tsvgp_lik_map_scalar_* only
 SCALAR_MAP_LIKS = (LIK_STUDENT_T, LIK_POISSON)
 MAPPED_LIKS = COUPLED_LIKS + SCALAR_MAP_LIKS  # likelihoods whose map runs behind the moments, not in their epilogue
@@ -156,6 +157,10 @@ _PROTOTYPES = {
                                           c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_lik_map_softmax_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_robustmax_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_robustmax_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_mc_normals_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_mc_normals_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_site_accum_work_bytes_f64": (c_int64, [c_int, c_int, c_int]),

@@ -2095,6 +2095,134 @@ __global__ __launch_bounds__(256) void lik_map_softmax_kernel(const T* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// lik_map_robustmax_kernel: gpflow.likelihoods.MultiClass(C) with the RobustMax inverse link [ext] (GPflow 2.2.1), the
+// deterministic map over C coupled latents.  With y the row's label, s_c = sqrt(max(v_c, 1e-10)), the 20 Gauss-Hermite nodes
+// X_i = m_y + x_i sqrt(max(2 v_y, 1e-10)) over the labelled latent and d_ci = (X_i - m_c) / s_c,
+//     F_ci = 1/2 (1 + erf(d_ci / sqrt 2)) (1 - 2e-4) + 1e-4,   P_i = prod_{c != y} F_ci,   p = sum_i w_i P_i   (w_i: weights / sqrt pi)
+//     ve = p log(1 - eps) + (1 - p) log(eps / (C - 1)),   kappa = log(1 - eps) - log(eps / (C - 1)),
+// and the derivative OF THAT SUM (reference src/models/tsvgp.py:256-263), r_ci = (1 - 2e-4) N(d_ci) / F_ci:
+//     c != y:  g0_c = -kappa sum_i w_i P_i r_ci / s_c,             g1_c = -kappa sum_i w_i P_i r_ci d_ci / (2 v_c)
+//     c == y:  g0_y =  kappa sum_i w_i P_i sum_{c != y} r_ci / s_c,  g1_y = kappa sum_i w_i P_i (sum_{c != y} r_ci / s_c) z_i / (2 s_y)
+// (z_i = sqrt 2 x_i); a clipped variance has derivative zero, as under tf.clip_by_value; a NaN variance stays NaN.
+// One thread per row, one workgroup per 128 rows as lik_map_scalar_kernel.  The loops run class by class: the first pass
+// multiplies the 20 products P_i up (one LDS column of 20 doubles per thread: indexed by the node, never by the class, so
+// nothing of the row is indexed at run time in registers and nothing goes to scratch), the second evaluates F_ci again,
+// weighs r_ci with the finished P_i and writes class c's g0, g1 at once, summing the labelled class's two values on the way.
+// The label is never an address: the class loop compares its counter with it; a label that is no integer in [0, C) makes the
+// row's ve, g0, g1 NaN.  fp64 arithmetic for either array type; no atomics, a summation order fixed by the shape.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double robustmax_cdf(double d) {
+    return 0.5 * (1.0 + erf(d * 0.70710678118654752440)) * (1.0 - 2e-4) + 1e-4;
+}
+
+template <typename T>
+__global__ __launch_bounds__(TILE) void lik_map_robustmax_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                                 const T* __restrict__ Y, int flags, int C, double log_hit,
+                                                                 double log_miss, T* __restrict__ g0o, T* __restrict__ g1o,
+                                                                 double* __restrict__ ve_partial,
+                                                                 int32_t* __restrict__ nonpos_partial, int64_t N) {
+    __shared__ double prod[20][TILE];  // P_i of the thread's row: nodes +z_i in [i], -z_i in [10 + i]
+    __shared__ double red[TILE / 64];
+    __shared__ int redi[TILE / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n = (int64_t)blockIdx.x * TILE + t;
+    const bool crop = !(flags & TSVGP_LIK_NOCROP);
+    T* __restrict__ g0r = g0o + n * C;
+    T* __restrict__ g1r = g1o + n * C;
+    double ve = 0.0;
+    int bad = 0;
+    if (n < N) {
+        const T* __restrict__ mr = mean + n * C;
+        const T* __restrict__ vr = var + n * C;
+        const double y = (double)Y[n];
+        const double poison = (y >= 0.0 && y < (double)C && y == floor(y)) ? 0.0 : __builtin_nan("");
+        double my = 0.0, vy = 1.0;
+        for (int c = 0; c < C; ++c) {
+            const double m = (double)mr[c], v = (double)vr[c];
+            bad |= (v > 0.0 && isfinite(m)) ? 0 : 1;
+            if ((double)c == y) my = m, vy = v;
+        }
+        const bool clip_y = 2.0 * vy < 1e-10;
+        const double sy = sqrt(clip_y ? 1e-10 : 2.0 * vy) * 0.70710678118654752440;  // s_y: X_i = m_y + z_i s_y
+#pragma unroll
+        for (int i = 0; i < 20; ++i) prod[i][t] = 1.0;
+        for (int c = 0; c < C; ++c) {
+            if ((double)c == y) continue;
+            const double m = (double)mr[c], v = (double)vr[c];
+            const double is = 1.0 / sqrt(v < 1e-10 ? 1e-10 : v);
+            const double d0 = (my - m) * is, dz = sy * is;
+#pragma unroll 2
+            for (int i = 0; i < 10; ++i) {
+                const double z = GH_X[i];
+                prod[i][t] *= robustmax_cdf(d0 + dz * z);
+                prod[10 + i][t] *= robustmax_cdf(d0 - dz * z);
+            }
+        }
+        double p = 0.0;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) p += GH_W[i] * (prod[i][t] + prod[10 + i][t]);
+        ve = p * log_hit + (1.0 - p) * log_miss + poison;
+        const double kappa = log_hit - log_miss;
+        double gy0 = 0.0, gy1 = 0.0;
+        for (int c = 0; c < C; ++c) {
+            if ((double)c == y) continue;
+            const double m = (double)mr[c], v = (double)vr[c];
+            const bool clip_c = v < 1e-10;
+            const double vc = clip_c ? 1e-10 : v;
+            const double is = 1.0 / sqrt(vc);
+            const double d0 = (my - m) * is, dz = sy * is;
+            double a = 0.0, b = 0.0, az = 0.0;
+#pragma unroll 2
+            for (int i = 0; i < 10; ++i) {
+                const double z = GH_X[i], wi = GH_W[i];
+                const double dp = d0 + dz * z, dm = d0 - dz * z;
+                // w_i P_i r_ci at +z_i and -z_i
+                const double rp = wi * prod[i][t] * ((1.0 - 2e-4) * 0.39894228040143267794) * exp(-0.5 * dp * dp) / robustmax_cdf(dp);
+                const double rm = wi * prod[10 + i][t] * ((1.0 - 2e-4) * 0.39894228040143267794) * exp(-0.5 * dm * dm) / robustmax_cdf(dm);
+                a += rp + rm;
+                b += rp * dp + rm * dm;
+                az += (rp - rm) * z;
+            }
+            gy0 += a * is;
+            gy1 += az * is;
+            double g1 = clip_c ? 0.0 : -kappa * b / (2.0 * vc);
+            if (crop && g1 > -1e-8) g1 = -1e-8;  // reference tsvgp.py:262-263; a NaN stays NaN
+            g0r[c] = (T)(-kappa * a * is + poison);
+            g1r[c] = (T)(g1 + poison);
+        }
+        double g1y = clip_y ? 0.0 : kappa * gy1 / (2.0 * sy);
+        if (crop && g1y > -1e-8) g1y = -1e-8;
+        for (int c = 0; c < C; ++c) {
+            if ((double)c == y) {
+                g0r[c] = (T)(kappa * gy0);
+                g1r[c] = (T)g1y;
+            }
+        }
+    } else {
+        for (int c = 0; c < C; ++c) {  // rows >= N of the [Np x C] outputs: zeros
+            g0r[c] = (T)0.0;
+            g1r[c] = (T)0.0;
+        }
+    }
+    double s = ve;
+    int k = bad;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        k += __shfl_xor(k, o);
+    }
+    if (lane == 0) {
+        red[w] = s;
+        redi[w] = k;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = red[0] + red[1];
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // mean_lik_kernel (TSVGP_LIK_MEANONLY): mean[n, p] = sum_j A[n, j] * gamma[j, p] and, for the Gaussian likelihood,
 // g0 = (y - mean) / s2, g1 = -1 / (2 s2) -- neither depends on the predictive variance.  HBM bound: one sweep of A.
 // One workgroup per 128-row panel (same grid as panel_kernel, so the per-workgroup partial buffers keep their
@@ -5057,6 +5185,20 @@ int lik_map_softmax(const T* mean, const T* var, const T* Y, int flags, int C, i
 }
 
 template <typename T>
+int lik_map_robustmax(const T* mean, const T* var, const T* Y, int flags, int C, double epsilon, T* g0, T* g1, double* ve_partial,
+                      int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
+    if ((flags & ~TSVGP_LIK_NOCROP) != TSVGP_LIK_MULTICLASS) return TSVGP_EINVAL;
+    if (C < 2 || C > TSVGP_MAX_BATCH || !(epsilon > 0.0 && epsilon < 1.0)) return TSVGP_EINVAL;
+    if (Np / TILE > 0x7fffffff) return TSVGP_EINVAL;  // the grid's block count is 31 bits
+    // the two values log p(y | f) takes, once, on the host: log(1 - eps) where the labelled latent is the largest, log(eps / (C - 1))
+    const double log_hit = std::log(1.0 - epsilon), log_miss = std::log(epsilon / (double)(C - 1));
+    hipLaunchKernelGGL(lik_map_robustmax_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(TILE), 0, (hipStream_t)stream, mean, var, Y,
+                       flags, C, log_hit, log_miss, g0, g1, ve_partial, nonpos_partial, N);
+    return launch_status();
+}
+
+template <typename T>
 int mc_normals(T* out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void* stream) {
     if (!out || S < 1 || S > TSVGP_MC_MAX_SAMPLES || N <= 0 || C < 1 || C > TSVGP_MAX_BATCH || row_offset < 0) return TSVGP_EINVAL;
     const int64_t per_row = S * ((C + 3) / 4);  // <= 2^28 * 8
@@ -5491,6 +5633,14 @@ int tsvgp_lik_map_softmax_f32(const float* mean, const float* var, const float* 
                               double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
     return lik_map_softmax<float>(mean, var, Y, flags, C, S, rng_state, row_offset, epsilon, g0, g1, ve_partial, nonpos_partial, N,
                                   Np, stream);
+}
+int tsvgp_lik_map_robustmax_f64(const double* mean, const double* var, const double* Y, int flags, int C, double epsilon, double* g0,
+                                double* g1, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_robustmax<double>(mean, var, Y, flags, C, epsilon, g0, g1, ve_partial, nonpos_partial, N, Np, stream);
+}
+int tsvgp_lik_map_robustmax_f32(const float* mean, const float* var, const float* Y, int flags, int C, double epsilon, float* g0,
+                                float* g1, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_robustmax<float>(mean, var, Y, flags, C, epsilon, g0, g1, ve_partial, nonpos_partial, N, Np, stream);
 }
 int tsvgp_mc_normals_f64(double* out, int64_t seed, int64_t draw, int64_t row_offset, int64_t S, int64_t N, int C, void* stream) {
     return mc_normals<double>(out, seed, draw, row_offset, S, N, C, stream);

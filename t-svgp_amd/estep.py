@@ -15,9 +15,9 @@ Kernel sequence of ``run(..., sites=True)`` by projection route (models/tsvgp.py
     whitened:   fill -> trmm(UPPER) -> moments(UPPER, on B) -> site_accum(B)
     projected:  fill -> trmm(UPPER) -> moments(UPPER, on B) -> trmm(LOWER) -> site_accum(a)
 ``mean_only`` replaces the moments product by one HBM-bound sweep (Gaussian likelihood, TSVGP_LIK_MEANONLY).
-A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``LIK_SOFTMAX``: C latents; Y [N x 1]) cannot run in
+A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``LIK_SOFTMAX`` / ``LIK_MULTICLASS``: C latents; Y [N x 1]) cannot run in
 the moments kernels' per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then its map
-(``tsvgp_lik_map_hetero`` / ``tsvgp_lik_map_softmax``) on them, then the site sums of the route -- ``run`` with P = latent_dim on
+(``tsvgp_lik_map_hetero`` / ``tsvgp_lik_map_softmax`` / ``tsvgp_lik_map_robustmax``) on them, then the site sums of the route -- ``run`` with P = latent_dim on
 one kernel, ``_run_batched`` on separate kernels, and a two-sweep form on the one-pass-per-latent path
 (``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments kernels (``LIK_STUDENT_T``, ``LIK_POISSON``;
 Y [N x P], one column per latent) take the same passes with ``tsvgp_lik_map_scalar`` as their map, one launch per column.
@@ -557,7 +557,8 @@ class EStepEngine:
     def _coupled_map(self, mean, var, Y, lik_id, N, Np, lik_param=None):
         """g0, g1 [Np, P] (rows >= N zero), ve_partial, nonpos_partial of the coupled likelihood map on mean, var [N, P] and
         Y [N, 1] in the compute dtype: ``tsvgp_lik_map_hetero_*`` (P = 2) or ``tsvgp_lik_map_softmax_*`` (P = C; ``lik_param`` is
-        the Softmax object: its sample count, row offset and device generator state, whose draw this call advances in-stream).
+        the Softmax object: its sample count, row offset and device generator state, whose draw this call advances in-stream) or
+        ``tsvgp_lik_map_robustmax_*`` (P = C; ``lik_param`` is the MultiClass object: its epsilon; deterministic, nothing advances).
         The outputs are cached buffers of their own: the site sums read them where they are, and a one-latent pass of the same
         call (``site_grads``) does not overwrite them."""
         T = self.dtype
@@ -577,6 +578,13 @@ class EStepEngine:
                     int(lik.row_offset), None, g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np,
                     self._stream()))
                 lik.advance()
+            return g0, g1, ve_partial, nonpos_partial
+        if (lik_id & 0xFF) == B.LIK_MULTICLASS:  # deterministic: one launch, nothing to advance
+            lik = lik_param
+            with torch.cuda.device(self.device):
+                self._launch("tsvgp_lik_map_robustmax", lambda: self._fn("tsvgp_lik_map_robustmax")(
+                    mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), P, float(lik.epsilon), g0.data_ptr(), g1.data_ptr(),
+                    ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, self._stream()))
             return g0, g1, ve_partial, nonpos_partial
         with torch.cuda.device(self.device):
             self._launch("tsvgp_lik_map_hetero", lambda: self._fn("tsvgp_lik_map_hetero")(
@@ -620,7 +628,7 @@ class EStepEngine:
 
     @staticmethod
     def _check_y(Y, N, P, lik_id, lik_param=None):
-        """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX: C) maps its latents onto ONE target column:
+        """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX, LIK_MULTICLASS: C) maps its latents onto ONE target column:
         Y [N, 1], P = latent_dim."""
         if (lik_id & 0xFF) == B.LIK_HETERO:
             if P != 2 or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
@@ -631,6 +639,12 @@ class EStepEngine:
             C = getattr(lik_param, "latent_dim", None)
             if P != C or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
                 raise ValueError(f"the Softmax likelihood needs {C} latent GPs (its latent_dim) and Y [N, 1] = [{N}, 1], got "
+                                 f"P = {P} and Y {None if Y is None else tuple(Y.shape)}")
+            return
+        if (lik_id & 0xFF) == B.LIK_MULTICLASS:
+            C = getattr(lik_param, "latent_dim", None)
+            if P != C or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
+                raise ValueError(f"the MultiClass likelihood needs {C} latent GPs (its latent_dim) and Y [N, 1] = [{N}, 1], got "
                                  f"P = {P} and Y {None if Y is None else tuple(Y.shape)}")
             return
         if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:

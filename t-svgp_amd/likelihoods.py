@@ -1,7 +1,8 @@
 """Likelihood objects of the hot path: ``Gaussian``, ``Bernoulli`` (probit, 20-point Gauss-Hermite),
 ``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite), ``Softmax`` (C latents,
 Monte Carlo with an in-kernel counter-based generator: ``tsvgp_lik_map_softmax_*``), ``StudentT`` (20-point Gauss-Hermite) and
-``Poisson`` (exp link, closed form): the last two one latent per target column, ``tsvgp_lik_map_scalar_*`` behind the moments.
+``Poisson`` (exp link, closed form): the last two one latent per target column, ``tsvgp_lik_map_scalar_*`` behind the moments;
+``MultiClass`` (C latents, ``RobustMax`` link, 20-point Gauss-Hermite over the labelled latent: ``tsvgp_lik_map_robustmax_*``).
 
 Their N-sized maps -- variational expectations and the (mean, var) gradients the E-step needs
 (reference src/models/tsvgp.py:256-263) -- run inside the fused HIP moments kernel
@@ -363,3 +364,107 @@ class Softmax:
         if epsilon is None:
             self.advance()
         return torch.cat(out)
+
+
+class RobustMax:
+    """gpflow.likelihoods.RobustMax(num_classes, epsilon) [ext]: the inverse link of ``MultiClass`` -- probability 1 - epsilon on the
+    class whose latent is the largest, epsilon / (num_classes - 1) on each of the others.  A holder of the two numbers: the
+    quadrature lives in ``MultiClass`` and in ``tsvgp_lik_map_robustmax_*``."""
+
+    def __init__(self, num_classes: int, epsilon: float = 1e-3):
+        if int(num_classes) != num_classes or not 2 <= num_classes <= B.MAX_BATCH:
+            raise ValueError(f"RobustMax: num_classes must be an integer in [2, {B.MAX_BATCH}], got {num_classes!r}")
+        if not 0.0 < float(epsilon) < 1.0:
+            raise ValueError(f"RobustMax: epsilon must lie in (0, 1), got {epsilon!r}")
+        self.num_classes = int(num_classes)
+        self.epsilon = float(epsilon)
+
+    @property
+    def _eps_k1(self) -> float:
+        return self.epsilon / (self.num_classes - 1.0)
+
+
+class MultiClass:
+    """gpflow.likelihoods.MultiClass(num_classes) [ext] (GPflow 2.2.1) with its default ``RobustMax`` inverse link: C = num_classes
+    latent GPs, Y [N, 1] class labels 0 .. C-1, p(y | f) = 1 - epsilon where the labelled latent is the largest, epsilon / (C - 1)
+    otherwise.  Every expectation is the 20-point Gauss-Hermite rule over the labelled latent of the probability that it is the
+    largest (``RobustMax.prob_is_largest``), so -- unlike ``Softmax`` -- nothing is drawn: the E-step has a fixed point, a replayed
+    graph repeats an eager step bit for bit and ``elbo_and_grads`` is exact.  The variational expectations and their gradients
+    run on the GPU (``tsvgp_lik_map_robustmax_*``); the helpers here evaluate the same sum in torch on the test points."""
+
+    lik_id = B.LIK_MULTICLASS
+    num_gauss_hermite_points = 20
+    _CHUNK = 1 << 22  # elements per [rows, C, C, 20] evaluation of the predictive helpers: the rows of a chunk follow from it
+
+    def __init__(self, num_classes: int, invlink=None, epsilon: float = 1e-3, **kwargs):
+        if int(num_classes) != num_classes or not 2 <= num_classes <= B.MAX_BATCH:
+            raise ValueError(f"MultiClass: num_classes must be an integer in [2, {B.MAX_BATCH}], got {num_classes!r}")
+        if kwargs:
+            raise NotImplementedError(f"MultiClass: unsupported arguments {sorted(kwargs)}")
+        if invlink is not None:
+            if not isinstance(invlink, RobustMax):
+                raise NotImplementedError(f"MultiClass: only the RobustMax inverse link is implemented, got {invlink!r}")
+            if invlink.num_classes != int(num_classes):
+                raise ValueError(f"MultiClass: the RobustMax link is over {invlink.num_classes} classes, the likelihood over "
+                                 f"{num_classes}")
+            epsilon = invlink.epsilon
+        if not 0.0 < float(epsilon) < 1.0:
+            raise ValueError(f"MultiClass: epsilon must lie in (0, 1), got {epsilon!r}")
+        self.num_classes = self.latent_dim = int(num_classes)
+        self.epsilon = float(epsilon)
+        self.invlink = invlink if invlink is not None else RobustMax(self.num_classes, self.epsilon)
+
+    # the engine takes the likelihood's scalar through ``lik_param``; this likelihood has two (C, epsilon): it hands over itself
+    @property
+    def lik_param(self):
+        return self
+
+    def graph_key(self):
+        """What a captured step bakes in of this likelihood: both travel as kernel arguments."""
+        return (self.num_classes, self.epsilon)
+
+    def _check(self, Fmu, Fvar):
+        if Fmu.dim() != 2 or Fmu.shape[1] != self.num_classes or Fvar.shape != Fmu.shape:
+            raise ValueError(f"MultiClass: Fmu, Fvar must be [N, {self.num_classes}], got {tuple(Fmu.shape)} and {tuple(Fvar.shape)}")
+
+    def log_prob(self, F, Y):
+        """log(1 - epsilon) where argmax_c F == y, log(epsilon / (C - 1)) elsewhere; F [N, C], Y [N, 1] -> [N]."""
+        hit = torch.argmax(F, dim=-1).to(F.dtype) == Y.to(F.dtype).reshape(-1)
+        both = torch.tensor([math.log(self.invlink._eps_k1), math.log(1.0 - self.epsilon)], dtype=F.dtype, device=F.device)
+        return torch.where(hit, both[1], both[0])
+
+    def _prob_every_class(self, Fmu, Fvar):
+        """[rows, C]: entry k the probability that latent k is the largest (``prob_is_largest`` with the label k)."""
+        C = self.num_classes
+        x, w = np.polynomial.hermite.hermgauss(self.num_gauss_hermite_points)
+        x = torch.as_tensor(x, dtype=Fmu.dtype, device=Fmu.device)
+        w = torch.as_tensor(w / math.sqrt(math.pi), dtype=Fmu.dtype, device=Fmu.device)
+        X = Fmu[:, :, None] + x * torch.sqrt(torch.clamp(2.0 * Fvar, min=1e-10))[:, :, None]  # [rows, k, i]
+        d = (X[:, :, None, :] - Fmu[:, None, :, None]) / torch.sqrt(torch.clamp(Fvar, min=1e-10))[:, None, :, None]  # [rows, k, c, i]
+        cdf = 0.5 * (1.0 + torch.erf(d / math.sqrt(2.0))) * (1.0 - 2e-4) + 1e-4
+        own = torch.eye(C, dtype=torch.bool, device=Fmu.device)[None, :, :, None]
+        return torch.sum(torch.prod(torch.where(own, torch.ones_like(cdf), cdf), dim=2) * w, dim=-1)
+
+    def _density(self, Fmu, Fvar):
+        """p (1 - epsilon) + (1 - p) epsilon / (C - 1) for every class; [N, C], row chunk by row chunk."""
+        self._check(Fmu, Fvar)
+        out = []
+        rows = max(1, self._CHUNK // (self.num_gauss_hermite_points * self.num_classes ** 2))
+        for lo in range(0, max(Fmu.shape[0], 1), rows):
+            p = self._prob_every_class(Fmu[lo:lo + rows], Fvar[lo:lo + rows])
+            out.append(p * (1.0 - self.epsilon) + (1.0 - p) * self.invlink._eps_k1)
+        return torch.cat(out)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        """(ps, ps - ps^2) with ps [N, C] the predictive density of every class."""
+        ps = self._density(Fmu, Fvar)
+        return ps, ps - torch.square(ps)
+
+    def predict_log_density(self, Fmu, Fvar, Y):
+        """log of the predictive density of the labelled class; [N].  No label is used as an index."""
+        if Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != Fmu.shape[0]:
+            raise ValueError(f"MultiClass: Y must be [N, 1] = [{Fmu.shape[0]}, 1], got {tuple(Y.shape)}")
+        ps = self._density(Fmu, Fvar)
+        classes = torch.arange(self.num_classes, dtype=Fmu.dtype, device=Fmu.device)
+        onehot = (Y.to(Fmu.dtype) == classes[None, :]).to(Fmu.dtype)
+        return torch.log(torch.sum(onehot * ps, dim=-1))

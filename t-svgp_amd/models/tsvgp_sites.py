@@ -89,7 +89,7 @@ class t_SVGP_sites(base_SVGP):
         self._init_variational_parameters(self.num_data, lambda_1, lambda_2)
         if getattr(likelihood, "latent_dim", 1) != 1:
             raise NotImplementedError("t_SVGP_sites is defined for one latent GP: a likelihood over several latents "
-                                      f"(latent_dim = {likelihood.latent_dim}) needs t_SVGP")
+                                      f"({type(likelihood).__name__}, latent_dim = {likelihood.latent_dim}) needs t_SVGP")
         if self.data[1].dim() != 2 or self.data[1].shape[0] != self.num_data or self.data[1].shape[1] != 1:
             raise ValueError(f"Y must be [N, 1] = [{self.num_data}, 1], got {tuple(self.data[1].shape)}")
         self.whiten = False  # tsvgp_sites.py:59

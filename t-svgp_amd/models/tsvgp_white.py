@@ -85,7 +85,7 @@ class t_SVGP_white(base_SVGP):
                                       "(util.py:87, :425): only num_latent_gps = 1 is defined")
         if getattr(likelihood, "latent_dim", 1) != 1:
             raise NotImplementedError("t_SVGP_white is defined for one latent GP: a likelihood over several latents "
-                                      f"(latent_dim = {likelihood.latent_dim}) needs t_SVGP")
+                                      f"({type(likelihood).__name__}, latent_dim = {likelihood.latent_dim}) needs t_SVGP")
         self.name = "t_svgp_white"
 
     def _init_variational_parameters(self, num_inducing, lambda_1, lambda_2):
