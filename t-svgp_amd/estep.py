@@ -17,10 +17,11 @@ Kernel sequence of ``run(..., sites=True)`` by projection route (models/tsvgp.py
 ``mean_only`` replaces the moments product by one HBM-bound sweep (Gaussian likelihood, TSVGP_LIK_MEANONLY).
 A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``LIK_SOFTMAX`` / ``LIK_MULTICLASS``: C latents; Y [N x 1]) cannot run in
 the moments kernels' per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then its map
-(``tsvgp_lik_map_hetero`` / ``tsvgp_lik_map_softmax`` / ``tsvgp_lik_map_robustmax``) on them, then the site sums of the route -- ``run`` with P = latent_dim on
-one kernel, ``_run_batched`` on separate kernels, and a two-sweep form on the one-pass-per-latent path
-(``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments kernels (``LIK_STUDENT_T``, ``LIK_POISSON``;
-Y [N x P], one column per latent) take the same passes with ``tsvgp_lik_map_scalar`` as their map, one launch per column.
+on them, then the site sums of the route -- ``run`` with P = latent_dim on one kernel, ``_run_batched`` on separate kernels, and a
+two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments
+kernels (``LIK_STUDENT_T``, ``LIK_POISSON``; Y [N x P], one column per latent) take the same passes.  Every map from
+(mean, var, Y) to (g0, g1, ve, nonpos) that runs as a launch of its own, the Gaussian / Bernoulli one of the stored-tile and
+two-product passes included, goes through ``EStepEngine.lik_map``.
 """
 from __future__ import annotations
 
@@ -54,6 +55,17 @@ class EStepStats:
     g1: Optional[torch.Tensor] = None  # [N, P]
     tile: Optional[torch.Tensor] = None  # [Np, Mp] the stored triangular product t_n = Tm k_n (run(keep_tile=True))
     dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d (likelihood parameter) over the rows (LIK_STUDENT_T: scale)
+
+
+@dataclass
+class LikMapResult:
+    """What ``EStepEngine.lik_map`` wrote: cached buffers of the engine, or the caller's own where it handed them in."""
+
+    g0: torch.Tensor  # [Np, P] d ve / d mean (rows >= N zero)
+    g1: torch.Tensor  # [Np, P] d ve / d var (rows >= N zero)
+    ve_partial: torch.Tensor  # fp64 sums of ve per 128 rows: [Np / 128], or [P, Np / 128] from the per-column scalar map
+    nonpos_partial: torch.Tensor  # int32 counts of rows with var <= 0, the same shape
+    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d scale over the rows (LIK_STUDENT_T only)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -113,7 +125,6 @@ class EStepEngine:
         self._side = None  # side stream of start_fill
         self.last_batched = False  # the last pass over separate kernels ran as batched launches
         self.last_trmm_batch = 1  # latents per whitening launch of that pass
-        self.last_dparam = None  # sum of d ve / d scale of the last ``_scalar_map`` (LIK_STUDENT_T), a device scalar
         self.profile = None  # set to a dict to record (start, stop) HIP events per kernel launch on the launch stream
         self.profile_only = None  # a set of kernel names: bracket only these launches
         # A/B switch (tools/dev_diag2.py): round 4's diagonal-block kernel instead of round 5's (TSVGP_POTRF_DIAG_V1)
@@ -554,71 +565,69 @@ class EStepEngine:
                                                                       mode, self._stream()))
         return C
 
-    def _coupled_map(self, mean, var, Y, lik_id, N, Np, lik_param=None):
-        """g0, g1 [Np, P] (rows >= N zero), ve_partial, nonpos_partial of the coupled likelihood map on mean, var [N, P] and
-        Y [N, 1] in the compute dtype: ``tsvgp_lik_map_hetero_*`` (P = 2) or ``tsvgp_lik_map_softmax_*`` (P = C; ``lik_param`` is
-        the Softmax object: its sample count, row offset and device generator state, whose draw this call advances in-stream) or
-        ``tsvgp_lik_map_robustmax_*`` (P = C; ``lik_param`` is the MultiClass object: its epsilon; deterministic, nothing advances).
-        The outputs are cached buffers of their own: the site sums read them where they are, and a one-latent pass of the same
-        call (``site_grads``) does not overwrite them."""
-        T = self.dtype
-        nblk = Np // B.TILE
+    def lik_map(self, mean, var, Y, lik_id, lik_param, N, Np, *, g0=None, g1=None, ve_partial=None,
+                nonpos_partial=None) -> LikMapResult:
+        """The likelihood map as a launch of its own, for every likelihood id: (mean, var) [N, P] and Y ([N, 1] under a coupled
+        likelihood, [N, P] otherwise), contiguous and of one dtype (fp64 or fp32: it picks the kernel), -> g0, g1 [Np, P] (rows
+        >= N zero) and the per-128-row partials of ve and of the rows with var <= 0.  ``lik_id`` may carry LIK_NOCROP.
+          LIK_GAUSSIAN, LIK_BERNOULLI   ``tsvgp_lik_map_*``            ``lik_param``: the likelihood's scalar
+          LIK_HETERO                    ``tsvgp_lik_map_hetero_*``     P = 2
+          LIK_SOFTMAX                   ``tsvgp_lik_map_softmax_*``    P = C; ``lik_param`` is the Softmax object: its sample count, row
+                                        offset and device generator state, whose draw this call advances in-stream
+          LIK_MULTICLASS                ``tsvgp_lik_map_robustmax_*``  P = C; ``lik_param`` is the MultiClass object: its epsilon
+          LIK_STUDENT_T, LIK_POISSON    ``tsvgp_lik_map_scalar_*``     ``lik_param`` = (param0, param1); one launch per column, each with
+                                        its own run of the partials [P, Np / 128]; StudentT: ``dparam`` = sum d ve / d scale
+        Outputs the caller does not hand in are cached buffers of their own ("coupled_g0/g1", "ve_partial" / "nonpos_partial",
+        "scalar_*"): the site sums read them where they are, and a one-latent pass of the same call (``site_grads``) does not
+        overwrite them."""
+        T = mean.dtype
+        lik = lik_id & 0xFF
         P = mean.shape[1]
-        g0, g1 = self._get("coupled_g0", (Np, P), T), self._get("coupled_g1", (Np, P), T)
-        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
-            return self._scalar_map(mean, var, Y, lik_id, N, Np, lik_param, g0, g1)
-        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
-        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
-        if (lik_id & 0xFF) == B.LIK_SOFTMAX:
-            lik = lik_param
-            state = lik.rng_state(self.device)
-            with torch.cuda.device(self.device):
-                self._launch("tsvgp_lik_map_softmax", lambda: self._fn("tsvgp_lik_map_softmax")(
-                    mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), P, int(lik.num_monte_carlo_points), state.data_ptr(),
-                    int(lik.row_offset), None, g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np,
-                    self._stream()))
-                lik.advance()
-            return g0, g1, ve_partial, nonpos_partial
-        if (lik_id & 0xFF) == B.LIK_MULTICLASS:  # deterministic: one launch, nothing to advance
-            lik = lik_param
-            with torch.cuda.device(self.device):
-                self._launch("tsvgp_lik_map_robustmax", lambda: self._fn("tsvgp_lik_map_robustmax")(
-                    mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), P, float(lik.epsilon), g0.data_ptr(), g1.data_ptr(),
-                    ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, self._stream()))
-            return g0, g1, ve_partial, nonpos_partial
-        with torch.cuda.device(self.device):
-            self._launch("tsvgp_lik_map_hetero", lambda: self._fn("tsvgp_lik_map_hetero")(
-                mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id), g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(),
-                nonpos_partial.data_ptr(), N, Np, self._stream()))
-        return g0, g1, ve_partial, nonpos_partial
-
-    def _scalar_map(self, mean, var, Y, lik_id, N, Np, lik_param, g0, g1):
-        """``tsvgp_lik_map_scalar_*`` (LIK_STUDENT_T, LIK_POISSON) on mean, var, Y [N, P] in the compute dtype: one launch per
-        column, each with its own run of the partial buffers [P, Np / 128].  ``lik_param`` = (param0, param1) of the likelihood
-        object.  Returns (g0, g1, ve_partial, nonpos_partial) as ``_coupled_map`` and leaves the sum of d ve / d scale (StudentT;
-        None otherwise) in ``self.last_dparam`` for the caller to put into its statistics."""
         nblk = Np // B.TILE
-        P = mean.shape[1]
-        if tuple(Y.shape) != tuple(mean.shape) or tuple(var.shape) != tuple(mean.shape):
-            raise ValueError(f"mean, var and Y must share one shape [N, P], got {tuple(mean.shape)}, {tuple(var.shape)}, {tuple(Y.shape)}")
-        if not (mean.is_contiguous() and var.is_contiguous() and Y.is_contiguous()):
-            raise ValueError("the scalar likelihood map reads contiguous [N, P] arrays")
-        p0, p1 = (float(x) for x in lik_param)
-        student = (lik_id & 0xFF) == B.LIK_STUDENT_T
-        ve_partial = self._get("scalar_ve_partial", (P, nblk), torch.float64)
-        nonpos_partial = self._get("scalar_nonpos_partial", (P, nblk), torch.int32)
-        dpar = self._get("scalar_dparam_partial", (P, nblk), torch.float64) if student else None
-        fn = self._fn("tsvgp_lik_map_scalar")
-        esz = mean.element_size()
+        scalar = lik in B.SCALAR_MAP_LIKS
+        g0 = self._get("coupled_g0", (Np, P), T) if g0 is None else g0
+        g1 = self._get("coupled_g1", (Np, P), T) if g1 is None else g1
+        key, shape = ("scalar_", (P, nblk)) if scalar else ("", (nblk,))
+        ve_partial = self._get(key + "ve_partial", shape, torch.float64) if ve_partial is None else ve_partial
+        nonpos_partial = self._get(key + "nonpos_partial", shape, torch.int32) if nonpos_partial is None else nonpos_partial
+        res = LikMapResult(g0, g1, ve_partial, nonpos_partial)
+        ins = (mean.data_ptr(), var.data_ptr(), Y.data_ptr())
+        outs = (g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr())
         with torch.cuda.device(self.device):
-            for p in range(P):
-                off = p * esz
-                self._launch("tsvgp_lik_map_scalar", lambda: fn(
-                    mean.data_ptr() + off, var.data_ptr() + off, Y.data_ptr() + off, P, int(lik_id), p0, p1, g0.data_ptr() + off,
-                    g1.data_ptr() + off, P, ve_partial[p].data_ptr(), dpar[p].data_ptr() if student else None,
-                    nonpos_partial[p].data_ptr(), N, Np, self._stream()))
-        self.last_dparam = dpar.sum() if student else None
-        return g0, g1, ve_partial, nonpos_partial
+            if lik in (B.LIK_GAUSSIAN, B.LIK_BERNOULLI):
+                self._launch("tsvgp_lik_map", lambda: self._fn("tsvgp_lik_map", T)(
+                    *ins, int(lik_id), float(lik_param), *outs, N, Np, P, self._stream()))
+            elif lik == B.LIK_HETERO:
+                self._launch("tsvgp_lik_map_hetero", lambda: self._fn("tsvgp_lik_map_hetero", T)(
+                    *ins, int(lik_id), *outs, N, Np, self._stream()))
+            elif lik == B.LIK_SOFTMAX:
+                state = lik_param.rng_state(self.device)
+                self._launch("tsvgp_lik_map_softmax", lambda: self._fn("tsvgp_lik_map_softmax", T)(
+                    *ins, int(lik_id), P, int(lik_param.num_monte_carlo_points), state.data_ptr(), int(lik_param.row_offset), None,
+                    *outs, N, Np, self._stream()))
+                lik_param.advance()
+            elif lik == B.LIK_MULTICLASS:  # deterministic: one launch, nothing to advance
+                self._launch("tsvgp_lik_map_robustmax", lambda: self._fn("tsvgp_lik_map_robustmax", T)(
+                    *ins, int(lik_id), P, float(lik_param.epsilon), *outs, N, Np, self._stream()))
+            elif scalar:
+                if tuple(Y.shape) != tuple(mean.shape) or tuple(var.shape) != tuple(mean.shape):
+                    raise ValueError(f"mean, var and Y must share one shape [N, P], got {tuple(mean.shape)}, {tuple(var.shape)}, "
+                                     f"{tuple(Y.shape)}")
+                if not (mean.is_contiguous() and var.is_contiguous() and Y.is_contiguous()):
+                    raise ValueError("the scalar likelihood map reads contiguous [N, P] arrays")
+                p0, p1 = (float(x) for x in lik_param)
+                dpar = self._get("scalar_dparam_partial", (P, nblk), torch.float64) if lik == B.LIK_STUDENT_T else None
+                fn = self._fn("tsvgp_lik_map_scalar", T)
+                for p in range(P):
+                    off = p * mean.element_size()
+                    self._launch("tsvgp_lik_map_scalar", lambda: fn(
+                        ins[0] + off, ins[1] + off, ins[2] + off, P, int(lik_id), p0, p1, outs[0] + off, outs[1] + off, P,
+                        ve_partial[p].data_ptr(), _ptr(None if dpar is None else dpar[p]), nonpos_partial[p].data_ptr(), N, Np,
+                        self._stream()))
+                res.dparam = None if dpar is None else dpar.sum()
+            else:
+                raise ValueError(f"lik_map: no likelihood map for lik_id {lik_id}")
+        return res
 
     @staticmethod
     def _fused_param(lik_id, lik_param) -> float:
@@ -630,24 +639,15 @@ class EStepEngine:
     def _check_y(Y, N, P, lik_id, lik_param=None):
         """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX, LIK_MULTICLASS: C) maps its latents onto ONE target column:
         Y [N, 1], P = latent_dim."""
-        if (lik_id & 0xFF) == B.LIK_HETERO:
-            if P != 2 or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
-                raise ValueError(f"the heteroskedastic likelihood needs 2 latent GPs and Y [N, 1] = [{N}, 1], got P = {P} and "
-                                 f"Y {None if Y is None else tuple(Y.shape)}")
-            return
-        if (lik_id & 0xFF) == B.LIK_SOFTMAX:
-            C = getattr(lik_param, "latent_dim", None)
+        lik = lik_id & 0xFF
+        if lik in B.COUPLED_LIKS:
+            name = {B.LIK_HETERO: "heteroskedastic", B.LIK_SOFTMAX: "Softmax", B.LIK_MULTICLASS: "MultiClass"}[lik]
+            C = 2 if lik == B.LIK_HETERO else getattr(lik_param, "latent_dim", None)  # (hetero passes lik_param = 0.0)
             if P != C or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
-                raise ValueError(f"the Softmax likelihood needs {C} latent GPs (its latent_dim) and Y [N, 1] = [{N}, 1], got "
+                own = "" if lik == B.LIK_HETERO else " (its latent_dim)"
+                raise ValueError(f"the {name} likelihood needs {C} latent GPs{own} and Y [N, 1] = [{N}, 1], got "
                                  f"P = {P} and Y {None if Y is None else tuple(Y.shape)}")
-            return
-        if (lik_id & 0xFF) == B.LIK_MULTICLASS:
-            C = getattr(lik_param, "latent_dim", None)
-            if P != C or Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != 1:
-                raise ValueError(f"the MultiClass likelihood needs {C} latent GPs (its latent_dim) and Y [N, 1] = [{N}, 1], got "
-                                 f"P = {P} and Y {None if Y is None else tuple(Y.shape)}")
-            return
-        if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:
+        elif Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != P:
             raise ValueError(f"Y must be [N, P] = [{N}, {P}], got {tuple(Y.shape)}")
 
     def kernel_grad(self, X, Z, kernel, U, g0, g1, beta):
@@ -796,7 +796,7 @@ class EStepEngine:
         N, M, P = X.shape[0], Z.shape[0], moment_Tm.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         need_g = lik_id != B.LIK_NONE
-        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
+        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS  # the map runs behind the moments: coupled latents or a scalar map
         if need_g:
             Y = Y.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -836,17 +836,19 @@ class EStepEngine:
         ve_partial = self._get("ve_partial", (nblk,), torch.float64)
         nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
         kdiag = (ctypes.c_double * P)(*[k.variance.item() for k in kernel.kernels])
-        if coupled:
+        lm = None
+        if mapped:
             if mean_only:
                 raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
-            # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
+            # the moments of every latent with no likelihood, then the map on them (mean / var stay on this stream)
             mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
                     KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), None, kdiag, B.LIK_NONE, 0.0, mean.data_ptr(),
                     var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
                     self._stream()))
-            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np, lik_param)
+            lm = self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
+            g0, g1, ve_partial, nonpos_partial = lm.g0, lm.g1, lm.ve_partial, lm.nonpos_partial  # what the common tail reads
         else:
             g0 = self._get("g0", (Np, P), T) if need_g else None
             g1 = self._get("g1", (Np, P), T) if need_g else None
@@ -858,12 +860,11 @@ class EStepEngine:
                     KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, kdiag, lik_flags,
                     self._fused_param(lik_id, lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
                     nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
-        stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
-        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
-            stats.dparam = self.last_dparam
-        if want_moments:  # (the coupled path's mean / var are cached buffers: copies)
-            stats.mean = mean.to(torch.float64, copy=coupled)
-            stats.var = None if var is None else var.to(torch.float64, copy=coupled)
+        stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64),
+                           dparam=None if lm is None else lm.dparam)
+        if want_moments:  # (the mapped path's mean / var are cached buffers: copies)
+            stats.mean = mean.to(torch.float64, copy=mapped)
+            stats.var = None if var is None else var.to(torch.float64, copy=mapped)
         if want_grads and need_g:
             stats.g0, stats.g1 = g0[:N].to(torch.float64), g1[:N].to(torch.float64)
         if sites:
@@ -892,8 +893,8 @@ class EStepEngine:
         if len(kernel.kernels) != P:
             raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
         lik_id = kw.get("lik_id", B.LIK_NONE)
-        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
-        if coupled or Y is not None:
+        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS  # the map runs behind the moments: coupled latents or a scalar map
+        if mapped or Y is not None:
             self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"))
         if X.shape[0] > 0:
             if prefill is not None and "KfuP" in prefill:  # the batched fill is already under way (start_fill)
@@ -909,7 +910,7 @@ class EStepEngine:
                                          want_moments=kw.get("want_moments", False), want_grads=want_grads,
                                          mean_only=kw.get("mean_only", False), prefill=prefill)
         self.last_batched = False
-        if coupled and X.shape[0] > 0:  # (an empty shard contributes zeros through the loop below)
+        if mapped and X.shape[0] > 0:  # (an empty shard contributes zeros through the loop below)
             return self._run_separate_coupled(X, Y, Z, kernel, moment_Tm=moment_Tm, gamma=gamma, whiten_T=whiten_T,
                                               project_T=project_T, want_grads=want_grads, **kw)
         parts = []
@@ -937,9 +938,9 @@ class EStepEngine:
 
     def _run_separate_coupled(self, X, Y, Z, kernel, *, moment_Tm, gamma, whiten_T, project_T, want_grads, lik_id, sites=False,
                               want_moments=False, mean_only=False, **kw) -> EStepStats:
-        """The one-pass-per-latent path under a likelihood that couples the latents (``LIK_HETERO``): the map needs the moments
-        of BOTH latents before any site sum, and this path has one K(X, Z) buffer.  Sweep 1: fill (and whitening) + moments with
-        no likelihood, per latent; the coupled map over [N, 2]; sweep 2 (``sites`` only): fill (and whitening / projection)
+        """The one-pass-per-latent path under a likelihood whose map runs behind the moments (``B.MAPPED_LIKS``): a coupled map
+        needs the moments of ALL latents before any site sum, and this path has one K(X, Z) buffer.  Sweep 1: fill (and whitening)
+        + moments with no likelihood, per latent; the map over [N, P] (``lik_map``); sweep 2 (``sites`` only): fill (and whitening / projection)
         again + the site sums of each latent with its column of the map (``run(site_grads=...)``).  The refill costs one
         K(X, Z) fill (plus the whitening product where the route has one) per latent -- the alternative, keeping both operands,
         is the batched path's [P, Np, Mp] buffer, and this path runs exactly when that does not fit or is not wanted."""
@@ -958,10 +959,9 @@ class EStepEngine:
             mean[:, p] = st.mean[:, 0]
             var[:, p] = st.var[:, 0]
         Yc = Y.to(device=dev, dtype=T).contiguous()
-        g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Yc, lik_id, N, Np, lik_param)
-        out = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
-        if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
-            out.dparam = self.last_dparam
+        lm = self.lik_map(mean, var, Yc, lik_id, lik_param, N, Np)
+        g0, g1 = lm.g0, lm.g1
+        out = EStepStats(n_rows=N, ve_sum=lm.ve_partial.sum(), nonpos=lm.nonpos_partial.sum().to(torch.float64), dparam=lm.dparam)
         if want_moments:
             out.mean, out.var = mean.to(torch.float64, copy=True), var.to(torch.float64, copy=True)
         if want_grads:
@@ -1062,7 +1062,7 @@ class EStepEngine:
 
         keep_tile (one latent, no whitening): the triangular product of the moments, t_n = Tm k_n, is STORED (``tsvgp_trmm``
         into the buffer "Tt", returned as ``stats.tile``) and the moments are assembled from it -- mean by a matrix-vector
-        product, var = kdiag - |t_n|^2 by a row norm, the gradients by ``tsvgp_lik_map`` -- instead of being squared and summed
+        product, var = kdiag - |t_n|^2 by a row norm, the gradients by ``lik_map`` -- instead of being squared and summed
         inside the fused kernel.  For the M-step (t_SVGP.elbo_and_grads), which needs Q k_n = Tm^T t_n for every row: a second
         triangular product of the stored tile instead of a dense N M^2 GEMM with Q = Tm^T Tm.
 
@@ -1085,10 +1085,9 @@ class EStepEngine:
         stream; this call waits for it instead of filling.
         mean_only (likelihood NONE or GAUSSIAN): skip the variance product of the moments (TSVGP_LIK_MEANONLY) -- the
         Gaussian g0, g1 do not depend on it; ``var`` is then None and ``ve_sum`` NaN.
-        lik_id LIK_HETERO (P = 2, Y [N, 1]) or LIK_SOFTMAX (P = C, Y [N, 1], ``lik_param`` = the Softmax object): moments of all
-        latents with no likelihood, then the coupled map (``tsvgp_lik_map_hetero_*`` / ``tsvgp_lik_map_softmax_*``), then the
-        site sums.  lik_id LIK_STUDENT_T / LIK_POISSON (Y [N, P], ``lik_param`` = the likelihood's (param0, param1)): the same
-        sequence with ``tsvgp_lik_map_scalar_*``, one launch per column; ``stats.dparam`` = sum d ve / d scale (StudentT).
+        lik_id in ``B.MAPPED_LIKS`` (coupled: P = latent_dim, Y [N, 1]; LIK_STUDENT_T / LIK_POISSON: Y [N, P]; ``lik_param`` as
+        ``lik_map`` takes it): moments of all latents with no likelihood, then ``lik_map``, then the site sums;
+        ``stats.dparam`` = sum d ve / d scale (StudentT).
         site_grads (lik_id NONE, one kernel): (g0, g1) [Np, P] in the compute dtype, rows >= N zero -- the site sums (and with
         ``keep_tile`` the stored product) of this pass with gradients a coupled map made elsewhere; the moments product then
         runs only for ``want_moments`` / ``keep_tile``, and ``ve_sum`` / ``nonpos`` are zero (the map's call counts them).
@@ -1125,7 +1124,7 @@ class EStepEngine:
             return st
         if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != D:
             raise ValueError(f"X must be [N, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
-        coupled = (lik_id & 0xFF) in B.MAPPED_LIKS  # (the map runs behind the moments: coupled latents or a scalar map)
+        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS  # the map runs behind the moments: coupled latents or a scalar map
         if lik_id != B.LIK_NONE:
             self._check_y(Y, N, P, lik_id, lik_param)
             Y = Y.to(device=dev, dtype=T).contiguous()
@@ -1174,35 +1173,34 @@ class EStepEngine:
         mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
         var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
         lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
-        tile = None
+        tile, lm = None, None
         if site_grads is not None:
             g0.copy_(site_grads[0])
             g1.copy_(site_grads[1])
         if keep_tile:
             if P != 1 or mean_only or whiten_T is not None or not need_g:
                 raise ValueError("keep_tile: one latent, a likelihood, no whitening")
-            if coupled:
+            if mapped:
                 raise ValueError("keep_tile: a likelihood whose map runs behind the moments comes in through site_grads")
             tile = self._get("Tt", (Np, Mp), T)
             self.trmm(A, Tm[0], tile, moment_mode)
             mean = torch.mv(A[:N], gam[:, 0]).reshape(N, 1)  # gam: [Mp, 1], rows >= M zero
             var = (variance - torch.linalg.vector_norm(tile[:N], dim=1).square()).reshape(N, 1)
             if site_grads is None:
-                with torch.cuda.device(dev):
-                    self._launch("tsvgp_lik_map", lambda: self._fn("tsvgp_lik_map")(
-                        mean.data_ptr(), var.data_ptr(), Y.data_ptr(), lik_id, float(lik_param), g0.data_ptr(), g1.data_ptr(),
-                        ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, 1, self._stream()))
-        elif coupled:
+                self.lik_map(mean, var, Y, lik_id, lik_param, N, Np, g0=g0, g1=g1, ve_partial=ve_partial,
+                             nonpos_partial=nonpos_partial)
+        elif mapped:
             if mean_only:
                 raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
-            # the moments of both latents with no likelihood, then the map that couples them (mean / var stay on this stream)
+            # the moments of every latent with no likelihood, then the map on them (mean / var stay on this stream)
             mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
             with torch.cuda.device(dev):
                 self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
                     A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, variance, B.LIK_NONE, 0.0, mean.data_ptr(),
                     var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
                     self._stream()))
-            g0, g1, ve_partial, nonpos_partial = self._coupled_map(mean, var, Y, lik_id, N, Np, lik_param)
+            lm = self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
+            g0, g1, ve_partial, nonpos_partial = lm.g0, lm.g1, lm.ve_partial, lm.nonpos_partial  # what the common tail reads
             if want_moments:
                 mean, var = mean.clone(), var.clone()
         elif site_grads is not None and not want_moments:
@@ -1218,9 +1216,8 @@ class EStepEngine:
             zero = torch.zeros((), dtype=torch.float64, device=dev)
             stats = EStepStats(n_rows=N, ve_sum=zero, nonpos=zero.clone())
         else:
-            stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64))
-            if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
-                stats.dparam = self.last_dparam
+            stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64),
+                               dparam=None if lm is None else lm.dparam)
         stats.tile = tile
         if want_moments:
             stats.mean, stats.var = mean.to(torch.float64), (None if var is None else var.to(torch.float64))
@@ -1265,7 +1262,7 @@ class EStepEngine:
         T2 = U_R^-1 U6 (``moment_Tm``, upper triangular), mean = b^T gamma.  Used when Lambda_2 + 1e-9 I is not positive definite
         (the single triangular product of ``run`` needs its factor; the reference only needs K + Lambda_2 + 1e-9 I).  Sequence:
         fill -> trmm (B) -> moments with NO likelihood (mean, kff - |T2 b|^2) -> |b|^2 by a row reduction of B -> the
-        likelihood map on the assembled moments (``tsvgp_lik_map_*``) -> site sums over B.  One shared kernel, one latent.
+        likelihood map on the assembled moments (``lik_map``) -> site sums over B.  One shared kernel, one latent.
         ``prefill``: as ``run``."""
         T, dev = self.dtype, self.device
         st = self.run(X, None, Z, kernel, moment_Tm=moment_Tm, moment_mode=B.TRI_UPPER, gamma=gamma, lik_id=B.LIK_NONE,
@@ -1281,24 +1278,12 @@ class EStepEngine:
             stats.mean, stats.var = st.mean, var
         if lik_id != B.LIK_NONE:
             Yc = Y.to(device=dev, dtype=T).contiguous()
-            mean_t, var_t = st.mean.to(T).contiguous(), var.to(T).contiguous()
-            nblk = Np // B.TILE
-            ve_partial = self._get("ve_partial", (nblk,), torch.float64)
-            nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
-            g0, g1 = self._get("g0", (Np, 1), T), self._get("g1", (Np, 1), T)
-            if (lik_id & 0xFF) in B.SCALAR_MAP_LIKS:
-                self._check_y(Yc, N, 1, lik_id, lik_param)
-                g0, g1, ve_partial, nonpos_partial = self._scalar_map(mean_t, var_t, Yc, lik_id, N, Np, lik_param, g0, g1)
-                stats.dparam = self.last_dparam
-            else:
-                with torch.cuda.device(dev):
-                    B.check(self._fn("tsvgp_lik_map")(mean_t.data_ptr(), var_t.data_ptr(), Yc.data_ptr(), lik_id, float(lik_param),
-                                                       g0.data_ptr(), g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(),
-                                                       N, Np, 1, self._stream()), "tsvgp_lik_map")
-            stats.ve_sum = ve_partial.sum()
-            stats.nonpos = nonpos_partial.sum().to(torch.float64)
+            self._check_y(Yc, N, 1, lik_id, lik_param)
+            lm = self.lik_map(st.mean.to(T).contiguous(), var.to(T).contiguous(), Yc, lik_id, lik_param, N, Np,
+                              g0=self._get("g0", (Np, 1), T), g1=self._get("g1", (Np, 1), T))
+            stats.ve_sum, stats.nonpos, stats.dparam = lm.ve_partial.sum(), lm.nonpos_partial.sum().to(torch.float64), lm.dparam
             if sites:
-                stats.acc2, stats.acc1 = self._site_sums(Bw, g0, g1, 1, M)
+                stats.acc2, stats.acc1 = self._site_sums(Bw, lm.g0, lm.g1, 1, M)
         return stats
 
     # ------------------------------------------------------------------ joint predictions
@@ -1563,19 +1548,16 @@ class EStepEngine:
         return S, Np, self.vgp_factor(S, Np), V
 
     def lik_grads(self, mean, var, Y, lik_id, lik_param):
-        """g0 = d ve / d mean, g1 = d ve / d var [N] at (mean, var, Y) [N, 1] fp64, never cropped (``tsvgp_lik_map_f64`` with
-        TSVGP_LIK_NOCROP): the gradients of the bound, not the site update's."""
+        """g0 = d ve / d mean, g1 = d ve / d var [N] at (mean, var, Y) [N, 1] fp64, never cropped (``lik_map`` in fp64 with
+        LIK_NOCROP): the gradients of the bound, not the site update's."""
         N = mean.shape[0]
         Np = B.round_up(N)
         nblk = Np // B.TILE
-        g0, g1 = self._get("vgp_g0", (Np, 1), torch.float64), self._get("vgp_g1", (Np, 1), torch.float64)
-        ve_partial = self._get("vgp_lik_ve", (nblk,), torch.float64)
-        nonpos_partial = self._get("vgp_lik_nonpos", (nblk,), torch.int32)
-        with torch.cuda.device(self.device):
-            self._launch("tsvgp_lik_map", lambda: self.lib.tsvgp_lik_map_f64(
-                mean.data_ptr(), var.data_ptr(), Y.data_ptr(), int(lik_id) | B.LIK_NOCROP, float(lik_param), g0.data_ptr(),
-                g1.data_ptr(), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, 1, self._stream()))
-        return g0[:N, 0], g1[:N, 0]
+        lm = self.lik_map(mean, var, Y, int(lik_id) | B.LIK_NOCROP, lik_param, N, Np,
+                          g0=self._get("vgp_g0", (Np, 1), torch.float64), g1=self._get("vgp_g1", (Np, 1), torch.float64),
+                          ve_partial=self._get("vgp_lik_ve", (nblk,), torch.float64),
+                          nonpos_partial=self._get("vgp_lik_nonpos", (nblk,), torch.int32))
+        return lm.g0[:N, 0], lm.g1[:N, 0]
 
     def vgp_kernel_grad(self, X, kernel, W, a, c):
         """sum_ij G[i, j] dK(X, X)[i, j] / d theta, G = W + 1/2 (a c^T + c a^T), for theta = variance and the lengthscales

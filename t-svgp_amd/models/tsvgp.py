@@ -242,10 +242,8 @@ class t_SVGP(base_SVGP):
                          num_latent_gps=num_latent_gps, num_data=num_data, compute_dtype=compute_dtype, device=device)
         self.num_inducing = self.inducing_variable.num_inducing
         self._init_variational_parameters(self.num_inducing, lambda_1, lambda_2_sqrt)
-        if self._coupled() and self.likelihood.lik_id == B.LIK_HETERO and self.num_latent_gps != 2:
-            raise ValueError(f"the heteroskedastic likelihood needs num_latent_gps = 2 (its latent_dim), got {self.num_latent_gps}")
         if self._coupled() and self.num_latent_gps != self.likelihood.latent_dim:
-            raise ValueError(f"the {type(self.likelihood).__name__} likelihood needs num_latent_gps = {self.likelihood.latent_dim} "
+            raise ValueError(f"the {self._lik_name()} likelihood needs num_latent_gps = {self.likelihood.latent_dim} "
                              f"(its latent_dim), got {self.num_latent_gps}")
         self.whiten = False
         self.force = force
@@ -316,16 +314,18 @@ class t_SVGP(base_SVGP):
         target column)."""
         return getattr(self.likelihood, "lik_id", None) in B.COUPLED_LIKS
 
+    def _lik_name(self) -> str:
+        return "heteroskedastic" if self.likelihood.lik_id == B.LIK_HETERO else type(self.likelihood).__name__
+
     def _mapped(self) -> bool:
-        """The likelihood's map runs behind the moments (``EStepEngine._coupled_map``): the coupled likelihoods and the scalar ones
+        """The likelihood's map runs behind the moments (``EStepEngine.lik_map``): the coupled likelihoods and the scalar ones
         without an arm in the moments kernels (StudentT, Poisson; Y [N, P] as for Gaussian)."""
         return getattr(self.likelihood, "lik_id", None) in B.MAPPED_LIKS
 
     def _check_targets(self, X, Y):
         """Y [N, 1] under the coupled likelihood (the engine checks Y [N, P] for the others)."""
         if self._coupled() and (Y.dim() != 2 or Y.shape[1] != 1 or Y.shape[0] != X.shape[0]):
-            name = "heteroskedastic" if self.likelihood.lik_id == B.LIK_HETERO else type(self.likelihood).__name__
-            raise ValueError(f"the {name} likelihood takes Y [N, 1] = [{X.shape[0]}, 1], got {tuple(Y.shape)}")
+            raise ValueError(f"the {self._lik_name()} likelihood takes Y [N, 1] = [{X.shape[0]}, 1], got {tuple(Y.shape)}")
 
     # -- M x M prelude -----------------------------------------------------------------------------------------
     def _kmv(self, K: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -781,8 +781,8 @@ class t_SVGP(base_SVGP):
         # The TRUE d ve / d var here: the crop of tsvgp.py:262-263 belongs to the site update, not to the ELBO (with the
         # 1e-3 jitter of the probit link log p is not log-concave in the far tails, so some g1 are positive)
         parts = []
-        coupled = self._mapped()
-        if coupled:
+        mapped = self._mapped()
+        if mapped:
             # A likelihood that couples the latents cannot ride on a per-kernel pass (and the scalar maps behind the moments do not
             # ride on the stored-tile form of one): one pass over all latents maps the
             # moments of all of them to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
@@ -800,7 +800,7 @@ class t_SVGP(base_SVGP):
             # triangular product of it -- 2 N M^2 flops for moments + U instead of the 3 N M^2 of the fused moments kernel plus a
             # dense GEMM with Q = D^T D (round 5; 16.8 + 28.1 ms -> 15.5 + ~5 + 16 ms at N = 1e6, M = 1024).
             tile_path = len(lat) == 1 and hasattr(eng, "trmm") and os.environ.get("TSVGP_MSTEP_TILE", "1") != "0"
-            if coupled:
+            if mapped:
                 st = eng.run(X, None, ops["Z"], kern, moment_Tm=Dm[sl], moment_mode=ops["moment_mode"], gamma=beta[:, sl],
                              sites=True, site_grads=(gc0[:, sl], gc1[:, sl]), **({"keep_tile": True} if tile_path else {}))
             else:
@@ -833,7 +833,7 @@ class t_SVGP(base_SVGP):
             st = EStepStats(n_rows=parts[0].n_rows, ve_sum=sum(s_.ve_sum for s_ in parts),
                             nonpos=sum(s_.nonpos for s_ in parts))
             st.acc2, st.acc1 = torch.cat([s_.acc2 for s_ in parts], dim=0), torch.cat([s_.acc1 for s_ in parts], dim=0)
-        if coupled:
+        if mapped:
             st.ve_sum, st.nonpos = stc.ve_sum, stc.nonpos
         student = self.likelihood.lik_id == B.LIK_STUDENT_T
         if student:  # sum_n d ve_n / d scale, summed over the ranks with the residual's slot (Gaussian only: free here)

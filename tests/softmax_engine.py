@@ -1,7 +1,7 @@
 """TEST DOUBLE (as tests/cpu_engine.py, which it extends): ``NumpyShardEngine`` plus the coupled Softmax map, so that the host
 logic around the Softmax likelihood -- constructor and target checks, the draw bookkeeping, row offsets over ranks, the site
 update -- runs on CPU.  The map here is the NumPy restatement (tests/softmax_ref.py) at the product likelihood's
-(seed, draw, row_offset); like ``EStepEngine._coupled_map`` it advances the likelihood's draw once per evaluation."""
+(seed, draw, row_offset); like ``EStepEngine.lik_map`` it advances the likelihood's draw once per evaluation."""
 import numpy as np
 import torch
 
