@@ -21,7 +21,9 @@ on them, then the site sums of the route -- ``run`` with P = latent_dim on one k
 two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments
 kernels (``LIK_STUDENT_T``, ``LIK_POISSON``; Y [N x P], one column per latent) take the same passes.  Every map from
 (mean, var, Y) to (g0, g1, ve, nonpos) that runs as a launch of its own, the Gaussian / Bernoulli one of the stored-tile and
-two-product passes included, goes through ``EStepEngine.lik_map``.
+two-product passes included, goes through ``EStepEngine.lik_map``.  The two other N-sized launches of a pass have one entry each
+as well, for the shared operand [Np, Mp] and the per-latent one [P, Np, Mp] alike: ``EStepEngine.moments`` (``_moments_then_map`` is
+the mapped pass's pair of it and ``lik_map``) and ``EStepEngine._site_sums``.
 """
 from __future__ import annotations
 
@@ -70,6 +72,15 @@ class LikMapResult:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def per_latent(t, p):
+    """Entry p of a per-latent operand given as None, a list, a [P, M, M] tensor or one shared [M, M] tensor."""
+    if t is None:
+        return None
+    if isinstance(t, (list, tuple)):
+        return t[p]
+    return t[p] if t.dim() == 3 else t
 
 
 def site_sum_chunk_rows(f64: bool, P: int) -> int:
@@ -635,6 +646,41 @@ class EStepEngine:
         ``lik_param``: models hand over their likelihood's whatever the pass, and a mapped likelihood's is no float."""
         return 0.0 if (lik_id & 0xFF) == B.LIK_NONE else float(lik_param)
 
+    def moments(self, A, Tm, gam, kdiag, N, moment_mode, *, lik_id=B.LIK_NONE, lik_param=0.0, mean_only=False, Y=None, mean=None,
+                var=None, g0=None, g1=None):
+        """The fused moments launch, the only one: A [Np, Mp], one operand and one prior variance ``kdiag`` for all P latents
+        (``tsvgp_moments_*``), or A [P, Np, Mp] with a sequence of P prior variances (``tsvgp_moments_batched_*``).  Tm [P, Mp, Mp]
+        and gam [Mp, P] are the padded operands; Y [N, P], mean, var [N, P] and g0, g1 [Np, P] are read / written where given
+        (None: that array is not touched).  ``lik_id`` (flag bits included) selects the epilogue's likelihood with its own
+        ``lik_param``; ``mean_only`` adds TSVGP_LIK_MEANONLY.  Returns the cached (ve_partial [Np / 128] fp64, nonpos_partial
+        int32) the launch wrote."""
+        Np, Mp = A.shape[-2:]
+        P = gam.shape[1]
+        ve_partial = self._get("ve_partial", (Np // B.TILE,), torch.float64)
+        nonpos_partial = self._get("nonpos_partial", (Np // B.TILE,), torch.int32)
+        if A.dim() == 3:
+            fn, operand, kdiag = self._fn("tsvgp_moments_batched"), (A.data_ptr(), Np * Mp), (ctypes.c_double * P)(*kdiag)
+        else:
+            fn, operand = self._fn("tsvgp_moments"), (A.data_ptr(),)
+        flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_moments", lambda: fn(
+                *operand, Tm.data_ptr(), gam.data_ptr(), _ptr(Y), kdiag, flags, self._fused_param(lik_id, lik_param), _ptr(mean),
+                _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
+                self._stream()))
+        return ve_partial, nonpos_partial
+
+    def _moments_then_map(self, A, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only=False):
+        """The pass of a likelihood whose map runs behind the moments (``B.MAPPED_LIKS``): the moments of every latent with no
+        likelihood into the cached "coupled_mean" / "coupled_var" [N, P] (they stay on this stream), then ``lik_map`` on them.
+        Returns (mean, var, LikMapResult)."""
+        if mean_only:
+            raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
+        P = gam.shape[1]
+        mean, var = self._get("coupled_mean", (N, P), self.dtype), self._get("coupled_var", (N, P), self.dtype)
+        self.moments(A, Tm, gam, kdiag, N, moment_mode, mean=mean, var=var)
+        return mean, var, self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
+
     @staticmethod
     def _check_y(Y, N, P, lik_id, lik_param=None):
         """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX, LIK_MULTICLASS: C) maps its latents onto ONE target column:
@@ -728,14 +774,7 @@ class EStepEngine:
     batch_separate = True  # False: always one pass per latent through a single K(X, Z) buffer (the round-1 path)
     batch_mem_fraction = 0.8  # of the device memory still free: what the [P, Np, Mp] operand of a batched pass may take
 
-    @staticmethod
-    def _per_latent(t, p):
-        """Entry p of a per-latent operand given as None, a list, a [P, M, M] tensor or one shared [M, M] tensor."""
-        if t is None:
-            return None
-        if isinstance(t, (list, tuple)):
-            return t[p]
-        return t[p] if t.dim() == 3 else t
+    _per_latent = staticmethod(per_latent)
 
     def _batch_plan(self, N, M, kernel, P, whiten_T, whiten_mode, project_T, moments_on_kfu, D=0):
         """Can the pass over P separately-parameterised latents run as batched launches (tsvgp_*_batched_*)?  Needs one
@@ -805,12 +844,9 @@ class EStepEngine:
         KfuP = self._get("KfuP", (P, Np, Mp), T)
         stride = Np * Mp
         if prefill is not None:
-            if prefill.get("KfuP") is not KfuP:
-                raise RuntimeError("prefill ticket does not belong to this pass")
-            torch.cuda.current_stream(dev).wait_event(prefill["event"])
+            self._take_prefill(prefill, "KfuP", KfuP)
         else:
-            if self._side is not None and not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(dev).wait_stream(self._side)
+            self._wait_stale_fill()
             self._fill_batched(X, Z, kernel, KfuP)
         # whitening in place, one launch per run of consecutive whitened latents: B_p = K_p U9_p^-T (upper form)
         runs, start = [], None
@@ -832,34 +868,18 @@ class EStepEngine:
                                                            self._stream()))
         Tm = self._pad_square(moment_Tm, Mp, "pad_Tm")
         gam = self._padded_gamma(gamma, Mp, P)
-        nblk = Np // B.TILE
-        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
-        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
-        kdiag = (ctypes.c_double * P)(*[k.variance.item() for k in kernel.kernels])
+        kdiag = [k.variance.item() for k in kernel.kernels]
         lm = None
         if mapped:
-            if mean_only:
-                raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
-            # the moments of every latent with no likelihood, then the map on them (mean / var stay on this stream)
-            mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
-            with torch.cuda.device(dev):
-                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
-                    KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), None, kdiag, B.LIK_NONE, 0.0, mean.data_ptr(),
-                    var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
-                    self._stream()))
-            lm = self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
+            mean, var, lm = self._moments_then_map(KfuP, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only)
             g0, g1, ve_partial, nonpos_partial = lm.g0, lm.g1, lm.ve_partial, lm.nonpos_partial  # what the common tail reads
         else:
             g0 = self._get("g0", (Np, P), T) if need_g else None
             g1 = self._get("g1", (Np, P), T) if need_g else None
             mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
             var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
-            lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
-            with torch.cuda.device(dev):
-                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments_batched")(
-                    KfuP.data_ptr(), stride, Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if need_g else None, kdiag, lik_flags,
-                    self._fused_param(lik_id, lik_param), _ptr(mean), _ptr(var), _ptr(g0), _ptr(g1), ve_partial.data_ptr(),
-                    nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
+            ve_partial, nonpos_partial = self.moments(KfuP, Tm, gam, kdiag, N, moment_mode, lik_id=lik_id, lik_param=lik_param,
+                                                      mean_only=mean_only, Y=Y if need_g else None, mean=mean, var=var, g0=g0, g1=g1)
         stats = EStepStats(n_rows=N, ve_sum=ve_partial.sum(), nonpos=nonpos_partial.sum().to(torch.float64),
                            dparam=None if lm is None else lm.dparam)
         if want_moments:  # (the mapped path's mean / var are cached buffers: copies)
@@ -868,18 +888,7 @@ class EStepEngine:
         if want_grads and need_g:
             stats.g0, stats.g1 = g0[:N].to(torch.float64), g1[:N].to(torch.float64)
         if sites:
-            nsplit = self.nsplit_override or self.choose_nsplit(Mp, P, Np)
-            nsplit = max(1, min(nsplit, Np // site_sum_chunk_rows(T == torch.float64, P)))
-            nbytes = int(self._fn("tsvgp_site_accum_work_bytes")(Mp, P, nsplit))
-            work = self._get("work", (nbytes,), torch.uint8)
-            acc2 = torch.empty((P, Mp, Mp), dtype=torch.float64, device=dev)
-            acc1 = torch.empty((P, Mp), dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                self._launch("tsvgp_site_accum", lambda: self._fn("tsvgp_site_accum_batched")(
-                    KfuP.data_ptr(), stride, g0.data_ptr(), g1.data_ptr(), acc2.data_ptr(), acc1.data_ptr(),
-                    work.data_ptr(), Np, Mp, P, nsplit, self._stream()))
-            stats.acc2 = acc2[:, :M, :M]
-            stats.acc1 = acc1[:, :M]
+            stats.acc2, stats.acc1 = self._site_sums(KfuP, g0, g1, P, M)
         self.last_batched = True
         return stats
 
@@ -915,14 +924,9 @@ class EStepEngine:
                                               project_T=project_T, want_grads=want_grads, **kw)
         parts = []
         for p, kp in enumerate(kernel.kernels):
-            if isinstance(whiten_T, (list, tuple)):  # per-latent routes: None = this latent works on K_fu directly
-                wt = whiten_T[p]
-            else:
-                wt = None if whiten_T is None else (whiten_T[p] if whiten_T.dim() == 3 else whiten_T)
-            pt = project_T[p] if isinstance(project_T, (list, tuple)) else (
-                None if project_T is None else (project_T[p] if project_T.dim() == 3 else project_T))
-            st = self.run(X, None if Y is None else Y[:, p:p + 1], Z, kp, moment_Tm=moment_Tm[p:p + 1],
-                          gamma=gamma[:, p:p + 1], whiten_T=wt, project_T=pt, want_grads=want_grads, **kw)
+            # (per-latent routes: None = this latent works on K_fu directly)
+            st = self.run(X, None if Y is None else Y[:, p:p + 1], Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1],
+                          whiten_T=per_latent(whiten_T, p), project_T=per_latent(project_T, p), want_grads=want_grads, **kw)
             if want_grads and st.g0 is not None:
                 st.g0, st.g1 = st.g0.clone(), st.g1.clone()  # views of a buffer the next latent overwrites
             parts.append(st)
@@ -996,33 +1000,14 @@ class EStepEngine:
         N, D = X.shape
         M = Z.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
-        if isinstance(kernel, SeparateIndependent):
+        separate = isinstance(kernel, SeparateIndependent)
+        if separate:
             P = len(kernel.kernels)
             if routes is None or any(r == "projected" for r in routes):
                 return None
             if self._batch_plan(N, M, kernel, P, None, B.TRI_UPPER, None, False, D=D) is None:
                 return None
-            main = torch.cuda.current_stream(dev)
-            if self._side is None:
-                self._side = torch.cuda.Stream(dev)
-            side = self._side
-            Xc = X.to(device=dev, dtype=T).contiguous()
-            Zc = Z.to(device=dev, dtype=T).contiguous()
-            self._b_tag = None
-            self._buf.pop("Kfu", None)
-            self._buf.pop("B", None)
-            KfuP = self._get("KfuP", (P, Np, Mp), T)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                self._fill_batched(Xc, Zc, kernel, KfuP)
-                done = torch.cuda.Event()
-                done.record(side)
-            if not capturing:
-                for t in (Xc, Zc, KfuP):
-                    t.record_stream(side)
-            # `keep`: see the single-kernel ticket below
-            return dict(event=done, KfuP=KfuP, keep=(Xc, Zc))
-        if (b_tag is not None and self._b_tag == (want, b_tag) and self._buf.get(want) is not None
+        elif (b_tag is not None and self._b_tag == (want, b_tag) and self._buf.get(want) is not None
                 and tuple(self._buf[want].shape) == (Np, Mp)):
             return None
         main = torch.cuda.current_stream(dev)
@@ -1031,17 +1016,27 @@ class EStepEngine:
         side = self._side
         Xc = X.to(device=dev, dtype=T).contiguous()
         Zc = Z.to(device=dev, dtype=T).contiguous()
-        inv_ls = kernel.inv_lengthscales(D, T, dev)
-        variance = kernel.variance.item()
         self._b_tag = None
-        Kfu = self._get("Kfu", (Np, Mp), T)
+        if separate:
+            self._buf.pop("Kfu", None)
+            self._buf.pop("B", None)
+            buf = self._get("KfuP", (P, Np, Mp), T)
+            keep, ticket = (Xc, Zc), dict(KfuP=buf)
+            fill = lambda: self._fill_batched(Xc, Zc, kernel, buf)
+        else:
+            inv_ls = kernel.inv_lengthscales(D, T, dev)
+            variance = kernel.variance.item()
+            buf = self._get("Kfu", (Np, Mp), T)
+            keep = (Xc, Zc, inv_ls)
+            ticket = dict(key=(X.data_ptr(), tuple(X.shape), Z.data_ptr(), tuple(Z.shape), id(kernel)), Kfu=buf)
+            fill = lambda: self.se_fill(Xc, Zc, inv_ls, variance, buf, kernel.kind)
         side.wait_stream(main)  # the buffer's last readers (the previous pass) and the conversions above
         with torch.cuda.stream(side):
-            self.se_fill(Xc, Zc, inv_ls, variance, Kfu, kernel.kind)
+            fill()
             done = torch.cuda.Event()
             done.record(side)
         if not capturing:
-            for t in (Xc, Zc, inv_ls, Kfu):  # blocks of the main stream's allocator pool that the side stream touches
+            for t in keep + (buf,):  # blocks of the main stream's allocator pool that the side stream touches
                 t.record_stream(side)
         # `keep`: the converted inputs must outlive the side stream's read of them.  Eagerly record_stream sees to that; under
         # capture nothing does -- a block freed DURING a capture goes straight back to the graph's pool, the next allocation on
@@ -1050,8 +1045,18 @@ class EStepEngine:
         # such a temporary; fp64 passes its tensors through, which is why three rounds of fp64 tests never saw it): the state
         # after four replayed steps was off by 1e-5 ... 0.4, differently on every run.  The ticket holds them until ``run`` has
         # made the consuming stream wait for the fill.
-        return dict(event=done, key=(X.data_ptr(), tuple(X.shape), Z.data_ptr(), tuple(Z.shape), id(kernel)), Kfu=Kfu,
-                    keep=(Xc, Zc, inv_ls))
+        return dict(event=done, keep=keep, **ticket)
+
+    def _wait_stale_fill(self):
+        """A fill started for a pass that never ran must not land on top of the one about to start (a capture begins synchronised)."""
+        if self._side is not None and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(self.device).wait_stream(self._side)
+
+    def _take_prefill(self, prefill, key, buf):
+        """Makes the current stream wait for the fill of ``start_fill`` / ``project_diag`` whose ticket names ``buf`` under ``key``."""
+        if prefill.get(key) is not buf:
+            raise RuntimeError("prefill ticket does not belong to this pass")
+        torch.cuda.current_stream(self.device).wait_event(prefill["event"])
 
     # ------------------------------------------------------------------ one N-pass
     def run(self, X, Y, Z, kernel, *, moment_Tm, moment_mode, gamma, lik_id=B.LIK_NONE, lik_param=0.0,
@@ -1146,13 +1151,9 @@ class EStepEngine:
             self._b_tag = None
             Kfu = self._get("Kfu", (Np, Mp), T)
             if prefill is not None:
-                if prefill["Kfu"] is not Kfu:
-                    raise RuntimeError("prefill ticket does not belong to this pass")
-                torch.cuda.current_stream(dev).wait_event(prefill["event"])
+                self._take_prefill(prefill, "Kfu", Kfu)
             else:
-                # a fill started for a pass that never ran must not land on top of this one (a capture begins synchronised)
-                if self._side is not None and not torch.cuda.is_current_stream_capturing():
-                    torch.cuda.current_stream(dev).wait_stream(self._side)
+                self._wait_stale_fill()
                 self.se_fill(X, Z, inv_ls, variance, Kfu, kernel.kind)
             A = Kfu
             if whiten_T is not None and not late_whiten:
@@ -1164,15 +1165,11 @@ class EStepEngine:
 
         Tm = self._pad_square(moment_Tm, Mp, "pad_Tm")
         gam = self._padded_gamma(gamma, Mp, P)
-        nblk = Np // B.TILE
-        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
-        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
         need_g = lik_id != B.LIK_NONE or site_grads is not None
         g0 = self._get("g0", (Np, P), T) if need_g else None
         g1 = self._get("g1", (Np, P), T) if need_g else None
         mean = torch.empty((N, P), dtype=T, device=dev) if want_moments else None
         var = torch.empty((N, P), dtype=T, device=dev) if (want_moments and not mean_only) else None
-        lik_flags = (lik_id | B.LIK_MEANONLY) if mean_only else lik_id
         tile, lm = None, None
         if site_grads is not None:
             g0.copy_(site_grads[0])
@@ -1186,32 +1183,21 @@ class EStepEngine:
             self.trmm(A, Tm[0], tile, moment_mode)
             mean = torch.mv(A[:N], gam[:, 0]).reshape(N, 1)  # gam: [Mp, 1], rows >= M zero
             var = (variance - torch.linalg.vector_norm(tile[:N], dim=1).square()).reshape(N, 1)
-            if site_grads is None:
-                self.lik_map(mean, var, Y, lik_id, lik_param, N, Np, g0=g0, g1=g1, ve_partial=ve_partial,
-                             nonpos_partial=nonpos_partial)
+            if site_grads is None:  # (the map writes the partials the moments launch would: the same cached buffers)
+                res = self.lik_map(mean, var, Y, lik_id, lik_param, N, Np, g0=g0, g1=g1)
+                ve_partial, nonpos_partial = res.ve_partial, res.nonpos_partial
         elif mapped:
-            if mean_only:
-                raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
-            # the moments of every latent with no likelihood, then the map on them (mean / var stay on this stream)
-            mean, var = self._get("coupled_mean", (N, P), T), self._get("coupled_var", (N, P), T)
-            with torch.cuda.device(dev):
-                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
-                    A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, variance, B.LIK_NONE, 0.0, mean.data_ptr(),
-                    var.data_ptr(), None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode,
-                    self._stream()))
-            lm = self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
+            mean, var, lm = self._moments_then_map(A, Tm, gam, variance, Y, lik_id, lik_param, N, Np, moment_mode, mean_only)
             g0, g1, ve_partial, nonpos_partial = lm.g0, lm.g1, lm.ve_partial, lm.nonpos_partial  # what the common tail reads
             if want_moments:
                 mean, var = mean.clone(), var.clone()
         elif site_grads is not None and not want_moments:
             pass  # the site sums alone
         else:
-            with torch.cuda.device(dev):
-                self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
-                    A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), _ptr(Y) if lik_id != B.LIK_NONE else None, variance, lik_flags,
-                    self._fused_param(lik_id, lik_param), _ptr(mean), _ptr(var), None if site_grads is not None else _ptr(g0),
-                    None if site_grads is not None else _ptr(g1), ve_partial.data_ptr(),
-                    nonpos_partial.data_ptr(), N, Np, Mp, P, moment_mode, self._stream()))
+            own = site_grads is None  # (with site_grads the launch writes mean / var only: g0, g1 hold the caller's)
+            ve_partial, nonpos_partial = self.moments(A, Tm, gam, variance, N, moment_mode, lik_id=lik_id, lik_param=lik_param,
+                                                      mean_only=mean_only, Y=Y if lik_id != B.LIK_NONE else None, mean=mean,
+                                                      var=var, g0=g0 if own else None, g1=g1 if own else None)
         if site_grads is not None:
             zero = torch.zeros((), dtype=torch.float64, device=dev)
             stats = EStepStats(n_rows=N, ve_sum=zero, nonpos=zero.clone())
@@ -1240,19 +1226,23 @@ class EStepEngine:
 
     def _site_sums(self, A, g0, g1, P, M):
         """(sum_n g1 a a^T [P, M, M], sum_n g0 a [P, M]) over the rows of one operand A [Np, Mp] shared by the P latents
-        (``tsvgp_site_accum_*``); g0, g1 [Np, P] with zero padding rows."""
+        (``tsvgp_site_accum_*``) or of one operand per latent, A [P, Np, Mp] (``tsvgp_site_accum_batched_*``); g0, g1 [Np, P] with
+        zero padding rows.  The only launch of either."""
         dev = self.device
-        Np, Mp = A.shape
+        Np, Mp = A.shape[-2:]
         nsplit = self.nsplit_override or self.choose_nsplit(Mp, P, Np)
         nsplit = max(1, min(nsplit, Np // site_sum_chunk_rows(self.dtype == torch.float64, P)))
         nbytes = int(self._fn("tsvgp_site_accum_work_bytes")(Mp, P, nsplit))
         work = self._get("work", (nbytes,), torch.uint8)
         acc2 = torch.empty((P, Mp, Mp), dtype=torch.float64, device=dev)
         acc1 = torch.empty((P, Mp), dtype=torch.float64, device=dev)
+        if A.dim() == 3:
+            fn, operand = self._fn("tsvgp_site_accum_batched"), (A.data_ptr(), Np * Mp)
+        else:
+            fn, operand = self._fn("tsvgp_site_accum"), (A.data_ptr(),)
         with torch.cuda.device(dev):
-            self._launch("tsvgp_site_accum", lambda: self._fn("tsvgp_site_accum")(
-                A.data_ptr(), g0.data_ptr(), g1.data_ptr(), acc2.data_ptr(), acc1.data_ptr(), work.data_ptr(), Np,
-                Mp, P, nsplit, self._stream()))
+            self._launch("tsvgp_site_accum", lambda: fn(*operand, g0.data_ptr(), g1.data_ptr(), acc2.data_ptr(), acc1.data_ptr(),
+                                                        work.data_ptr(), Np, Mp, P, nsplit, self._stream()))
         return acc2[:, :M, :M], acc1[:, :M]
 
     def run_two_product(self, X, Y, Z, kernel, *, whiten_T, moment_Tm, gamma, lik_id=B.LIK_NONE, lik_param=0.0, sites=False,
@@ -1349,8 +1339,7 @@ class EStepEngine:
         gam = self._padded_gamma(gamma, Mp, P)
         Kfu = self._get("Kfu", (Np, Mp), T)
         tile = self._get("Tt", (Np, Mp), T)
-        if self._side is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(dev).wait_stream(self._side)
+        self._wait_stale_fill()
         for p in range(P):
             kp = kernel.kernels[p] if separate else kernel
             inv_ls, variance = kp.inv_lengthscales(D, T, dev), kp.variance.item()
@@ -1399,7 +1388,7 @@ class EStepEngine:
     def project_diag(self, X, Z, kernel, w1, w2):
         """The projection of per-datum sites onto the inducing points (reference src/util.py:188-236 with cholesky=False and
         no K_uu):  acc2 = sum_n w2_n k_n k_n^T [1, M, M],  acc1 = sum_n w1_n k_n [1, M]  over k_n = K(Z, x_n), fp64 -- the fill
-        and ``tsvgp_site_accum_*`` with the caller's weights w1, w2 [Np, 1] (compute dtype, rows >= N zero) in place of the
+        and ``_site_sums`` with the caller's weights w1, w2 [Np, 1] (compute dtype, rows >= N zero) in place of the
         likelihood gradients.  The filled K(X, Z) stays in the buffer: the returned ticket hands it to ``run(prefill=...)`` /
         ``run_two_product`` / ``diag_sites_moments`` of the same step, which then do not fill again."""
         T, dev = self.dtype, self.device
@@ -1415,8 +1404,7 @@ class EStepEngine:
             return zero, torch.zeros((1, M), dtype=torch.float64, device=dev), None
         self._b_tag = None
         Kfu = self._get("Kfu", (Np, Mp), T)
-        if self._side is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(dev).wait_stream(self._side)
+        self._wait_stale_fill()
         self.se_fill(X, Z, kernel.inv_lengthscales(D, T, dev), kernel.variance.item(), Kfu, kernel.kind)
         acc2, acc1 = self._site_sums(Kfu, w1, w2, 1, M)
         done = torch.cuda.Event()
@@ -1440,16 +1428,9 @@ class EStepEngine:
             self.trmm(Kfu, self._pad_square(whiten_T, Mp, "pad_Linv"), A, B.TRI_UPPER)
         Tm = self._pad_square(moment_Tm, Mp, "pad_Tm")
         gam = self._padded_gamma(gamma, Mp, 1)
-        nblk = Np // B.TILE
-        ve_partial = self._get("ve_partial", (nblk,), torch.float64)
-        nonpos_partial = self._get("nonpos_partial", (nblk,), torch.int32)
         mean = self._get("ds_mean", (N, 1), T)
         var = None if mean_only else self._get("ds_var", (N, 1), T)
-        flags = (B.LIK_NONE | B.LIK_MEANONLY) if mean_only else B.LIK_NONE
-        with torch.cuda.device(dev):
-            self._launch("tsvgp_moments", lambda: self._fn("tsvgp_moments")(
-                A.data_ptr(), Tm.data_ptr(), gam.data_ptr(), None, kernel.variance.item(), flags, 0.0, mean.data_ptr(), _ptr(var),
-                None, None, ve_partial.data_ptr(), nonpos_partial.data_ptr(), N, Np, Mp, 1, moment_mode, self._stream()))
+        self.moments(A, Tm, gam, kernel.variance.item(), N, moment_mode, mean_only=mean_only, mean=mean, var=var)
         return mean, var
 
     def diag_site_step(self, mean, var, Y, lik_id, lik_param, lr, l1, l2, l1c=None, l2c=None):

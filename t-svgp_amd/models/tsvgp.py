@@ -39,7 +39,7 @@ import torch
 from .. import _backend as B
 from .. import distributed as D_
 from ..base import default_device, default_float, default_jitter, to_tensor
-from ..estep import EStepStats
+from ..estep import EStepStats, per_latent
 from ..inducing_variables import inducingpoint_wrapper
 from ..kernels import SeparateIndependent, latent_kernels
 from ..sites import DenseSites
@@ -1073,9 +1073,7 @@ class t_SVGP(base_SVGP):
             o = i * slot
             send[o:o + M * M] = ops["moment_Tm"][i].reshape(-1)
             send[o + M * M:o + M * M + M] = ops["gamma"][:, i]
-            wt = eng._per_latent(ops["whiten_T"], i) if hasattr(eng, "_per_latent") else (
-                None if ops["whiten_T"] is None else (ops["whiten_T"][i] if isinstance(ops["whiten_T"], (list, tuple)) else
-                                                      (ops["whiten_T"][i] if ops["whiten_T"].dim() == 3 else ops["whiten_T"])))
+            wt = per_latent(ops["whiten_T"], i)
             if routes[p] != "direct" and wt is not None:
                 send[o + M * M + M:o + slot] = wt.reshape(-1)
         allops = D_.all_gather_flat(send).reshape(G, per, slot)

@@ -2,10 +2,14 @@
 with the same interface, so that the HOST logic of the product -- M x M prelude, packing, the all-reduce over ranks and
 the site-update epilogue -- can be exercised on CPU (``gloo``, world_size 2) where no HIP kernel can run.
 It is never importable from the package and never used on a GPU box."""
+import importlib
+
 import numpy as np
 import torch
 
 from oracle import tsvgp_oracle as O
+
+per_latent = importlib.import_module("t-svgp_amd.estep").per_latent
 
 
 class _Stats:
@@ -25,12 +29,9 @@ class NumpyShardEngine:
         if hasattr(kernel, "kernels"):  # one pass per latent, as EStepEngine._run_separate
             parts = [self.run(X, None if Y is None else Y[:, p:p + 1], Z, kp, moment_Tm=moment_Tm[p:p + 1],
                               moment_mode=moment_mode, gamma=gamma[:, p:p + 1], lik_id=lik_id, lik_param=lik_param,
-                              whiten_T=(whiten_T[p] if isinstance(whiten_T, (list, tuple)) else None if whiten_T is None
-                                        else (whiten_T[p] if whiten_T.dim() == 3 else whiten_T)),
-                              whiten_mode=whiten_mode, sites=sites, want_moments=want_moments, want_grads=want_grads,
-                              project_T=(project_T[p] if isinstance(project_T, (list, tuple)) else None if project_T is None
-                                         else (project_T[p] if project_T.dim() == 3 else project_T)),
-                              mean_only=mean_only, moments_on_kfu=moments_on_kfu, project_mode=project_mode)
+                              whiten_T=per_latent(whiten_T, p), whiten_mode=whiten_mode, sites=sites, want_moments=want_moments,
+                              want_grads=want_grads, project_T=per_latent(project_T, p), mean_only=mean_only,
+                              moments_on_kfu=moments_on_kfu, project_mode=project_mode)
                      for p, kp in enumerate(kernel.kernels)]
             st = _Stats()
             st.n_rows = parts[0].n_rows
