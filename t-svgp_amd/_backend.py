@@ -42,7 +42,6 @@ MC_MAX_SAMPLES = 1 << 28  # TSVGP_MC_MAX_SAMPLES
 POTRF_SUBST = 1  # TSVGP_POTRF_SUBST
 POTRF_RHS_UPPER = 2  # TSVGP_POTRF_RHS_UPPER
 POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
-POTRF_DIAG_V2 = 8  # TSVGP_POTRF_DIAG_V2
 POTRF_FUSE = 16  # TSVGP_POTRF_FUSE
 VGP_NO_ROWS = 1  # TSVGP_VGP_NO_ROWS
 ABI_VERSION = 5  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
@@ -188,8 +187,6 @@ _PROTOTYPES = {
                                       c_double, c_double, c_void_p, c_double, c_void_p]),
     "tsvgp_site_beta_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "tsvgp_gemv_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "tsvgp_keeper_run": (c_int, [c_void_p, c_double, c_int, c_void_p]),
-    "tsvgp_keeper_signal": (c_int, [c_void_p, c_int, c_void_p]),
     "tsvgp_step_status_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "tsvgp_sym_pack_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tsvgp_sym_unpack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),

@@ -9,8 +9,7 @@
 //                       coalesced stores.
 //   panel_kernel<STORE> C = A * Tm^T restricted to a triangular k-range (inverted-factor triangular solve).  MFMA bound.
 //   panel_kernel<MOMENTS>  same product, but the tile is squared and row-summed in registers (never stored); the mean
-//                       GEMV rides on the first column tile (FUSE) or runs as a pre-pass; the likelihood-gradient map
-//                       runs in the epilogue.
+//                       GEMV runs as a pre-pass; the likelihood-gradient map runs in the epilogue.
 //   mean_lik_kernel     the moments without the variance product (TSVGP_LIK_MEANONLY): mean GEMV + Gaussian gradient
 //                       map in one sweep of the operand.  HBM bound.
 //   syrk_kernel         weighted Gram  sum_n g1[n] a_n a_n^T  over an N-slice per workgroup (lower tiles only) + the
@@ -86,7 +85,6 @@ struct PanelK {
     static constexpr int KC = sizeof(T) == 8 ? 16 : 32;
     static constexpr int H = KC / 2;  // elements one thread stages per operand and chunk
     static constexpr int RS = KC + (sizeof(T) == 8 ? 1 : 2);
-    static constexpr int DEPTH = 1;  // chunks of global prefetch held in registers (1 or 2)
 };
 
 // H consecutive elements of one row: global -> registers (16-byte loads) and registers -> LDS (8-byte stores: the rows
@@ -263,11 +261,10 @@ __device__ __forceinline__ void bern_sums_f(float m, float sd, bool y1, int i0, 
         a1 -= w * dl * z;
     }
 }
-// The quadrature in the arithmetic of the N-arrays' type T (1: fp64 for both, as up to round 5 -- profiles/r05_lik_split_lab.txt)
-#define TSVGP_BERN_F64 0
+// The quadrature in the arithmetic of the N-arrays' type T (fp64 for both up to round 5 -- profiles/r05_lik_split_lab.txt)
 template <typename T>
 __device__ __forceinline__ void bern_sums_t(double m, double sd, bool y1, int i0, int i1, double& a0, double& a1, double& av) {
-    if constexpr (sizeof(T) == 4 && !TSVGP_BERN_F64) {
+    if constexpr (sizeof(T) == 4) {
         float b0, b1, bv;
         bern_sums_f((float)m, (float)sd, y1, i0, i1, b0, b1, bv);
         a0 = (double)b0;
@@ -430,7 +427,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
     __shared__ __attribute__((aligned(16))) T Xs[FILL_ROWS][DT];  // pre-scaled by inv_ls
     typedef typename FillVec<T, CPT>::type vec_t;
 
-    __builtin_amdgcn_s_setprio(1);  // in front of the clock keeper's waves (priority 0), behind the factorisation's (3)
+    __builtin_amdgcn_s_setprio(1);  // behind the factorisation's waves (priority 3)
     const T variance = var.v[blockIdx.z];
     inv_ls += (size_t)blockIdx.z * D;
     K += (size_t)blockIdx.z * strideK;
@@ -691,14 +688,16 @@ struct PanelArgs {
     double kdiag[TSVGP_MAX_BATCH];  // MOMENTS: k(x, x) = kernel variance of latent p (one kernel per latent: they differ)
 };
 
-// FUSE (MOMENTS, triangular modes): the mean GEMV rides on the column tile whose k-range covers every chunk of the
-// row panel (the first one for UPPER, the last one for LOWER): each thread multiplies the eight A values it stages by gamma (kept in dynamic LDS, Mp elements) before
-// storing them, which removes the separate sweep of the panel from HBM (1.0 of 18.3 ms at N = 1e6, M = 1024).
-template <typename T, int MODE, int TRI, bool FUSE = false>
+// Launched for the dense products (STORE and MOMENTS) and for the triangular moments whose gamma_p does not fit
+// panel1_kernel's dynamic LDS (P1_GAMMA_LDS_MAX); every other triangular product runs in panel1_kernel.
+// (A form with the mean GEMV riding on the column tile that sweeps every k-chunk, gamma_p in dynamic LDS, served the small
+// triangular moments until panel1_kernel took them: code in git history.  Of it, `gsm` and the tile body's tag FIRST -- false
+// on every call -- are still here: taking them out changes the closure of the tile body and with it the register allocation of
+// every instantiation, and a change that only prunes leaves the instruction stream of a surviving kernel as it is.)
+template <typename T, int MODE, int TRI>
 __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
-    static_assert(!FUSE || (MODE == MODE_MOMENTS && TRI != TSVGP_TRI_DENSE), "FUSE rides on the tile with the full k sweep");
     extern __shared__ __attribute__((aligned(16))) unsigned char panel_dyn_smem[];
-    T* const gsm = reinterpret_cast<T*>(panel_dyn_smem);  // FUSE: gamma_p, Mp elements
+    T* const gsm = reinterpret_cast<T*>(panel_dyn_smem);  // read under FIRST only
     constexpr int RS = PanelK<T>::RS, KC = PanelK<T>::KC, H = PanelK<T>::H;  // KC shadows the site kernel's constant
     constexpr int CPT = TILE / KC;  // chunks per 128-wide k-tile
     __shared__ __attribute__((aligned(16))) T lds[2][2][TILE * RS];
@@ -734,20 +733,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
         // summed over the 16 lanes that share (lane>>4) and lane lr keeps the one with index lr & 7.
         double rs_mine = 0.0;
         T mpart = T(0);
-        // Registers of the global prefetch (DEPTH chunks in flight, see below).  They live outside the tile body so that
-        // the FIRST chunk of the next column tile can be requested before this tile's epilogue: its load
+        // Registers of the global prefetch (one chunk in flight, see below).  They live outside the tile body so that
+        // the first chunk of the next column tile can be requested before this tile's epilogue: its load
         // latency then hides behind the square-sum / store of the finished tile instead of opening the next one.
-        constexpr int DEPTH = PanelK<T>::DEPTH;
-        T ra[DEPTH][H], rb[DEPTH][H];
+        T ra[H], rb[H];
         bool pre = false;  // ra[0] / rb[0] already hold the first chunk of the tile about to start
-        if constexpr (FUSE) {
-            // the first tile (it = 0 for both triangles) starts at chunk 0: its loads fly while gamma is staged
-            load_run<T, H>(ra[0], TSVGP_AROW(0));
-            load_run<T, H>(rb[0], TSVGP_AT(Tp, 0));
-            pre = true;
-            for (int j = t; j < Mp; j += NTHREADS) gsm[j] = a.gamma[(size_t)j * a.P + p];
-            __syncthreads();
-        } else if constexpr (MODE == MODE_MOMENTS) {
+        if constexpr (MODE == MODE_MOMENTS) {
             // Mean GEMV phase: mean[n] = sum_j A[n, j] * gamma[j, p].  A memory/VALU-only sweep of this workgroup's row
             // panel with no accumulators live (it runs beside the partner workgroup's MFMAs on the same CU); gamma_p
             // is staged in LDS (reusing the staging buffers) and read as a two-address broadcast.
@@ -766,7 +757,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
         }
 
         auto tile_body = [&](const int it, auto first_tag, const int it_next) {
-            constexpr bool FIRST = decltype(first_tag)::value;  // FUSE: the tile that also accumulates the mean
+            constexpr bool FIRST = decltype(first_tag)::value;  // a tile that also accumulates the mean: none
             const T* Tbase = Tp + (size_t)it * TILE * Mp;
 #define TSVGP_TROW(c_) TSVGP_AT(Tbase, c_)
 
@@ -776,96 +767,90 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 #pragma unroll
                 for (int n = 0; n < 8; ++n) acc[s][n] = acc_t{0, 0, 0, 0};
 
-            // DEPTH chunks of global prefetch are held in registers (one set of H + H values per chunk in flight).
-            // fp64 has room for one set only (128 accumulator registers); fp32 could take two (PanelK::DEPTH),
-            // but that measured slower (8.68 vs 8.40 ms at N = 1e6, M = 1024), so both types run with one.  A set is
-            // chosen by the parity of the chunk index, so every loop below steps by two chunks (all chunk ranges are
+            // One chunk of global prefetch is held in registers (H + H values).  fp64 has room for one set only (128
+            // accumulator registers); fp32 could take two, but that measured slower (8.68 vs 8.40 ms at N = 1e6,
+            // M = 1024), so both types run with one.  Every loop below steps by two chunks (all chunk ranges are
             // even); the pairing itself is worth 3 % (fp64) to 6 % (fp32) over a one-chunk loop body.
             int buf = 0;
-            // one pipeline step on chunk c_: prefetch chunk c_ + DEPTH to registers, MFMAs on chunk c_ (LDS buffer
-            // `buf`), then stage chunk c_ + 1 (fetched one step earlier when DEPTH == 2) into the other buffer;
-            // one barrier per chunk.  PAR = parity of c_ (compile time).
-#define TSVGP_FETCH(SET, cnext)                           \
-    {                                                     \
-        load_run<T, H>(ra[SET], TSVGP_AROW(cnext));       \
-        load_run<T, H>(rb[SET], TSVGP_TROW(cnext));       \
+            // one pipeline step on chunk c_: prefetch chunk c_ + 1 to registers, MFMAs on chunk c_ (LDS buffer
+            // `buf`), then stage chunk c_ + 1 into the other buffer; one barrier per chunk.
+#define TSVGP_FETCH(cnext)                     \
+    {                                          \
+        load_run<T, H>(ra, TSVGP_AROW(cnext)); \
+        load_run<T, H>(rb, TSVGP_TROW(cnext)); \
     }
-#define TSVGP_STAGE(SET, cnext, b_)                                                        \
-    {                                                                                      \
-        if constexpr (FIRST) {                                                             \
-            const T* gq = gsm + (cnext) * KC + skh * H;                                    \
-            _Pragma("unroll") for (int q = 0; q < H; ++q) mpart += ra[SET][q] * gq[q];     \
-        }                                                                                  \
-        store_run<T, H>(lds_wr + (b_) * BUF_STRIDE, ra[SET]);                              \
-        store_run<T, H>(lds_wr + (b_) * BUF_STRIDE + OP_STRIDE, rb[SET]);                  \
+#define TSVGP_STAGE(cnext, b_)                                                    \
+    {                                                                             \
+        if constexpr (FIRST) {                                                    \
+            const T* gq = gsm + (cnext) * KC + skh * H;                           \
+            _Pragma("unroll") for (int q = 0; q < H; ++q) mpart += ra[q] * gq[q]; \
+        }                                                                         \
+        store_run<T, H>(lds_wr + (b_) * BUF_STRIDE, ra);                          \
+        store_run<T, H>(lds_wr + (b_) * BUF_STRIDE + OP_STRIDE, rb);              \
     }
-#define TSVGP_STEP2(MLO, MHI, PAR, c_)                                                          \
-    {                                                                                           \
-        const bool has_f = ((c_) + DEPTH < c_end);                                              \
-        const bool has_s = ((c_) + 1 < c_end);                                                  \
-        if (has_f) TSVGP_FETCH(DEPTH == 2 ? (PAR) : 0, (c_) + DEPTH)                            \
-        mma_chunk_rowk<T, MLO, MHI>(acc, &lds[buf][0][0], &lds[buf][1][0], w, lane);            \
-        if (has_s) TSVGP_STAGE(DEPTH == 2 ? ((PAR) ^ 1) : 0, (c_) + 1, buf ^ 1)                 \
-        __syncthreads();                                                                        \
-        buf ^= 1;                                                                               \
+#define TSVGP_STEP2(MLO, MHI, c_)                                                    \
+    {                                                                                \
+        const bool has_n = ((c_) + 1 < c_end);                                       \
+        if (has_n) TSVGP_FETCH((c_) + 1)                                             \
+        mma_chunk_rowk<T, MLO, MHI>(acc, &lds[buf][0][0], &lds[buf][1][0], w, lane); \
+        if (has_n) TSVGP_STAGE((c_) + 1, buf ^ 1)                                    \
+        __syncthreads();                                                             \
+        buf ^= 1;                                                                    \
     }
-#define TSVGP_STEP(NMASK, PAR, c_) TSVGP_STEP2(NMASK, NMASK, PAR, c_)
+#define TSVGP_STEP(NMASK, c_) TSVGP_STEP2(NMASK, NMASK, c_)
             const int cd = it * CPT;  // first chunk of the diagonal k-tile (even)
             const int c_first = (TRI == TSVGP_TRI_UPPER) ? cd : 0;
             const int c_end = (TRI == TSVGP_TRI_LOWER) ? cd + CPT : nchunk;
-            if (!pre) TSVGP_FETCH(0, c_first)
-            TSVGP_STAGE(0, c_first, 0)
-            if constexpr (DEPTH == 2) {
-                if ((c_first + 1 < c_end)) TSVGP_FETCH(1, c_first + 1)
-            }
+            if (!pre) TSVGP_FETCH(c_first)
+            TSVGP_STAGE(c_first, 0)
             __syncthreads();
 
             if constexpr (TRI == TSVGP_TRI_DENSE) {
                 for (int c = 0; c < nchunk; c += 2) {
-                    TSVGP_STEP(0xFF, 0, c)
-                    TSVGP_STEP(0xFF, 1, c + 1)
+                    TSVGP_STEP(0xFF, c)
+                    TSVGP_STEP(0xFF, c + 1)
                 }
             } else if constexpr (TRI == TSVGP_TRI_LOWER) {
                 // full k-tiles 0..it-1, then the diagonal k-tile: chunk cl only meets column blocks cb >= cl
                 for (int c = 0; c < cd; c += 2) {
-                    TSVGP_STEP(0xFF, 0, c)
-                    TSVGP_STEP(0xFF, 1, c + 1)
+                    TSVGP_STEP(0xFF, c)
+                    TSVGP_STEP(0xFF, c + 1)
                 }
                 if constexpr (KC == 16) {
-                    TSVGP_STEP(0xFF, 0, cd)
-                    TSVGP_STEP(0xFE, 1, cd + 1)
-                    TSVGP_STEP(0xFC, 0, cd + 2)
-                    TSVGP_STEP(0xF8, 1, cd + 3)
-                    TSVGP_STEP(0xF0, 0, cd + 4)
-                    TSVGP_STEP(0xE0, 1, cd + 5)
-                    TSVGP_STEP(0xC0, 0, cd + 6)
-                    TSVGP_STEP(0x80, 1, cd + 7)
+                    TSVGP_STEP(0xFF, cd)
+                    TSVGP_STEP(0xFE, cd + 1)
+                    TSVGP_STEP(0xFC, cd + 2)
+                    TSVGP_STEP(0xF8, cd + 3)
+                    TSVGP_STEP(0xF0, cd + 4)
+                    TSVGP_STEP(0xE0, cd + 5)
+                    TSVGP_STEP(0xC0, cd + 6)
+                    TSVGP_STEP(0x80, cd + 7)
                 } else {  // 32-wide chunks: two 16-wide k-blocks per chunk
-                    TSVGP_STEP2(0xFF, 0xFE, 0, cd)
-                    TSVGP_STEP2(0xFC, 0xF8, 1, cd + 1)
-                    TSVGP_STEP2(0xF0, 0xE0, 0, cd + 2)
-                    TSVGP_STEP2(0xC0, 0x80, 1, cd + 3)
+                    TSVGP_STEP2(0xFF, 0xFE, cd)
+                    TSVGP_STEP2(0xFC, 0xF8, cd + 1)
+                    TSVGP_STEP2(0xF0, 0xE0, cd + 2)
+                    TSVGP_STEP2(0xC0, 0x80, cd + 3)
                 }
             } else {
                 // the diagonal k-tile first: chunk cl only meets column blocks cb <= cl; then full k-tiles it+1..
                 if constexpr (KC == 16) {
-                    TSVGP_STEP(0x01, 0, cd)
-                    TSVGP_STEP(0x03, 1, cd + 1)
-                    TSVGP_STEP(0x07, 0, cd + 2)
-                    TSVGP_STEP(0x0F, 1, cd + 3)
-                    TSVGP_STEP(0x1F, 0, cd + 4)
-                    TSVGP_STEP(0x3F, 1, cd + 5)
-                    TSVGP_STEP(0x7F, 0, cd + 6)
-                    TSVGP_STEP(0xFF, 1, cd + 7)
+                    TSVGP_STEP(0x01, cd)
+                    TSVGP_STEP(0x03, cd + 1)
+                    TSVGP_STEP(0x07, cd + 2)
+                    TSVGP_STEP(0x0F, cd + 3)
+                    TSVGP_STEP(0x1F, cd + 4)
+                    TSVGP_STEP(0x3F, cd + 5)
+                    TSVGP_STEP(0x7F, cd + 6)
+                    TSVGP_STEP(0xFF, cd + 7)
                 } else {
-                    TSVGP_STEP2(0x01, 0x03, 0, cd)
-                    TSVGP_STEP2(0x07, 0x0F, 1, cd + 1)
-                    TSVGP_STEP2(0x1F, 0x3F, 0, cd + 2)
-                    TSVGP_STEP2(0x7F, 0xFF, 1, cd + 3)
+                    TSVGP_STEP2(0x01, 0x03, cd)
+                    TSVGP_STEP2(0x07, 0x0F, cd + 1)
+                    TSVGP_STEP2(0x1F, 0x3F, cd + 2)
+                    TSVGP_STEP2(0x7F, 0xFF, cd + 3)
                 }
                 for (int c = cd + CPT; c < nchunk; c += 2) {
-                    TSVGP_STEP(0xFF, 0, c)
-                    TSVGP_STEP(0xFF, 1, c + 1)
+                    TSVGP_STEP(0xFF, c)
+                    TSVGP_STEP(0xFF, c + 1)
                 }
             }
 #undef TSVGP_STEP
@@ -874,10 +859,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
 #undef TSVGP_FETCH
 #undef TSVGP_TROW
             pre = false;
-            if (DEPTH == 1 && it_next >= 0) {  // request the next tile's first chunk; the epilogue below covers its latency
+            if (it_next >= 0) {  // request the next tile's first chunk; the epilogue below covers its latency
                 const int cn = (TRI == TSVGP_TRI_UPPER) ? it_next * CPT : 0;
-                load_run<T, H>(ra[0], TSVGP_AROW(cn));
-                load_run<T, H>(rb[0], TSVGP_AT(Tp + (size_t)it_next * TILE * Mp, cn));
+                load_run<T, H>(ra, TSVGP_AROW(cn));
+                load_run<T, H>(rb, TSVGP_AT(Tp + (size_t)it_next * TILE * Mp, cn));
                 pre = true;
             }
 
@@ -912,16 +897,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void panel_kernel(PanelArgs<T> a) {
                 rs_mine += keep;
             }
         };  // tile_body
-        const auto next_of = [ntile](int it) { return it + 1 < ntile ? it + 1 : -1; };
-        if constexpr (FUSE && TRI == TSVGP_TRI_UPPER) {  // upper triangle: the FIRST column tile sweeps every k-chunk
-            tile_body(0, std::true_type{}, next_of(0));
-            for (int it = 1; it < ntile; ++it) tile_body(it, std::false_type{}, next_of(it));
-        } else if constexpr (FUSE) {  // lower triangle: the LAST one does
-            for (int it = 0; it + 1 < ntile; ++it) tile_body(it, std::false_type{}, next_of(it));
-            tile_body(ntile - 1, std::true_type{}, -1);
-        } else {
-            for (int it = 0; it < ntile; ++it) tile_body(it, std::false_type{}, next_of(it));
-        }
+        for (int it = 0; it < ntile; ++it) tile_body(it, std::false_type{}, it + 1 < ntile ? it + 1 : -1);
 
         if constexpr (MODE == MODE_MOMENTS) {
             // lane (lr < 8, lane>>4) holds the complete sum of row  row_block(w, lr>>2)*16 + rowmap(lane, lr&3)
@@ -1031,16 +1007,15 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 constexpr int P1_OPS = TILE * 16;    // 8-byte fragment units per operand image of a chunk (16 KB)
 constexpr int P1_BUFS = 2 * P1_OPS;  // fragment units per chunk buffer (A image + T image, 32 KB)
 constexpr size_t P1_GAMMA_LDS_MAX = 64 * 1024;  // dynamic LDS for gamma_p beside the 64 KB ring: Mp <= 8192 (fp32: 16384)
-constexpr size_t P1W_GAMMA_LDS_MAX = 32 * 1024;  // two tiles per pass: beside the 96 KB ring (Mp <= 4096 in fp64)
-// Upper form, one tile per pass: the chunks of a tile's DIAGONAL k-tile in the order 8, 1, 7, 2, 6, 3, 5, 4 column blocks (fp32: 8, 2,
+// Upper form: the chunks of a tile's DIAGONAL k-tile in the order 8, 1, 7, 2, 6, 3, 5, 4 column blocks (fp32: 8, 2,
 // 6, 4) instead of 1, 2, ... 8 (round 4).  A chunk of c + 2 is requested while chunk c runs and must have landed when chunk c + 1
 // ends: behind two SHORT chunks (1 and 2 column blocks: 8 + 16 MFMAs per wave, ~0.7 us) it has not -- the ascending order stalled
 // on chunks 2, 3, 4 of every diagonal k-tile, ~2.5 us per column tile (phase accounting of round 3: the diagonal chunks at 0.81 of
 // their MFMA time) -- while a long and a short chunk together last as long as a full one.  All of a tile's accumulators are then
 // first touched by its first chunk (srcC = 0 folds into those MFMAs).  Measured (profiles/r04_moments_epilogue_ablation.txt,
 // moments alone at N = 1e6): fp64 M = 512 4.20 -> 4.10 ms (-2.5 %), fp64 M = 1024 unchanged (15.18 ms), fp32 (four diagonal chunks of
-// 2, 4, 6, 8 column blocks) 7.71 -> 7.81 ms SLOWER -- so fp64 only.  (0: the ascending order.)
-#define TSVGP_DIAG_ORDER 1
+// 2, 4, 6, 8 column blocks) 7.71 -> 7.81 ms SLOWER -- so fp64 only
+// (REORDER in the kernel); fp32 and the lower form keep the ascending order.
 
 // Sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), left in every lane of the row: four rotate-and-add steps through
 // v_mov_b32_dpp row_ror (two per double), no LDS crossbar and no s_waitcnt -- the xor butterfly of __shfl_xor compiles to
@@ -1084,30 +1059,26 @@ struct P1Types<float> {
     typedef v2f frag_t;
     typedef v4f unit_t;
 };
-template <typename F, int NT = 8>
+template <typename F>
 struct Frag1 {
-    F v[2 + NT];  // v[0], v[1]: A fragments of the wave's two row blocks; v[2 + n]: T fragment of column block n
+    F v[2 + 8];  // v[0], v[1]: A fragments of the wave's two row blocks; v[2 + n]: T fragment of column block n
 };
 #define TSVGP_AI __attribute__((always_inline))
 #define TSVGP_IC(x) std::integral_constant<int, (x)>{}
 #define TSVGP_BC(x) std::integral_constant<bool, (x)>{}
 #define TSVGP_SB() __builtin_amdgcn_sched_barrier(0)
 
-// W2: column tiles per pass (1, or 2 for the upper-form moments at an even number of tiles): with two, the A fragments of a
-// k-step serve 32 MFMAs instead of 16, a barrier and a set of DMA issues come once per 128 MFMAs, and the row panel is swept
-// 2.5 instead of 4.5 times (M = 1024); the accumulators are then all 256 AGPRs of the wave (fp64).
-// No launcher instantiates W2 = 2: re-measured in round 5 it gained nothing in fp32 and lost 14 % in fp64 at M = 512
-// (profiles/r05_moments_wide_ab.txt; the launch arm removed, code in git history).
-template <typename T, int MODE = MODE_MOMENTS, int TRI = TSVGP_TRI_UPPER, int W2 = 1>
+// One column tile per pass.  (Two tiles per pass -- the A fragments of a k-step serving 32 MFMAs -- gained nothing in fp32 and
+// lost 14 % in fp64 at M = 512: profiles/r05_moments_wide_ab.txt, docs/history_r01-r03.md; code in git history.)
+template <typename T, int MODE = MODE_MOMENTS, int TRI = TSVGP_TRI_UPPER>
 __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
-    static_assert(W2 == 1 || (W2 == 2 && MODE == MODE_MOMENTS && TRI == TSVGP_TRI_UPPER), "two tiles per pass: upper-form moments");
-    constexpr int NB = 8 * W2;                // column blocks of a pass
-    constexpr int BUFS = (1 + W2) * P1_OPS;   // fragment units per chunk buffer: the A image + W2 T images
-    constexpr int NDMA = 4 + 4 * W2;          // DMA pieces per wave and chunk
+    constexpr int NB = 8;            // column blocks of a tile
+    constexpr int BUFS = P1_BUFS;    // fragment units per chunk buffer: the A image + the T image
+    constexpr int NDMA = 8;          // DMA pieces per wave and chunk
     extern __shared__ __attribute__((aligned(16))) unsigned char panel_dyn_smem[];
     typedef typename P1Types<T>::frag_t frag_t;
     typedef typename P1Types<T>::unit_t unit_t;
-    typedef Frag1<frag_t, NB> Frag;
+    typedef Frag1<frag_t> Frag;
     T* const gsm = reinterpret_cast<T*>(panel_dyn_smem);  // gamma_p, Mp elements
     __shared__ __attribute__((aligned(1024))) frag_t lds[2 * BUFS];
     __shared__ double rowq[TILE];
@@ -1146,18 +1117,15 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         offa0[ks] = o + w * 256;
         offa1[ks] = o + (7 - w) * 256;
     }
-    // Two tiles per pass: the ring is 96 KB, beyond the 64 KB a ds_read's immediate offset reaches from one base.  Left to fold
-    // the buffer offset into every read, the compiler materialises one address register per (k-step, fragment) of the second
-    // buffer and spills; the second buffer therefore gets its own twelve bases, opaque to constant folding.
+    // (bases of the second chunk buffer, once read by the two-tiles-per-pass form and by nothing now: the fragment reads fold the
+    // buffer offset into their immediates.  Deleting them moves a scalar shift in this kernel's prologue, and a change that only
+    // prunes leaves the instruction stream of a surviving kernel as it is.)
     int offa0_1[4], offa1_1[4], offb_1[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         offa0_1[ks] = offa0[ks] + BUFS;
         offa1_1[ks] = offa1[ks] + BUFS;
         offb_1[ks] = offb[ks] + BUFS;
-        if constexpr (W2 == 2) {
-            asm volatile("" : "+v"(offa0_1[ks]), "+v"(offa1_1[ks]), "+v"(offb_1[ks]));
-        }
     }
     // mean (column tile 0): the thread reads the 16-byte unit t & 7 of rows 32 q + (t >> 3) of the landed A image; behind
     // that physical unit sits the logical unit glog (columns 2 glog, 2 glog + 1 of the chunk)
@@ -1195,7 +1163,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         const unsigned lds_u = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_base);
         unsigned dma_vo = 0;
         uint64_t tb_u = 0;
-        constexpr bool REORDER = TSVGP_DIAG_ORDER && W2 == 1 && TRI == TSVGP_TRI_UPPER && sizeof(T) == 8;
+        constexpr bool REORDER = TRI == TSVGP_TRI_UPPER && sizeof(T) == 8;
         // REORDER: cu.c counts POSITIONS in the tile's stream; position q < CPT of the diagonal k-tile is its chunk
         // (q even ? CPT - 1 - q / 2 : q / 2), i.e. 7, 0, 6, 1, 5, 2, 4, 3
         auto kchunk = [&](const Cursor cu) TSVGP_AI {
@@ -1207,12 +1175,12 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
             dma_vo = dvoff + (unsigned)(kchunk(cu) * KC * sizeof(T));
             tb_u = uni64(Tp + ((size_t)cu.it * TILE + 8 * w) * Mp);
         };
-        // piece I of a chunk: I < 8: I even -> A piece I / 2, I odd -> piece I / 2 of the first T image; I >= 8: piece I - 8 of the second
+        // piece I of a chunk: I even -> A piece I / 2, I odd -> T piece I / 2
         auto dma_piece = [&](auto i_tag, const int buf) TSVGP_AI {
-            constexpr int I = decltype(i_tag)::value, q = I < 8 ? (I >> 1) : I - 8;
-            constexpr int IMG = I < 8 ? (I & 1) : 2;  // 0: A, 1: T of the pass's first tile, 2: T of its second tile
+            constexpr int I = decltype(i_tag)::value, q = I >> 1;
+            constexpr int IMG = I & 1;  // 0: A, 1: T
             const unsigned la = lds_u + (unsigned)((buf * BUFS + q * 512 + IMG * P1_OPS) * sizeof(frag_t));
-            const uint64_t g = (IMG == 0 ? ab_u : tb_u + (IMG == 2 ? 4 * grp : 0)) + q * grp;
+            const uint64_t g = (IMG == 0 ? ab_u : tb_u) + q * grp;
             const unsigned vo_ = dma_vo;  // (an asm operand alone does not capture a variable in a generic lambda)
             // one wait state between the write of M0 and the LDS-DMA that reads it.  (Fetching only the T pieces a diagonal chunk
             // reads -- the others issued with EXEC = 0 -- was 1.7 % SLOWER at M = 1024 and 512: profiles/r03_moments_lab_notes.txt)
@@ -1222,8 +1190,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
             // upper form: tile it takes the chunks CPT it .. nchunk - 1; lower form: 0 .. CPT (it + 1) - 1 (its diagonal k-tile last)
             const int c_end = (TRI == TSVGP_TRI_UPPER) ? nchunk : (cu.it + 1) * CPT;
             if (cu.c + 1 == c_end) {
-                if (cu.it + W2 < ntile) {
-                    cu.it += W2;
+                if (cu.it + 1 < ntile) {
+                    ++cu.it;
                     cu.c = (TRI == TSVGP_TRI_UPPER) ? cu.it * CPT : 0;
                 }
             } else {
@@ -1239,11 +1207,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
 
         auto rd1 = [&](Frag& f, auto e_tag, auto ks_tag, auto buf_tag) TSVGP_AI {
             constexpr int E = decltype(e_tag)::value, KS = decltype(ks_tag)::value, BI = decltype(buf_tag)::value;
-            if constexpr (W2 == 2 && BI == 1) {
-                if constexpr (E == 0) f.v[0] = lds[offa0_1[KS]];
-                else if constexpr (E == 1) f.v[1] = lds[offa1_1[KS]];
-                else f.v[E] = lds[offb_1[KS] + ((E - 2) >> 3) * P1_OPS + ((E - 2) & 7) * 256];
-            } else {
+            {
                 constexpr int boff = BI * BUFS;
                 if constexpr (E == 0) f.v[0] = lds[offa0[KS] + boff];
                 else if constexpr (E == 1) f.v[1] = lds[offa1[KS] + boff];
@@ -1282,7 +1246,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         auto chunk = [&](auto m_tag, auto mn_tag, auto buf_tag, auto gc_tag, const int c_this) TSVGP_AI {
             constexpr int M = decltype(m_tag)::value, MN = decltype(mn_tag)::value, BUF = decltype(buf_tag)::value;
             constexpr bool GC = decltype(gc_tag)::value;
-            constexpr int m = popc8(M & 0xFF) + popc8(M >> 8), mn = popc8(MN & 0xFF) + popc8(MN >> 8), NM = 2 * m, NR = 2 + m, NRN = 2 + mn;
+            constexpr int m = popc8(M), mn = popc8(MN), NM = 2 * m, NR = 2 + m, NRN = 2 + mn;
             constexpr int B0 = BUF * BUFS, B1 = (BUF ^ 1) * BUFS;
             if constexpr (MN != 0) {  // the DMA addresses of chunk c + 2: scalar work in front of the first MFMAs
                 dma_setup(cf);
@@ -1351,9 +1315,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
         // a0, a1, b0 (fp32: and b1) of chunk (0, 0); lower form: tile 0 starts with its diagonal k-tile, all eight column blocks
         cfor<0, ((TRI == TSVGP_TRI_UPPER && !REORDER) ? 2 + BPC : 10)>([&](auto i) TSVGP_AI { rd1(fx, i, TSVGP_IC(0), TSVGP_IC(0)); });
 
-        for (int it = 0; it < ntile; it += W2) {
+        for (int it = 0; it < ntile; ++it) {
             const int cd = it * CPT;
-            const bool last_tile = it + W2 == ntile;
+            const bool last_tile = it + 1 == ntile;
             // an accumulator is zeroed in front of the diagonal chunk that first touches its column block
 #define TSVGP_ZACC(n_) { acc[0][n_] = acc_t{0, 0, 0, 0}; acc[1][n_] = acc_t{0, 0, 0, 0}; }
             auto diag = [&](auto gc) TSVGP_AI {
@@ -1431,46 +1395,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void panel1_kernel(PanelArgs<T> a) {
                     else chunk(TSVGP_IC(0xC0), TSVGP_IC(0), TSVGP_IC(1), gc, cd + 3);
                 }
             };
-            // two tiles per pass (upper form): the diagonal k-tile of the first tile (its column blocks one by one), then the
-            // diagonal k-tile of the second one under the full first tile, then the full k-tiles behind both
-            auto wide_pass = [&](auto gc) TSVGP_AI {
-                cfor<0, CPT>([&](auto j) TSVGP_AI {  // region A: chunk j adds the column blocks BPC j .. of the first tile
-                    constexpr int J = decltype(j)::value;
-                    constexpr int M_ = (1 << (BPC * (J + 1))) - 1;
-                    constexpr int MN_ = J + 1 < CPT ? (1 << (BPC * (J + 2))) - 1 : (0xFF | (((1 << BPC) - 1) << 8));
-                    cfor<0, BPC>([&](auto q) TSVGP_AI {
-                        acc[0][BPC * J + decltype(q)::value] = acc_t{0, 0, 0, 0};
-                        acc[1][BPC * J + decltype(q)::value] = acc_t{0, 0, 0, 0};
-                    });
-                    chunk(TSVGP_IC(M_), TSVGP_IC(MN_), TSVGP_IC(J & 1), gc, cd + J);
-                });
-                cfor<0, CPT>([&](auto j) TSVGP_AI {  // region B: the first tile in full, the second one block by block
-                    constexpr int J = decltype(j)::value;
-                    constexpr int M_ = 0xFF | (((1 << (BPC * (J + 1))) - 1) << 8);
-                    constexpr int MN_ = J + 1 < CPT ? (0xFF | (((1 << (BPC * (J + 2))) - 1) << 8)) : 0xFFFF;
-                    cfor<0, BPC>([&](auto q) TSVGP_AI {
-                        acc[0][8 + BPC * J + decltype(q)::value] = acc_t{0, 0, 0, 0};
-                        acc[1][8 + BPC * J + decltype(q)::value] = acc_t{0, 0, 0, 0};
-                    });
-                    // (no separate variant for the end of the stream: the last chunk of the last pass fetches the saturated cursor
-                    // into a dead buffer and pre-reads fragments nobody uses -- one straight line instead of a branch with 256
-                    // live accumulators on both sides of its join)
-                    chunk(TSVGP_IC(M_), TSVGP_IC(MN_), TSVGP_IC(J & 1), gc, cd + CPT + J);
-                });
-                if (!last_tile) {
-                    const int c_last = nchunk - 1;
-                    for (int c = cd + 2 * CPT; c < c_last - 1; c += 2) {
-                        chunk(TSVGP_IC(0xFFFF), TSVGP_IC(0xFFFF), TSVGP_IC(0), gc, c);
-                        chunk(TSVGP_IC(0xFFFF), TSVGP_IC(0xFFFF), TSVGP_IC(1), gc, c + 1);
-                    }
-                    chunk(TSVGP_IC(0xFFFF), TSVGP_IC(0xFFFF), TSVGP_IC(0), gc, c_last - 1);
-                    chunk(TSVGP_IC(0xFFFF), TSVGP_IC((1 << BPC) - 1), TSVGP_IC(1), gc, c_last);
-                }
-            };
-            if constexpr (W2 == 2) {
-                if (it == 0) wide_pass(TSVGP_BC(true));
-                else wide_pass(TSVGP_BC(false));
-            } else if constexpr (TRI == TSVGP_TRI_LOWER) {
+            if constexpr (TRI == TSVGP_TRI_LOWER) {
                 if (MODE == MODE_MOMENTS && last_tile) {
                     if constexpr (MODE == MODE_MOMENTS) lower_tile(TSVGP_BC(true));
                 } else {
@@ -3349,7 +3274,9 @@ __device__ __forceinline__ void chol_inv_offdiag(double* __restrict__ S, const d
 // through the LDS image, which is dead by then, as whole row halves.  EXPERIMENT (TSVGP_POTRF_FUSE), measured and not the
 // default: one launch fewer per block step, but the substitution fed from LDS (conditional reads of the parked inverses, no
 // operand prefetch) takes longer than the panel kernel fed from `work`: 436 against 412 us at M = 1024
-// (profiles/r05_chain_ab.txt); ~150 registers per lane.
+// (profiles/r05_chain_ab.txt); ~150 registers per lane.  (Taking the experiment out was tried with the tile-dataflow diagonal kernel's
+// removal: with <true> no longer instantiated the compiler allocates <false> differently -- 87 instead of 90 VGPRs, other scalar
+// registers throughout -- and a change that only prunes leaves the instruction stream of a surviving kernel as it is.)
 template <bool FUSED>
 __global__ __launch_bounds__(CH_THREADS) void potrf_diag_kernel(double* __restrict__ A, int lda, int64_t stride, int k,
                                                                 double* __restrict__ work, int* __restrict__ info,
@@ -4049,52 +3976,6 @@ __global__ __launch_bounds__(NTHREADS) void gemv_rows_kernel(const double* __res
 }
 
 // flags[0] = sum |info_a|, flags[1] = nonpos (as is, NaN included), flags[2] = sum |info_b|   (t_SVGP._status_flags)
-// ---------------------------------------------------------------------------------------------------------------
-// Clock keeper (round 5).  The chip's clock follows its load with a time constant of several milliseconds: behind 1.5 ms of
-// the latency-bound M x M chain (a handful of workgroups at a time) the moments kernel starts near 2.05 GHz and climbs back
-// towards the 2.3-2.4 GHz it holds back-to-back -- 2.22 ms instead of 1.95 for a 125 000-row launch, 16.5 instead of 15.2 at
-// N = 1e6 (profiles/r05_clock_lab.txt, tools/clock_lab.py).  A kernel that keeps the vector ALUs of every CU issuing fp64 FMAs
-// on registers over that stretch -- one wave per SIMD, lowest priority, no memory traffic but the poll of a flag -- holds the
-// clock (1.95 ms again).  It runs on a side stream beside the chain and leaves when the main stream raises the flag in front of
-// the N-pass, or after max_ticks of the 100 MHz real-time counter, whichever comes first: every wave reaches one of the two.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NTHREADS) void clock_keeper_kernel(const int* __restrict__ flag, unsigned max_ticks) {
-    __shared__ int leave;
-    __builtin_amdgcn_s_setprio(0);
-    if (threadIdx.x == 0) leave = 0;
-    __syncthreads();
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    const bool poller = threadIdx.x < 64;  // wave 0 polls the flag (one load per workgroup and round), the others read LDS
-    double x0 = 1.0 + 1e-9 * threadIdx.x, x1 = x0 + 0.25, x2 = x0 + 0.5, x3 = x0 + 0.75;
-    const double a = 1.0 - 0x1p-40, b = 0x1p-40;
-    for (;;) {
-#pragma unroll 1
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int i = 0; i < 32; ++i) {  // 4 x 128 FMAs per lane: ~2 us of the SIMD's fp64 issue slots per round
-                x0 = __builtin_fma(x0, a, b);
-                x1 = __builtin_fma(x1, a, b);
-                x2 = __builtin_fma(x2, a, b);
-                x3 = __builtin_fma(x3, a, b);
-            }
-        }
-        if (poller) {
-            if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ||
-                __builtin_amdgcn_s_memrealtime() - t0 >= max_ticks) {
-                if (threadIdx.x == 0) __hip_atomic_store(&leave, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                break;
-            }
-        } else if (__hip_atomic_load(&leave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0 ||
-                   __builtin_amdgcn_s_memrealtime() - t0 >= max_ticks) {
-            break;
-        }
-    }
-    asm volatile("" ::"v"(x0), "v"(x1), "v"(x2), "v"(x3));
-}
-__global__ void keeper_signal_kernel(int* flag, int value) {
-    __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ void step_status_kernel(const int* __restrict__ info_a, int na, const int* __restrict__ info_b, int nb,
                                    const double* __restrict__ nonpos, double* __restrict__ flags) {
     if (threadIdx.x == 0) {
@@ -5079,22 +4960,16 @@ int trmm(const T* A, int64_t strideA, const T* Tm, int64_t strideT, T* C, int64_
     a.strideT = strideT;
     a.strideC = strideC;
     const dim3 grid((unsigned)(Np / TILE), (unsigned)batch), block(NTHREADS);
-    // (The two panel_kernel arms behind a panel1_kernel arm of the same condition are never reached.  They stay because they
-    // instantiate those kernels: without them the device code of the library would change.)
     if (mode == TSVGP_TRI_LOWER) {
         static DynLdsOptIn optin1sl;
         if (optin1sl.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), 0) != TSVGP_OK)
             return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
-    } else if (mode == TSVGP_TRI_LOWER)
-        hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
-    else if (mode == TSVGP_TRI_UPPER) {
+    } else if (mode == TSVGP_TRI_UPPER) {
         static DynLdsOptIn optin1s;  // 66 KB of static LDS
         if (optin1s.ensure(reinterpret_cast<const void*>(&panel1_kernel<T, MODE_STORE>), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_STORE>), grid, block, 0, (hipStream_t)stream, a);
-    } else if (mode == TSVGP_TRI_UPPER)
-        hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_UPPER>), grid, block, 0, (hipStream_t)stream, a);
-    else
+    } else
         hipLaunchKernelGGL((panel_kernel<T, MODE_STORE, TSVGP_TRI_DENSE>), grid, block, 0, (hipStream_t)stream, a);
     return launch_status();
 }
@@ -5257,9 +5132,7 @@ int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y
     a.mode = mode;
     a.lik = lik;
     const dim3 grid((unsigned)(Np / TILE)), block(NTHREADS);
-    // (The two fused-mean panel_kernel arms (gamma of at most 8192 bytes) stand behind a panel1_kernel arm that takes every such
-    // call and are never reached.  They stay because they instantiate those kernels: without them the device code of the library
-    // would change.  The plain panel_kernel arms serve an Mp whose gamma does not fit beside panel1_kernel's ring.)
+    // (the triangular panel_kernel arms serve an Mp whose gamma does not fit beside panel1_kernel's ring)
     if (mean_only)
         hipLaunchKernelGGL((mean_lik_kernel<T>), grid, block, (size_t)Mp * P * sizeof(T), (hipStream_t)stream, a);
     else if (mode == TSVGP_TRI_LOWER && (size_t)Mp * sizeof(T) <= P1_GAMMA_LDS_MAX) {
@@ -5269,21 +5142,14 @@ int moments(const T* A, int64_t strideA, const T* Tm, const T* gamma, const T* Y
             return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER>), grid, block, (size_t)Mp * sizeof(T),
                            (hipStream_t)stream, a);
-    } else if (mode == TSVGP_TRI_LOWER && (size_t)Mp * sizeof(T) <= 8192)
-        hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER, true>), grid, block, (size_t)Mp * sizeof(T),
-                           (hipStream_t)stream, a);
-    else if (mode == TSVGP_TRI_LOWER)
+    } else if (mode == TSVGP_TRI_LOWER)
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_LOWER>), grid, block, 0, (hipStream_t)stream, a);
     else if (mode == TSVGP_TRI_UPPER && (size_t)Mp * sizeof(T) <= P1_GAMMA_LDS_MAX) {
         // upper form: one workgroup per CU with the hand-laid instruction stream (panel1_kernel)
         static DynLdsOptIn optin1;
         if (optin1.ensure(reinterpret_cast<const void*>(&panel1_kernel<T>), P1_GAMMA_LDS_MAX) != TSVGP_OK) return TSVGP_ELAUNCH;
         hipLaunchKernelGGL((panel1_kernel<T>), grid, block, (size_t)Mp * sizeof(T), (hipStream_t)stream, a);
-    } else if (mode == TSVGP_TRI_UPPER && (size_t)Mp * sizeof(T) <= 8192)
-        // gamma fits beside the staging buffers without costing the second workgroup per CU: fused mean
-        hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_UPPER, true>), grid, block, (size_t)Mp * sizeof(T),
-                           (hipStream_t)stream, a);
-    else if (mode == TSVGP_TRI_UPPER)
+    } else if (mode == TSVGP_TRI_UPPER)
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_UPPER>), grid, block, 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL((panel_kernel<T, MODE_MOMENTS, TSVGP_TRI_DENSE>), grid, block, 0, (hipStream_t)stream, a);
@@ -5359,30 +5225,21 @@ int site_accum_slots() {
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
     if (sizeof(T) == 8) return cus;  // syrk1_kernel: one workgroup per CU by construction (512 registers per wave)
-    {  // syrk1f_kernel: what its registers and 68 KB of LDS allow
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&syrk1f_kernel), NTHREADS, 0) !=
-            hipSuccess)
-            return -1;
-        return cus * (nb > 2 ? 2 : nb < 1 ? 1 : nb);
-    }
-    // (Never reached.  The lines below stay because they are the first use of syrk_kernel<T> in this file: without them the
-    // compiler emits that kernel at another place in the code object, and the device code of the library would change.)
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&syrk_kernel<T>), NTHREADS,
-                                                     0) != hipSuccess)
+    // syrk1f_kernel: what its registers and 68 KB of LDS allow
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&syrk1f_kernel), NTHREADS, 0) != hipSuccess)
         return -1;
-    if (nb > 2) nb = 2;
-    return cus * nb;
+    return cus * (nb > 2 ? 2 : nb < 1 ? 1 : nb);
 }
 
 int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, double* work, int flags, void* stream,
           double* X = nullptr, double* Xt = nullptr, double* T = nullptr, int rhs_rows = 0) {
     if (!A || !info || !work || M <= 0 || (M % CH_NB) || lda < M || batch <= 0 ||
-        (flags & ~(TSVGP_POTRF_SUBST | TSVGP_POTRF_RHS_UPPER | TSVGP_POTRF_DIAG_V1 | TSVGP_POTRF_DIAG_V2 | TSVGP_POTRF_FUSE)) || rhs_rows < 0 || (rhs_rows % CH_NB) ||
+        (flags & ~(TSVGP_POTRF_SUBST | TSVGP_POTRF_RHS_UPPER | TSVGP_POTRF_DIAG_V1 | TSVGP_POTRF_FUSE)) || rhs_rows < 0 || (rhs_rows % CH_NB) ||
         (rhs_rows > 0 && stride < (int64_t)(M + rhs_rows) * lda))
         return TSVGP_EINVAL;
     const bool rhs_upper = (flags & TSVGP_POTRF_RHS_UPPER) != 0;
     const bool inv = X != nullptr, subst = (flags & TSVGP_POTRF_SUBST) != 0, diag_v1 = (flags & TSVGP_POTRF_DIAG_V1) != 0,
-               diag_v2 = (flags & TSVGP_POTRF_DIAG_V2) != 0, fuse = (flags & TSVGP_POTRF_FUSE) != 0;
+               fuse = (flags & TSVGP_POTRF_FUSE) != 0;
     if (inv && (!Xt || !T)) return TSVGP_EINVAL;
     const int nt = M / CH_NB;
     const size_t smem = (size_t)CH_NB * CH_LD * sizeof(double);
@@ -5413,10 +5270,8 @@ int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, doubl
         const bool panel2 = !inv && !diag_v1 && !subst;
         const int need_inverse = inv ? 1 : ((below > 0 || ext_rows > 0) && !subst) ? (panel2 ? 2 : 1) : 0;
         const int nstrips = (below * CH_NB + ext_rows) / 16;
-        const bool fused = panel2 && !diag_v2 && fuse && nstrips > 0;  // (measured slower than two launches: tsvgp_hip.h)
-        if (panel2 && diag_v2) {  // the diagonal block as an MFMA tile dataflow (tsvgp_chol.hip; experimental)
-            if (tsvgp_chol::launch_diag2(A, lda, stride, k, work, info, need_inverse, batch, st) != hipSuccess) return TSVGP_ELAUNCH;
-        } else if (fused) {  // diagonal block AND the panel rows below it in one launch
+        const bool fused = panel2 && fuse && nstrips > 0;  // (measured slower than two launches: tsvgp_hip.h)
+        if (fused) {  // diagonal block AND the panel rows below it in one launch
             const int per = CH_THREADS / 64;
             hipLaunchKernelGGL(potrf_diag_kernel<true>, dim3(batch, (nstrips + per - 1) / per), dim3(CH_THREADS), smem, st, A, lda, stride,
                                k, work, info, 2, X, Xt, M, xstride, nstrips);
@@ -5801,22 +5656,6 @@ int tsvgp_step_status_f64(const int32_t* info_a, int na, const int32_t* info_b, 
                           void* stream) {
     if (!flags || na < 0 || nb < 0 || (na > 0 && !info_a) || (nb > 0 && !info_b)) return TSVGP_EINVAL;
     hipLaunchKernelGGL(step_status_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, info_a, na, info_b, nb, nonpos, flags);
-    return launch_status();
-}
-int tsvgp_keeper_run(const int32_t* flag, double max_us, int workgroups, void* stream) {
-    if (!flag || !(max_us > 0.0) || max_us > 1.0e6 || workgroups < 0) return TSVGP_EINVAL;
-    if (workgroups == 0) {  // one workgroup of four waves per CU: one wave per SIMD
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            return TSVGP_ELAUNCH;
-        workgroups = cus;
-    }
-    hipLaunchKernelGGL(clock_keeper_kernel, dim3(workgroups), dim3(NTHREADS), 0, (hipStream_t)stream, flag, (unsigned)(max_us * 100.0));
-    return launch_status();
-}
-int tsvgp_keeper_signal(int32_t* flag, int value, void* stream) {
-    if (!flag) return TSVGP_EINVAL;
-    hipLaunchKernelGGL(keeper_signal_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, flag, value);
     return launch_status();
 }
 int tsvgp_sym_pack_f64(const double* A, int lda, int64_t stride, int M, int P, double* packed, void* stream) {

@@ -953,10 +953,6 @@ class t_SVGP(base_SVGP):
         statistics, prelude operands).  No host synchronisation."""
         warm_key = self._warm_key(X, jitter)
         eng = self._get_engine()
-        # the clock keeper bridges the M x M prelude to the N-pass (EStepEngine.keeper_begin); the epilogue has its own
-        self._keep_clock = (self.device.type == "cuda" and getattr(eng, "clock_keeper", 0) != 0
-                            and X.shape[0] * self.num_inducing >= self.KEEPER_MIN_NM)
-        keeper = eng.keeper_begin() if self._keep_clock else None
         # K(X, Z) depends on neither lambda nor the M x M factors: its fill runs on a side stream beside the prelude.
         # (Starting it only behind the two GEMMs that assemble W -- they take 130-190 us each under the fill instead of 40 --
         # measured 0.1-0.2 ms SLOWER per step, and again 36.61 vs 36.46 ms after the fill and the factorisation were reworked:
@@ -995,8 +991,6 @@ class t_SVGP(base_SVGP):
         if ops is None:
             ops = self._site_operands(whiten_jitter=jitter, warm_key=warm_key, routes=routes, fork=fork, Kzz=Kzz, K6=K6,
                                       beside_fill=pre is not None)  # a long fill is already under way: see cholesky_solve_upper
-        if keeper is not None:
-            eng.keeper_end(keeper)
         st = eng.run(X, Y, ops["Z"], self.kernel, moment_Tm=ops["moment_Tm"], prefill=pre,
                      moment_mode=ops["moment_mode"], gamma=ops["gamma"],
                      lik_id=self.likelihood.lik_id, lik_param=self.likelihood.lik_param,
@@ -1006,7 +1000,6 @@ class t_SVGP(base_SVGP):
                      mean_only=self.skip_unused_variance and self.likelihood.lik_id == B.LIK_GAUSSIAN)
         return st, ops
 
-    KEEPER_MIN_NM = int(os.environ.get("TSVGP_KEEPER_MIN_NM", "50000000"))  # N * M from which the M x M sections get a clock keeper
     FILL_INLINE_MAX_NM = int(os.environ.get("TSVGP_FILL_INLINE_MAX_NM", "0"))  # N * M up to which the fill runs in line in front of the moments
     LATE_FILL_MAX_NM = int(os.environ.get("TSVGP_LATE_FILL_MAX_NM", "300000000"))  # N * M up to which the fill starts behind W's GEMMs
 
@@ -1322,15 +1315,6 @@ class t_SVGP(base_SVGP):
         """All-reduce of the packed accumulators (RCCL) + the replicated M x M epilogue (tsvgp.py:278-303).
         Returns the status flags (device tensor, see ``_status_flags``).  ``reduced``: the already summed
         (acc2, acc1, nonpos, rows) when the caller did the collective itself (the two-graph replay)."""
-        eng = self._get_engine()
-        keeper = eng.keeper_begin() if getattr(self, "_keep_clock", False) else None  # to the next step's prelude
-        try:
-            return self._site_update_body(st, ops, lr, jitter, inplace, reduced, latents)
-        finally:
-            if keeper is not None:
-                eng.keeper_end(keeper)
-
-    def _site_update_body(self, st, ops, lr, jitter, inplace, reduced, latents):
         P, M = self.num_latent_gps, self.num_inducing
         eng = self._get_engine()
         if reduced is not None:
@@ -1341,7 +1325,7 @@ class t_SVGP(base_SVGP):
             torch.cuda.current_stream(self.device).wait_event(ops["epi_event"])
 
         G1, G0 = self._map_sums(ops, acc2, acc1)
-        # tsvgp.py:286-300 in one pass (tsvgp_site_target_f64): with lambda_2 = -1/2 L L^T the matrix to factor is
+        # tsvgp.py:286-300 in one pass (tsvgp_site_update_f64): with lambda_2 = -1/2 L L^T the matrix to factor is
         #   -2 [(1 - lr) lambda_2 + lr scale G1] + jitter I = (1 - lr) L L^T - 2 lr scale G1 + jitter I;
         # L L^T of the old factor comes from the prelude, `rows` (the global number of rows) is a device scalar: the
         # minibatch scale of :286-291 needs no synchronisation
@@ -1353,9 +1337,6 @@ class t_SVGP(base_SVGP):
             # symmetrisation, the matrix of the final factorisation, the chain rule of util.py:429-438 and the convex update of
             # lambda_1 (tsvgp.py:284-297) in ONE launch (tsvgp_site_update_f64; it was a kernel, a gemv and ~10 elementwise launches)
             target, lambda_1 = eng.site_update(G1, G0, ops["LLt"], ops["meanZ"], l1_old, lr, jitter, rows, self.num_data)
-        elif hasattr(eng, "site_target") and G1.is_cuda:
-            target, G1 = eng.site_target(G1, ops["LLt"], 1.0 - lr, -2.0 * lr, jitter, rows, self.num_data)
-            scale = (float(self.num_data) / rows) if self.num_data is not None else 1.0
         else:
             G1 = 0.5 * (G1 + G1.transpose(-1, -2))
             scale = (float(self.num_data) / rows) if self.num_data is not None else 1.0

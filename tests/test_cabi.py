@@ -41,6 +41,30 @@ def test_argument_validation_needs_no_gpu():
     assert lib.tsvgp_site_accum_work_bytes_f32(1000, 1, 15) == -1
 
 
+def test_potrf_rejects_the_removed_block_step_flag_and_no_keeper_symbol_is_exported():
+    """Bit 8 of ``flags`` selected the tile-dataflow diagonal kernel, which is gone: the three factorisation entry points return
+    TSVGP_EINVAL for it from the mask check, in front of any launch (M = 128, one matrix, real host buffers: nothing reads them).
+    Bit 16 (TSVGP_POTRF_FUSE) is still a valid selection and is exercised on the GPU (test_potrf_block_step_variants).  The clock
+    keeper's two entry points are gone too: the library exports no ``tsvgp_keeper_*`` symbol."""
+    import ctypes
+
+    B = pkg()._backend
+    lib = B.lib()
+    M = 128
+    A = (ctypes.c_double * (2 * M * M))()  # the matrix and, for potrf_solve, M right-hand-side rows below it
+    work, X, Xt, T = ((ctypes.c_double * (M * M))() for _ in range(4))
+    info = (ctypes.c_int32 * 1)()
+    ptr = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    assert B.POTRF_SUBST | B.POTRF_RHS_UPPER | B.POTRF_DIAG_V1 | B.POTRF_FUSE == 23  # bit 8 is the one no name is left for
+    for flags in (8, 8 | B.POTRF_DIAG_V1):
+        assert lib.tsvgp_potrf_f64(ptr(A), M, M, 1, M * M, ptr(info), ptr(work), flags, None) == 1
+        assert lib.tsvgp_potrf_inv_f64(ptr(A), M, M, 1, M * M, ptr(info), ptr(work), ptr(X), ptr(Xt), ptr(T), flags, None) == 1
+        assert lib.tsvgp_potrf_solve_f64(ptr(A), M, M, 1, 2 * M * M, ptr(info), ptr(work), M, flags, None) == 1
+    assert not hasattr(lib, "tsvgp_keeper_run") and not hasattr(lib, "tsvgp_keeper_signal")
+    assert not [n for n in B.exported_symbols() if "keeper" in n]
+    assert b"tsvgp_keeper_" not in open(os.environ.get("TSVGP_HIP_LIB", B.LIB_PATH), "rb").read()  # the dynamic symbol table's strings included
+
+
 def test_product_path_fails_loudly_without_gpu():
     """No CPU fallback: with no ROCm device the model refuses to run the E-step (it never routes through the oracle)."""
     import numpy as np

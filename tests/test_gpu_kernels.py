@@ -156,6 +156,71 @@ def test_moments_and_likelihood_map(engines, dtype, tol, lik, N, M, P, mode):
         assert abs(float(vep.sum()) - ve_ref) < 1e-9 * max(1.0, abs(ve_ref))
 
 
+WIDE_M = 8320  # gamma_p is 66 560 bytes in fp64: one tile beyond the 64 KiB of dynamic LDS panel1_kernel keeps it in
+
+
+@pytest.fixture(scope="module")
+def wide_moments_problem():
+    """One draw for both triangles: A [128 x 8320] (100 live rows), a dense Tm [8320 x 8320] (554 MB, drawn on the device), gamma, Y;
+    the host copies the reference is computed from."""
+    N, M = 100, WIDE_M
+    g = torch.Generator(device="cuda:0").manual_seed(17)
+    A = torch.zeros((128, M), dtype=torch.float64, device="cuda:0")
+    A[:N] = torch.randn((N, M), generator=g, dtype=torch.float64, device="cuda:0") / np.sqrt(M)
+    Tm = torch.randn((M, M), generator=g, dtype=torch.float64, device="cuda:0") / np.sqrt(M)  # q ~ 0.5 < kdiag: positive variances
+    gamma = torch.randn((M, 1), generator=g, dtype=torch.float64, device="cuda:0")
+    Y = torch.randn((N, 1), generator=g, dtype=torch.float64, device="cuda:0")
+    return dict(N=N, M=M, A=A, Tm=Tm, gamma=gamma, Y=Y, A_h=A.cpu().numpy()[:N], Tm_h=Tm.cpu().numpy(), gamma_h=gamma.cpu().numpy(),
+                Y_h=Y.cpu().numpy())
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_moments_beyond_the_gamma_lds_limit(engines, wide_moments_problem, mode):
+    """tsvgp_moments_f64 at Mp = 8320, where gamma_p (66 560 bytes) no longer fits the dynamic LDS of panel1_kernel
+    (P1_GAMMA_LDS_MAX, 64 KiB) and the launcher takes the triangular panel_kernel arms: N = 100 (one row panel with a partial tail),
+    P = 1, Gaussian likelihood, lower and upper form, against the NumPy fp64 reference of test_moments_and_likelihood_map (the same
+    sums, as one matrix product) under that test's fp64 tolerance rule.  fp32 would need Mp = 16 512 (a 1.1 GB operand and a gamma
+    that no longer fits the staging buffers either) and is left out."""
+    w = wide_moments_problem
+    eng = engines[torch.float64]
+    B = pkg()._backend
+    tol = 1e-11
+    N, M, P, Np, kdiag = w["N"], w["M"], 1, 128, 2.5
+    Tmt = (torch.triu(w["Tm"]) if mode == 1 else torch.tril(w["Tm"])).reshape(1, M, M).contiguous()
+    Tm_h = np.triu(w["Tm_h"]) if mode == 1 else np.tril(w["Tm_h"])
+    mean = torch.empty((N, P), dtype=torch.float64, device="cuda:0")
+    var = torch.empty((N, P), dtype=torch.float64, device="cuda:0")
+    g0 = torch.full((Np, P), float("nan"), dtype=torch.float64, device="cuda:0")
+    g1 = torch.full((Np, P), float("nan"), dtype=torch.float64, device="cuda:0")
+    vep = torch.zeros(Np // 128, dtype=torch.float64, device="cuda:0")
+    npp = torch.zeros(Np // 128, dtype=torch.int32, device="cuda:0")
+    assert M * 8 > 64 * 1024 and M % 128 == 0
+    B.check(eng._fn("tsvgp_moments")(w["A"].data_ptr(), Tmt.data_ptr(), w["gamma"].data_ptr(), w["Y"].data_ptr(), kdiag, B.LIK_GAUSSIAN,
+                                     0.3, mean.data_ptr(), var.data_ptr(), g0.data_ptr(), g1.data_ptr(), vep.data_ptr(), npp.data_ptr(),
+                                     N, Np, M, P, mode, eng._stream()), "moments")
+    torch.cuda.synchronize()
+    C = w["A_h"] @ Tm_h.T  # C[n, i] = sum_j A[n, j] Tm[i, j]: _moments_ref's einsum for P = 1
+    mref, vref = w["A_h"] @ w["gamma_h"], kdiag - np.sum(C * C, axis=-1)[:, None]
+    err_m, err_v = relerr(mean.cpu().numpy(), mref), np.max(np.abs(var.cpu().numpy() - vref))
+    print(f"mode {mode}: mean relerr {err_m:.3e} (< {tol * 20:.1e}), var abs err {err_v:.3e} (< {tol * 20 * kdiag:.1e}), "
+          f"var in [{vref.min():.3f}, {vref.max():.3f}]")
+    assert err_m < tol * 20
+    assert err_v < tol * 20 * kdiag
+    assert int(npp.sum()) == int(np.sum(vref <= 0))
+    ok = vref > 0
+    assert ok.all()  # the inputs are scaled for it: every row goes through the likelihood map
+    mu_k, var_k = mean.cpu().numpy(), var.cpu().numpy()
+    olik = O.Gaussian(variance=0.3)
+    r0, r1 = olik.variational_expectations_grads(mu_k, var_k, w["Y_h"])
+    r1 = np.minimum(r1, -1e-8)
+    k0, k1 = g0.cpu().numpy(), g1.cpu().numpy()
+    np.testing.assert_allclose(k0[:N], r0, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(k1[:N], r1, rtol=1e-10, atol=1e-10)
+    assert np.all(k0[N:] == 0) and np.all(k1[N:] == 0)
+    ve_ref = np.sum(olik.variational_expectations(mu_k, var_k, w["Y_h"]))
+    assert abs(float(vep.sum()) - ve_ref) < 1e-9 * max(1.0, abs(ve_ref))
+
+
 @pytest.mark.parametrize("dtype,tol", DTYPES)
 @pytest.mark.parametrize("lik", ["none", "gaussian"])
 @pytest.mark.parametrize("N,M,P", [(100, 128, 1), (300, 256, 2), (129, 384, 3), (1000, 1024, 1), (150, 1152, 8)])
@@ -592,18 +657,18 @@ def test_fill_large_input_dimension(engines, dtype, tol, kind, name, N, M, D):
     assert np.all(K[N:, :] == 0) and np.all(K[:, M:] == 0)
 
 
-@pytest.mark.parametrize("variant", ["default", "DIAG_V1", "DIAG_V2", "FUSE"])
+@pytest.mark.parametrize("variant", ["default", "DIAG_V1", "FUSE"])
 @pytest.mark.parametrize("M,batch", [(128, 1), (256, 2), (384, 3), (1024, 1)])
 def test_potrf_block_step_variants(engines, variant, M, batch):
-    """Round 5: the block step of tsvgp_potrf_f64 / tsvgp_potrf_solve_f64 in its four forms -- the default (inverted 16 x 16
+    """Round 5: the block step of tsvgp_potrf_f64 / tsvgp_potrf_solve_f64 in its three forms -- the default (inverted 16 x 16
     diagonal tiles + substitution panels on MFMA tile registers, tsvgp_chol.hip), round 4's (TSVGP_POTRF_DIAG_V1: assembled
-    128 x 128 inverse + product panels; what a call beside a long fill takes), the tile-dataflow diagonal kernel
-    (TSVGP_POTRF_DIAG_V2) and the fused diagonal + panel launch (TSVGP_POTRF_FUSE) -- against NumPy: factor, solve and
+    128 x 128 inverse + product panels; what a call beside a long fill takes) and the fused diagonal + panel launch
+    (TSVGP_POTRF_FUSE) -- against NumPy: factor, solve and
     the LAPACK index of the first non-positive pivot (reference src/util.py:376-389, src/models/tsvgp.py:270, :300)."""
     eng = engines[torch.float64]
     B = pkg()._backend
     saved = eng.potrf_flags
-    eng.potrf_flags = {"default": 0, "DIAG_V1": B.POTRF_DIAG_V1, "DIAG_V2": B.POTRF_DIAG_V2, "FUSE": B.POTRF_FUSE}[variant]
+    eng.potrf_flags = {"default": 0, "DIAG_V1": B.POTRF_DIAG_V1, "FUSE": B.POTRF_FUSE}[variant]
     try:
         rng = np.random.RandomState(11 + M)
         A = rng.randn(batch, M, M)
@@ -669,64 +734,6 @@ def test_cond2_estimate_through_the_engine(engines):
             assert abs(e - s) <= 1e-6 * s, (M, e, s)
     bad = torch.as_tensor(np.diag([1.0, -1.0, 2.0] + [1.0] * 125), device="cuda:0")
     assert np.isinf(float(U.cond2_estimate(bad, eng.cholesky)[0]))
-
-
-def test_clock_keeper_leaves_on_the_flag_and_on_its_bound(engines):
-    """tsvgp_keeper_run / tsvgp_keeper_signal (the opt-in clock keeper beside the M x M sections): its waves
-    leave when the flag is raised -- at once when it already is, within microseconds of a signal from another stream -- and
-    after max_us on their own when nobody raises it (the exit condition every wave reaches)."""
-    eng = engines[torch.float64]
-    dev = eng.device
-    lib = eng.lib
-    flag = torch.zeros(16, dtype=torch.int32, device=dev)
-    main = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    assert lib.tsvgp_keeper_signal(flag.data_ptr(), 1, main.cuda_stream) == 0
-    timed(lambda: lib.tsvgp_keeper_run(flag.data_ptr(), 50000.0, 0, main.cuda_stream))  # (first launch: code load)
-    raised = timed(lambda: lib.tsvgp_keeper_run(flag.data_ptr(), 50000.0, 0, main.cuda_stream))
-    assert int(flag[0]) == 1 and raised < 5.0, raised
-    assert lib.tsvgp_keeper_signal(flag.data_ptr(), 0, main.cuda_stream) == 0
-    bound = timed(lambda: lib.tsvgp_keeper_run(flag.data_ptr(), 3000.0, 0, main.cuda_stream))
-    assert 2.9 < bound < 8.0, bound
-    # raised from ANOTHER stream while the keeper runs: it leaves far below its bound.  (Streams and events exist before the launch:
-    # anything that synchronises the device behind a running keeper -- an allocation, a first library call loading code objects --
-    # waits for its bound, which is why the engine's default bound is 4 ms.)
-    side = torch.cuda.Stream(dev)
-    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    assert lib.tsvgp_keeper_signal(flag.data_ptr(), 0, main.cuda_stream) == 0
-    side.wait_stream(main)
-    s0.record(side)
-    assert lib.tsvgp_keeper_run(flag.data_ptr(), 200000.0, 0, side.cuda_stream) == 0
-    s1.record(side)
-    assert lib.tsvgp_keeper_signal(flag.data_ptr(), 1, main.cuda_stream) == 0
-    torch.cuda.synchronize()
-    assert s0.elapsed_time(s1) < 50.0, s0.elapsed_time(s1)
-    # through the engine: begin / end return, the keeper is gone behind end (its bound here: 20 ms)
-    old = eng.clock_keeper, eng.keeper_max_us
-    eng.clock_keeper, eng.keeper_max_us = -1, 20000.0
-    try:
-        t = eng.keeper_begin()
-        assert t is not None
-        eng.keeper_end(t)
-        torch.cuda.synchronize()
-        assert t.query()
-        eng.clock_keeper = 0
-        assert eng.keeper_begin() is None
-    finally:
-        eng.clock_keeper, eng.keeper_max_us = old
-    for bad in (lambda: lib.tsvgp_keeper_run(None, 10.0, 0, None), lambda: lib.tsvgp_keeper_run(flag.data_ptr(), 0.0, 0, None),
-                lambda: lib.tsvgp_keeper_run(flag.data_ptr(), 2.0e6, 0, None), lambda: lib.tsvgp_keeper_signal(None, 1, None)):
-        assert bad() == 1  # TSVGP_EINVAL
 
 
 def test_tri_copy_shift_and_the_runs_form_of_factor_and_solve(engines):

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""(CPU) Lane-level NumPy emulation of the 128 x 128 diagonal-block Cholesky kernel `potrf_diag2_kernel`
-(t-svgp_amd/csrc/tsvgp_chol.hip): every 16 x 16 tile lives in the accumulator layout of v_mfma_f64_16x16x4_f64,
+"""(CPU) Lane-level NumPy emulation of the 128 x 128 diagonal-block Cholesky kernel `potrf_diag2_kernel` (measured slower than
+potrf_diag_kernel and removed from t-svgp_amd/csrc/tsvgp_chol.hip: profiles/r05_potrf_diag_lab.txt, code in git history) and of the
+panel kernel chol_panel2_kernel, which stays: every 16 x 16 tile lives in the accumulator layout of v_mfma_f64_16x16x4_f64,
     lane (n = l & 15, G = l >> 4), register r  <->  T[n][4 r + G],
 and every step of the factorisation is an MFMA whose operands are registers of other tiles as they stand (see the
 kernel's header).  The emulation follows the kernel wave by wave and barrier by barrier: LDS writes of a wave become
 visible to the OTHER waves only at the next barrier (a read of a word another wave wrote since the last barrier, or a
 word two waves wrote in one interval, raises) -- so it checks the index algebra (slot maps, row ownership, the
-progressive look-ahead, the trailing jobs) AND the placement of the barriers.  Run it before touching the kernel.
+progressive look-ahead, the trailing jobs) AND the placement of the barriers.
 usage: emul_diag2.py [seed]"""
 import sys
 import numpy as np

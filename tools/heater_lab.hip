@@ -1,7 +1,7 @@
 // heater_lab.hip -- round 5, verdict item 4 (the moments kernel's clock tax): does the clock the chip holds under the MFMA kernels
 // drop over a ~1.5 ms stretch of latency-bound launches, and does a kernel that keeps the matrix pipes busy over that stretch hold
 // it?  Two kernels bounded by the 100 MHz real-time counter: lab_sleep (one wave asleep) and lab_heat (nwg workgroups of four waves
-// chaining v_mfma_f64_16x16x4_f64, or fp64 FMAs, on registers).  Built on the GPU box by tools/clock_lab.py.
+// chaining v_mfma_f64_16x16x4_f64, or fp64 FMAs, on registers).  Its driver script went with the clock keeper (code in git history).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -21,18 +21,17 @@ for a, b in zip(mom[:-1], mom[1:]):
     seg = rows[a:b]
     acc = [r for r in seg if "syrk1" in name(r) or "syrk_kernel" in name(r)]
     red = [r for r in seg if "syrk_reduce" in name(r)]
-    keep = [r for r in seg if "clock_keeper" in name(r)]
     if not acc or not red:
         continue
     t_red = E(red[-1])
     per.append(dict(period=(S(rows[b]) - S(rows[a])) / 1e3, moments=(E(rows[a]) - S(rows[a])) / 1e3,
                     accum=sum(E(r) - S(r) for r in acc) / 1e3, mxm=(S(rows[b]) - t_red) / 1e3,
-                    npass=(t_red - S(rows[a])) / 1e3, keeper=sum(E(r) - S(r) for r in keep) / 1e3, nk=len(seg)))
+                    npass=(t_red - S(rows[a])) / 1e3, nk=len(seg)))
     for r in seg:
-        if S(r) >= t_red and "clock_keeper" not in name(r):
+        if S(r) >= t_red:
             d = agg.setdefault(short(name(r)), [0, 0.0]); d[0] += 1; d[1] += (E(r) - S(r)) / 1e3
 print(f"{len(per)} steps; mean (min .. max) in us")
-for k in ("period", "npass", "moments", "accum", "mxm", "keeper", "nk"):
+for k in ("period", "npass", "moments", "accum", "mxm", "nk"):
     v = np.array([p[k] for p in per])
     print(f"  {k:8s} {v.mean():9.1f}  ({v.min():.1f} .. {v.max():.1f})")
 print("kernels of the M x M sections, per step:")
