@@ -533,6 +533,31 @@ int tsvgp_kernel_grad_f32(int kind, const float *X, const float *Z, const float 
                           int64_t ldu, const float *g0, const float *g1, int gstride, const float *beta, int bstride,
                           int64_t N, int M, int D, double *zpart, double *lpart, double *vpart, void *stream);
 
+/* (9) Greedy conditional-variance selection of inducing points (Burt, Rasmussen, van der Wilk 2020, "ConditionalVariance"; [ext]:
+ *     nothing in the reference chooses Z): pivoted Cholesky of K(X, X) that always takes the row with the largest residual prior
+ *     variance.  With k = variance * f_kind(r) exactly as tsvgp_kernel_fill_* (same device functions, D <= 32), d[n] = variance:
+ *        for j in 0 .. M-1:
+ *            p = the lowest n with d[n] == max(d);   stop unless d[p] > floor      (count = j)
+ *            c = (k(X, x_p) - sum_{i<j} C[i, :] * C[i, p]) / sqrt(d[p])
+ *            C[j, :] = c;   d = max(d - c * c, 0);   d[p] = 0;   indices[j] = p;   pivots[j] = d[p] as found
+ *     X [N x D] row-major, inv_ls [D].  C [M x ldc]: the factor TRANSPOSED (row j = the j-th Cholesky column over n), ldc >= Np = N
+ *     rounded up to 128 and even; columns n in [N, Np) are written as 0, columns >= Np are not touched, rows >= count neither.
+ *     d [Np]: on return the residual conditional variance diag(K_ff - K_fS K_SS^-1 K_Sf) for n < N (exactly 0 at every picked
+ *     row), 0 beyond.  indices, pivots [M]: entries [0, count) are written.  count: one device int.  C and d on 16-byte
+ *     boundaries; work: tsvgp_greedy_select_work_bytes(N, M) bytes on an 8-byte boundary (-1: N < 1, M < 1 or N beyond 128 * (2^31 - 1)).
+ *     N >= 1, M >= 1 (M > N is allowed: the selection stops at count <= N), variance > 0, floor finite and >= 0 -- the caller
+ *     passes max(threshold, 1e-12 * variance): below that a residual is rounding noise of the subtraction, and a duplicate row
+ *     must not be taken with a pivot of 1e-17.
+ *     The call enqueues 2 M launches on `stream` (one grid over n that extends the factor, one workgroup that reduces the
+ *     per-workgroup maxima and gathers the next pivot's factor entries) and reads nothing back: the steps behind the stop
+ *     condition return at once on a device flag.  No workgroup waits for another.  HBM bound on the read of the rows of C
+ *     built so far, 8 Np count^2 / 2 bytes in all.  The dot product's summation order depends on j alone: two calls agree bit for
+ *     bit, and identical rows of X get identical columns of C. */
+int64_t tsvgp_greedy_select_work_bytes(int64_t N, int M);
+int tsvgp_greedy_select_f64(int kind, const double *X, const double *inv_ls, double variance, double floor, double *C, int64_t ldc,
+                            double *d, int64_t *indices, double *pivots, int32_t *count, void *work, int64_t N, int M, int D,
+                            void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

@@ -190,6 +190,9 @@ _PROTOTYPES = {
     "tsvgp_step_status_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "tsvgp_sym_pack_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tsvgp_sym_unpack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_greedy_select_work_bytes": (c_int64, [c_int64, c_int]),
+    "tsvgp_greedy_select_f64": (c_int, [c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

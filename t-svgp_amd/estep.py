@@ -1529,3 +1529,44 @@ class EStepEngine:
         cols = size // (nt * (nt + 1) // 2 + 1)
         total = part[size - cols:]
         return total[0].clone(), total[1:1 + D] * inv_ls
+
+    def greedy_select(self, X, kernel, M: int, threshold: float = 0.0):
+        """Greedy conditional-variance selection of at most M rows of X as inducing points (``tsvgp_greedy_select_f64``):
+        pivoted Cholesky of K(X, X) that always takes the row with the largest residual prior variance and stops when that
+        falls to ``floor = max(threshold, 1e-12 * variance)`` or below.  X [N, D <= 32] on this device (converted to fp64 when
+        it is not: the arithmetic is fp64 whatever the engine's compute dtype), ``kernel`` one stationary kernel.
+
+        Allocates the transposed factor C [M, Np] fp64 for the length of the call -- 8 M Np bytes, 8.4 GB at N = 1e6,
+        M = 1024 -- plus d [Np] and the outputs; makes the one call (2 M launches, no host read between them) and reads
+        ``count`` back once.  Returns ``(indices [count] int64, pivots [count], d [N], count)``, tensors on the device:
+        d is the residual conditional variance diag(K_ff - K_fS K_SS^-1 K_Sf), exactly 0 at every picked row."""
+        if isinstance(kernel, SeparateIndependent):
+            raise ValueError("greedy_select: one kernel defines one conditional variance; pass the latent's kernel you mean")
+        if X.dim() != 2 or X.shape[0] < 1:
+            raise ValueError("greedy_select: X must be [N >= 1, D]")
+        N, D = X.shape
+        M = int(M)
+        if M < 1:
+            raise ValueError(f"greedy_select: M >= 1, got {M}")
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"greedy_select: 1 <= D <= {MAX_INPUT_DIM}, got {D}")
+        variance = kernel.variance.item()
+        floor = max(float(threshold), 1e-12 * variance)
+        X = X.to(device=self.device, dtype=torch.float64).contiguous()
+        Np = B.round_up(N)
+        nbytes = int(self.lib.tsvgp_greedy_select_work_bytes(N, M))
+        if nbytes <= 0:
+            raise ValueError(f"greedy_select: no workspace layout for N = {N}, M = {M}")
+        inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
+        C = torch.empty((M, Np), dtype=torch.float64, device=self.device)
+        d = torch.empty((Np,), dtype=torch.float64, device=self.device)
+        indices = torch.zeros((M,), dtype=torch.int64, device=self.device)
+        pivots = torch.zeros((M,), dtype=torch.float64, device=self.device)
+        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        work = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_greedy_select", lambda: self.lib.tsvgp_greedy_select_f64(
+                int(kernel.kind), X.data_ptr(), inv_ls.data_ptr(), variance, floor, C.data_ptr(), Np, d.data_ptr(),
+                indices.data_ptr(), pivots.data_ptr(), count.data_ptr(), work.data_ptr(), N, M, D, self._stream()))
+        n = int(count.item())  # the one device -> host read (it also keeps C alive until the launches are through)
+        return indices[:n], pivots[:n], d[:N], n
