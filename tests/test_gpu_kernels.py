@@ -347,7 +347,8 @@ def test_site_accum_rejects_misaligned_operands(engines):
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("M,P,num_data", [(96, 1, None), (200, 3, 5000.0), (1024, 1, 1.0e6), (33, 2, 77.0)])
+@pytest.mark.parametrize("M,P,num_data", [(96, 1, None), (200, 3, 5000.0), (1024, 1, 1.0e6), (33, 2, 77.0),
+                                           (200, 10, 5000.0), (33, 10, None)])  # ten latents: the multiclass chain
 def test_site_update_and_target_kernels(engines, M, P, num_data):
     """``tsvgp_site_update_f64`` (one launch: symmetrised G1 -> the matrix of the final factorisation, the chain rule of reference
     src/util.py:429-438 and the convex update of lambda_1, src/models/tsvgp.py:284-297) and ``tsvgp_site_target_f64`` against
@@ -373,7 +374,7 @@ def test_site_update_and_target_kernels(engines, M, P, num_data):
     assert relerr(tt.cpu().numpy(), want_t) < 1e-14 and relerr(Gsym.cpu().numpy(), Gs) < 1e-15
 
 
-@pytest.mark.parametrize("M,P", [(96, 1), (200, 3), (1024, 1), (33, 2), (1, 1)])
+@pytest.mark.parametrize("M,P", [(96, 1), (200, 3), (1024, 1), (33, 2), (1, 1), (200, 10), (33, 10)])
 def test_site_beta_kernel(engines, M, P):
     """``tsvgp_site_beta_f64``: beta = l1 - D^T (D v) with D upper triangular (what lies below the diagonal is never read) --
     K^-1 m of reference src/util.py:176-179 -- against NumPy; repeated launches bit-identical."""
@@ -400,7 +401,7 @@ def test_invalid_arguments_are_rejected(engines):
 
 
 @pytest.mark.parametrize("robust", [False, True])
-@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (200, 2), (33, 1)])
+@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (200, 2), (33, 1), (256, 10), (200, 10)])
 def test_potrf(engines, M, batch, robust):
     """Blocked Cholesky (tsvgp_potrf_f64) vs LAPACK, with the panels solved by the inverted diagonal block (default) and
     by substitution (TSVGP_POTRF_SUBST); non-positive-definite input reports info like potrf."""
@@ -441,7 +442,7 @@ def test_potrf_substitution_panels_on_a_barely_definite_matrix(engines, M):
     assert np.max(np.abs(X @ Ln - np.eye(M))) < 1e-6
 
 
-@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (640, 2), (1536, 1), (200, 2), (33, 1)])
+@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (640, 2), (1536, 1), (200, 2), (33, 1), (256, 10), (200, 10)])
 def test_potrf_inverse(engines, M, batch):
     """tsvgp_potrf_inv_f64: the factor and its inverse (2x2 block recursion on the inverted diagonal blocks), also for
     block counts that are not powers of two."""
@@ -461,7 +462,7 @@ def test_potrf_inverse(engines, M, batch):
 
 
 @pytest.mark.parametrize("robust", [False, True])
-@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (640, 2), (200, 2), (33, 1)])
+@pytest.mark.parametrize("M,batch", [(128, 1), (256, 3), (1024, 1), (640, 2), (200, 2), (33, 1), (256, 10), (200, 10)])
 def test_potrf_solve_upper(engines, M, batch, robust):
     """tsvgp_potrf_solve_f64 + tsvgp_flip_transpose_f64 (``EStepEngine.cholesky_solve_upper``): the upper-form factor A = U U^T and
     D = U^-1 L^T for a lower triangular L in ONE pass (the right-hand side rides through the factorisation as panel rows) --
@@ -692,7 +693,7 @@ def test_potrf_block_step_variants(engines, variant, M, batch):
         eng.potrf_flags = saved
 
 
-@pytest.mark.parametrize("M,P,shared", [(64, 1, True), (200, 3, True), (1024, 2, False)])
+@pytest.mark.parametrize("M,P,shared", [(64, 1, True), (200, 3, True), (1024, 2, False), (200, 10, True), (256, 10, False)])
 def test_gemv_rows(engines, M, P, shared):
     """tsvgp_gemv_f64 (``EStepEngine.gemv``): y[:, p] = A_p v[:, p], one matrix for every latent or one per latent -- the
     matrix-vector products of the replicated chain ((K_uu + 1e-6 I) lambda_1, K_uu beta: reference src/util.py:176-179,

@@ -236,6 +236,61 @@ def test_fp32_against_fp64_oracle(kind):
     assert abs(e_h - e_o) <= 1e-4 + 1e-3 * abs(e_o)
 
 
+# Ten classes and more than one tile: M = 150 pads to Mp = 256 -- two diagonal tiles and an off-diagonal one in the site sums, which
+# above eight latents run in syrk_kernel<T>; with separate kernels the latent-batched entries carry P = 10.
+N10_, M10_, C10_, D10_ = 300, 150, 10, 7
+
+
+def _ten_class_problem(kind, projection, **kw):
+    """``problem`` at D = 7 and the pair of ``pair``: 150 inducing points spread over [-2, 2]^7 keep cond(K_uu + jitter I) <= 1e4 for
+    every latent's kernel (NumPy on the CPU: 81 for the shared Matern-5/2, 35 .. 2.9e3 for the ten SE kernels of lengthscale
+    1.2 .. 2.1; at D = 6 the last of them is at 1.5e4), which the 1e-8 bound of ``_compare_state`` assumes.  All ten classes occur."""
+    from oracle import tsvgp_oracle as O
+
+    X, Y, Z = problem(N=N10_, M=M10_, D=D10_, C=C10_, seed=0)
+    assert set(Y[:, 0]) == set(range(C10_))
+    hip, ora = pair(Z, C10_, kind, projection=projection, **kw)
+    if kind == "perlatent":
+        hip._get_engine().batch_separate = False
+    kernels = [ora.kernel] if kind == "shared" else ora.kernel.kernels
+    conds = [float(np.linalg.cond(k.K(Z, Z) + O.DEFAULT_JITTER * np.eye(M10_))) for k in kernels]
+    print(f"robustmax C=10 {kind}: cond(K_uu + jitter I) per kernel " + " ".join(f"{c:.2e}" for c in conds))
+    assert max(conds) <= 1e4
+    return X, Y, hip, ora
+
+
+@pytest.mark.parametrize("projection", ["direct", "whitened"])
+@pytest.mark.parametrize("kind", ["shared", "separate", "perlatent"])
+def test_ten_classes_on_two_tiles_match_oracle(kind, projection):
+    X, Y, hip, ora = _ten_class_problem(kind, projection, num_data=N10_)
+    assert hip._routes(1e-9) == [projection] * C10_
+    assert pkg()._backend.round_up(M10_) == 256 and C10_ > 8
+    for _ in range(3):
+        hip.natgrad_step((X, Y), lr=0.5)
+        ora.natgrad_step((X, Y), lr=0.5)
+        _compare_state(hip, ora, 1e-8)
+    if kind != "shared":
+        assert hip._get_engine().last_batched == (kind == "separate")
+    e_h, e_o = float(hip.elbo((X, Y))), float(ora.elbo((X, Y)))
+    print(f"robustmax C=10 {kind} {projection}: elbo {e_h:.10f} oracle {e_o:.10f}")
+    assert abs(e_h - e_o) < 1e-9 * abs(e_o)
+    assert float(hip.elbo((X, Y))) == e_h  # nothing is drawn: the same number again
+
+
+def test_ten_classes_on_two_tiles_fp32_against_fp64_oracle():
+    X, Y, hip, ora = _ten_class_problem("separate", "whitened", compute_dtype=torch.float32)
+    for _ in range(3):
+        hip.natgrad_step((X, Y), lr=0.5)
+        ora.natgrad_step((X, Y), lr=0.5)
+    mu_h, var_h = hip.predict_f(X)
+    mu_o, var_o = ora.predict_f(X)
+    np.testing.assert_allclose(mu_h.cpu().numpy(), mu_o, rtol=1e-3, atol=1e-4)
+    np.testing.assert_allclose(var_h.cpu().numpy(), var_o, rtol=1e-3, atol=1e-4)
+    e_h, e_o = float(hip.elbo((X, Y))), float(ora.elbo((X, Y)))
+    print(f"robustmax C=10 fp32 separate: elbo {e_h:.6f} oracle {e_o:.6f}")
+    assert abs(e_h - e_o) <= 1e-4 + 1e-3 * abs(e_o)
+
+
 def test_minibatch_step_with_num_data_rescaling():
     X, Y, Z = problem(N=N_, M=M_, seed=3)
     hip, ora = _gpu_pair(Z, "shared", num_data=N_)
