@@ -367,9 +367,11 @@ int tsvgp_site_accum_batched_f32(const float *B, int64_t strideB, const float *g
 /* (6) Batched lower Cholesky of the M x M site matrices, in place:  A[b] = L[b] L[b]^T, L written to the lower triangle
  *     of the 128x128 diagonal blocks and below (the strictly upper part of the diagonal blocks is zeroed; blocks above
  *     the diagonal are left untouched).  Replaces tf.linalg.cholesky of reference src/models/tsvgp.py:270,300 and
- *     src/util.py:377-388.  M must be a multiple of 128 (pad with an identity block), lda >= M, matrix b starts at
- *     A + b*stride.  info[b] = 0, or the 1-based index of the first non-positive pivot (LAPACK potrf convention).
- *     work: batch * 128 * 128 doubles. */
+ *     src/util.py:377-388.  M must be a multiple of 128 (pad with an identity block), lda >= M and even, A on a 16-byte
+ *     boundary (16-byte row accesses), matrix b starts at A + b*stride; with batch > 1 stride even and >= M * lda (the
+ *     matrices are factored side by side and must not overlap; batch == 1 does not read stride).  Anything else is
+ *     TSVGP_EINVAL before any launch.  info[b] = 0, or the 1-based index of the first non-positive pivot (LAPACK potrf
+ *     convention; a NaN pivot counts as non-positive).  work: batch * 128 * 128 doubles, on a 16-byte boundary like A. */
 #define TSVGP_POTRF_SUBST 1 /* flags: solve the panels below each diagonal block by substitution against L_kk (16-wide
                                sub-blocks by forward substitution, the rest by MFMA updates, as LAPACK's blocked trsm)
                                instead of multiplying by inv(L_kk): ~0.15 ms slower at M = 1024, but as robust as a
@@ -385,7 +387,8 @@ int tsvgp_potrf_f64(double *A, int M, int lda, int batch, int64_t stride, int32_
                     void *stream);
 
 /* (6a) Factor AND solve in one pass: the buffer of matrix b holds, directly below its M rows, `rhs_rows` further rows B
- *     [rhs_rows x M] (same lda; stride >= (M + rhs_rows) * lda).  They ride through the factorisation as panel rows -- every
+ *     [rhs_rows x M] (same lda, even; A on a 16-byte boundary; stride >= (M + rhs_rows) * lda for every batch, and even with
+ *     batch > 1; TSVGP_EINVAL otherwise, before any launch).  They ride through the factorisation as panel rows -- every
  *     block step solves them against the diagonal block and applies the trailing update to them with the same tile kernels --
  *     and come out as  B L^-T  (= (L^-1 B^T)^T: the triangular solve of reference src/util.py:173, D = chol(W)^-1 L^T, without
  *     the inverse factor of (6b), its recursion levels and the GEMM that applied it).  rhs_rows a multiple of 128.
@@ -453,7 +456,8 @@ int tsvgp_vgp_kernel_grad_f64(int kind, const double *X, const double *inv_ls, d
  *     solve needs anyway are combined by the 2x2 block recursion inv([[A,0],[C,B]]) = [[A^-1,0],[-B^-1 C A^-1, B^-1]]
  *     as MFMA tile products.  Replaces tf.linalg.triangular_solve / cholesky_solve with M x M right-hand sides
  *     (reference src/util.py:168-175, src/models/tsvgp.py:270-271): the callers apply X by GEMM.
- *     T: scratch, batch * M * M doubles.  Other arguments as tsvgp_potrf_f64. */
+ *     T: scratch, batch * M * M doubles.  X, Xt and T on 16-byte boundaries.  Other arguments as tsvgp_potrf_f64: lda even, A on a
+ *     16-byte boundary, with batch > 1 stride even and >= M * lda; TSVGP_EINVAL otherwise, before any launch. */
 int tsvgp_potrf_inv_f64(double *A, int M, int lda, int batch, int64_t stride, int32_t *info, double *work, double *X,
                         double *Xt, double *T, int flags, void *stream);
 

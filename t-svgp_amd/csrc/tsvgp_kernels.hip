@@ -5239,10 +5239,17 @@ int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, doubl
         (flags & ~(TSVGP_POTRF_SUBST | TSVGP_POTRF_RHS_UPPER | TSVGP_POTRF_DIAG_V1 | TSVGP_POTRF_FUSE)) || rhs_rows < 0 || (rhs_rows % CH_NB) ||
         (rhs_rows > 0 && stride < (int64_t)(M + rhs_rows) * lda))
         return TSVGP_EINVAL;
+    // every kernel below moves rows with 16-byte accesses at A + b*stride + r*lda + c (c even); the matrices of a batch are
+    // factored side by side and must not overlap
+    // (`work` is read the same way by the round-4 panel product, T by the inverse recursion)
+    if ((lda % 2) || ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(work)) & 15) ||
+        (batch > 1 && ((stride % 2) || stride < (int64_t)(M + rhs_rows) * lda)))
+        return TSVGP_EINVAL;
     const bool rhs_upper = (flags & TSVGP_POTRF_RHS_UPPER) != 0;
     const bool inv = X != nullptr, subst = (flags & TSVGP_POTRF_SUBST) != 0, diag_v1 = (flags & TSVGP_POTRF_DIAG_V1) != 0,
                fuse = (flags & TSVGP_POTRF_FUSE) != 0;
-    if (inv && (!Xt || !T)) return TSVGP_EINVAL;
+    if (inv && (!Xt || !T || ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xt) | reinterpret_cast<uintptr_t>(T)) & 15)))
+        return TSVGP_EINVAL;
     const int nt = M / CH_NB;
     const size_t smem = (size_t)CH_NB * CH_LD * sizeof(double);
     static DynLdsOptIn optin;
@@ -5252,7 +5259,6 @@ int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, doubl
     hipStream_t st = (hipStream_t)stream;
     const int64_t xstride = (int64_t)M * M;
     if (inv) {  // the blocks the recursion does not write stay zero
-        if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xt)) & 15) return TSVGP_EINVAL;
         zero_fill(X, sizeof(double) * xstride * batch, st);
         zero_fill(Xt, sizeof(double) * xstride * batch, st);
     }

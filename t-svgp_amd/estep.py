@@ -421,7 +421,8 @@ class EStepEngine:
                 W = Wp
         elif Mp == M:  # no padding: one copy (or none) instead of a zero fill plus a copy
             W = A.reshape(nb, M, M)
-            if not (overwrite and W.is_contiguous() and W.data_ptr() == A.data_ptr()):
+            # (a contiguous view at an odd element offset of its storage is not on the 16-byte boundary the kernels need: copy it)
+            if not (overwrite and W.is_contiguous() and W.data_ptr() == A.data_ptr() and W.data_ptr() % 16 == 0):
                 W = W.clone(memory_format=torch.contiguous_format)
         else:
             W = torch.zeros((nb, Mp, Mp), dtype=torch.float64, device=self.device)

@@ -59,6 +59,26 @@ def make_pair(Z, lik="gaussian", noise=0.1, lengthscales=1.0, variance=1.0, P=1,
     return hip, ora
 
 
+def potrf_layout_cases(M, rhs_rows=0):
+    """Layout arguments of the three ``tsvgp_potrf*_f64`` entries at the edge of what they accept: (name, accepted, rejected),
+    two dicts of (lda, off, batch, stride) that differ in ONE argument.  ``off``: the matrix starts that many doubles behind a
+    16-byte boundary.  tests/test_cabi.py calls the rejected ones (host buffers, nothing launches), tests/test_gpu_chol_family.py
+    runs the accepted ones."""
+    rows = M + rhs_rows
+    # (the base stride is that of the widest lda below, M + 4 > M + 3, so that the odd lda breaks the evenness rule alone)
+    base = dict(lda=M + 2, off=0, batch=2, stride=(rows + 2) * (M + 4))
+    cases = [("odd lda", {}, dict(lda=M + 3)),
+             ("A off the 16-byte boundary", dict(off=2), dict(off=1)),
+             ("odd stride in a batch", {}, dict(stride=base["stride"] + 1)),
+             ("overlapping matrices of a batch", dict(stride=rows * (M + 2)), dict(stride=rows * (M + 2) - 2))]
+    return [(name, {**base, **ok}, {**base, **ok, **bad}) for name, ok, bad in cases]
+
+
+# The other buffers of the same entries (work; X, Xt, T of tsvgp_potrf_inv_f64) are moved with 16-byte accesses too: doubles between
+# the 16-byte boundary and the pointer, (accepted, rejected) -- the same two tests.
+POTRF_AUX_OFF = (2, 1)
+
+
 def relerr(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)

@@ -65,6 +65,57 @@ def test_potrf_rejects_the_removed_block_step_flag_and_no_keeper_symbol_is_expor
     assert b"tsvgp_keeper_" not in open(os.environ.get("TSVGP_HIP_LIB", B.LIB_PATH), "rb").read()  # the dynamic symbol table's strings included
 
 
+@pytest.mark.parametrize("entry", ["potrf", "potrf_solve", "potrf_inv"])
+def test_potrf_rejects_layouts_its_16_byte_row_accesses_cannot_take(entry):
+    """The kernels behind the three factorisation entries move rows with 16-byte loads and stores at A + b*stride + r*lda + c and
+    factor the matrices of a batch side by side: an odd lda, an A off the 16-byte boundary, an odd stride in a batch and a stride
+    that lets two matrices of a batch overlap, and a work, X, Xt or T off the boundary, are TSVGP_EINVAL in front of any launch
+    (real host buffers, every pointer non-NULL: nothing reads them).  Each rejected call differs in ONE argument from a call the entry accepts (tests.helpers.
+    potrf_layout_cases); that the accepted ones run and give the right factor is tests/test_gpu_chol_family.py's part.  One matrix
+    keeps taking any stride when no rows ride along (the call in test_argument_validation_needs_no_gpu passes 0)."""
+    import ctypes
+
+    from tests.helpers import POTRF_AUX_OFF, potrf_layout_cases
+
+    lib = pkg()._backend.lib()
+    M = 128
+    rhs_rows = M if entry == "potrf_solve" else 0
+    aligned = lambda a: (ctypes.addressof(a) + 15) // 16 * 16
+    work, X, Xt, T = ((ctypes.c_double * (2 * M * M + 2))() for _ in range(4))
+    info = (ctypes.c_int32 * 2)()
+
+    def call(lda, off, batch, stride):
+        A = (ctypes.c_double * (batch * stride + 8))()
+        a = aligned(A) + 8 * off
+        if entry == "potrf":
+            return lib.tsvgp_potrf_f64(a, M, lda, batch, stride, ctypes.addressof(info), aligned(work), 0, None)
+        if entry == "potrf_solve":
+            return lib.tsvgp_potrf_solve_f64(a, M, lda, batch, stride, ctypes.addressof(info), aligned(work), rhs_rows, 0, None)
+        return lib.tsvgp_potrf_inv_f64(a, M, lda, batch, stride, ctypes.addressof(info), aligned(work), aligned(X), aligned(Xt),
+                                       aligned(T), 0, None)
+
+    cases = potrf_layout_cases(M, rhs_rows)
+    assert len(cases) == 4
+    for name, ok, bad in cases:
+        assert sum(ok[key] != bad[key] for key in ok) == 1, name  # the neighbour differs in that one argument
+        assert ok["lda"] % 2 == 0 and ok["off"] % 2 == 0 and ok["stride"] % 2 == 0 and ok["stride"] >= (M + rhs_rows) * ok["lda"], name
+        assert call(**bad) == 1, f"{entry}: {name} was not rejected"
+    # work (and X, Xt, T of the inverse path) are moved the same way: each one 8 bytes off the boundary, on the first accepted layout
+    lay = cases[0][1]
+    A = (ctypes.c_double * (lay["batch"] * lay["stride"] + 8))()
+    a, inf = aligned(A), ctypes.addressof(info)
+    assert POTRF_AUX_OFF[0] % 2 == 0 and POTRF_AUX_OFF[1] % 2 == 1
+    bump = 8 * POTRF_AUX_OFF[1]
+    if entry == "potrf":
+        assert lib.tsvgp_potrf_f64(a, M, lay["lda"], lay["batch"], lay["stride"], inf, aligned(work) + bump, 0, None) == 1
+    elif entry == "potrf_solve":
+        assert lib.tsvgp_potrf_solve_f64(a, M, lay["lda"], lay["batch"], lay["stride"], inf, aligned(work) + bump, rhs_rows, 0, None) == 1
+    else:
+        for which in range(4):
+            w, x, xt, t = (aligned(buf) + (bump if i == which else 0) for i, buf in enumerate((work, X, Xt, T)))
+            assert lib.tsvgp_potrf_inv_f64(a, M, lay["lda"], lay["batch"], lay["stride"], inf, w, x, xt, t, 0, None) == 1, which
+
+
 def test_product_path_fails_loudly_without_gpu():
     """No CPU fallback: with no ROCm device the model refuses to run the E-step (it never routes through the oracle)."""
     import numpy as np
