@@ -112,6 +112,10 @@ def test_moments_and_likelihood_map(engines, dtype, tol, lik, N, M, P, mode):
     Np = B.round_up(N)
     A = np.zeros((Np, M))
     A[:N] = rng.randn(N, M) / np.sqrt(M)
+    # rows 0..39 keep q of about M / 4 (M / 8 in the triangular forms), far above kdiag: non-positive variances, which are counted;
+    # the rows from 40 on are scaled to q of about 1 (0.5), so that kdiag - q is positive and the likelihood map below is checked
+    # on them (with every row at the first scale ``ok`` was empty and the map's assertions held vacuously)
+    A[40:N] *= 2.0 / np.sqrt(M)
     Tm = rng.randn(P, M, M) * 0.5
     if mode == 1:
         Tm = np.triu(Tm)
@@ -154,6 +158,19 @@ def test_moments_and_likelihood_map(engines, dtype, tol, lik, N, M, P, mode):
     if ok.all():
         ve_ref = np.sum(olik.variational_expectations(mu_k, var_k, Y))
         assert abs(float(vep.sum()) - ve_ref) < 1e-9 * max(1.0, abs(ve_ref))
+    assert ok[40:].all() and not ok[:40].any()
+    # block by block: the counts of non-positive variances, and ve over a block's own rows (entry bound ltol (1 + |ve|), summed
+    # over the block: a partial written to another block keeps the total and fails here).  The Gaussian ve is defined for any
+    # variance; the Bernoulli one for the blocks behind row 39
+    starts = np.arange(0, N, 128)
+    assert np.array_equal(npp.cpu().numpy(), np.add.reduceat((vref <= 0).sum(axis=1), starts))
+    v_ve = var_k if lik == "gaussian" else vs
+    blk_ok = np.ones(len(starts), bool) if lik == "gaussian" else np.add.reduceat((~ok).sum(axis=1), starts) == 0
+    assert blk_ok.sum() >= len(starts) - 1
+    ve_entries = olik.variational_expectations(mu_k[..., None], v_ve[..., None], Y[..., None])
+    blk_err = np.abs(vep.cpu().numpy() - np.add.reduceat(ve_entries.sum(axis=1), starts))
+    blk_tol = ltol * np.add.reduceat((1 + np.abs(ve_entries)).sum(axis=1), starts)
+    assert np.all(blk_err[blk_ok] <= blk_tol[blk_ok])
 
 
 WIDE_M = 8320  # gamma_p is 66 560 bytes in fp64: one tile beyond the 64 KiB of dynamic LDS panel1_kernel keeps it in
