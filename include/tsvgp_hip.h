@@ -90,7 +90,11 @@ int tsvgp_site_accum_slots_f32(void);
  *     K [rows_alloc x ldk] row-major with rows_alloc >= round_up(N,128) and ldk >= round_up(M,128); entries with n >= N or
  *     m >= M (up to the padded extents) are written as 0.  D <= 32 (padded to 1, 2, 4, 8, 16 or 32 inside).
  *     fp64: exp is the device library's algorithm restated for arguments <= 0 (bit-identical values).  An output of 512 MB or
- *     more is written with non-temporal stores (it cannot stay cached for its reader; work on other streams keeps its L2). */
+ *     more is written with non-temporal stores (it cannot stay cached for its reader; work on other streams keeps its L2).
+ *     ldk even and K on a boundary of two elements -- 16 bytes in fp64, 8 bytes in fp32 (a thread stores its adjacent columns as
+ *     one vector; TSVGP_EINVAL otherwise, before any launch).  fp32 with D <= 16 stores four columns per thread (16 bytes) when
+ *     K is on a 16-byte boundary and ldk (and strideK of (1c)) a multiple of 4, else two: the same values either way.  The same
+ *     rule holds for (1b). */
 int tsvgp_se_fill_f64(const double *X, const double *Z, const double *inv_ls, double variance, double *K, int64_t N,
                       int M, int D, int64_t ldk, void *stream);
 int tsvgp_se_fill_f32(const float *X, const float *Z, const float *inv_ls, float variance, float *K, int64_t N, int M,
@@ -114,7 +118,8 @@ int tsvgp_kernel_fill_f32(int kind, const float *X, const float *Z, const float 
  *     Kuf [P, M, N] at src/models/tsvgp.py:269 for BASELINE configs[4]) in ONE launch:
  *        K[p][n, m] = variance[p] * k(r_p),   r_p^2 = sum_d ((x_nd - z_md) * inv_ls[p*D + d])^2,   latent p at K + p*strideK.
  *     inv_ls [P x D] is a device array; variance_host [P] is a HOST array (the scalars travel as kernel arguments, exactly
- *     as `variance` does above).  1 <= P <= TSVGP_MAX_BATCH; strideK >= round_up(N,128) * ldk, even. */
+ *     as `variance` does above).  1 <= P <= TSVGP_MAX_BATCH; strideK >= round_up(N,128) * ldk, even; K on a boundary of two
+ *     elements as in (1) -- with the even strideK every K + p*strideK is then on it too (TSVGP_EINVAL otherwise, before any launch). */
 int tsvgp_kernel_fill_batched_f64(int kind, const double *X, const double *Z, const double *inv_ls,
                                   const double *variance_host, double *K, int64_t strideK, int64_t N, int M, int D,
                                   int64_t ldk, int P, void *stream);
@@ -125,7 +130,10 @@ int tsvgp_kernel_fill_batched_f32(int kind, const float *X, const float *Z, cons
 /* (1d) Input dimensions beyond 32 (the reference's MNIST notebook has D = 784): the scaled squared distance is then a
  *     GEMM, r2[n,m] = xx[n] + zz[m] - 2 G[n,m] with G = (X/l)(Z/l)^T (GPflow's square_distance form [ext]), which the caller
  *     takes from the BLAS library into K [rows_pad x ldk]; this call turns it into K = variance * k(r2) in place and
- *     zero-fills the padding (rows >= N, columns >= M).  xx [N], zz [M]: squared norms of the scaled rows. */
+ *     zero-fills the padding (rows >= N, columns >= M).  xx [N], zz [M]: squared norms of the scaled rows.  ldk even and K on a
+ *     boundary of two elements (16 bytes in fp64, 8 in fp32: a thread loads and stores its two columns as one vector;
+ *     TSVGP_EINVAL otherwise, before any launch).  A slightly negative r2 (rounding of the expanded form) goes into the profile
+ *     as it is: the squared exponential returns variance * exp(-r2 / 2) > variance, the Matern kernels clamp. */
 int tsvgp_gram_to_kernel_f64(int kind, double *K, const double *xx, const double *zz, double variance, int64_t N, int M,
                              int64_t ldk, void *stream);
 int tsvgp_gram_to_kernel_f32(int kind, float *K, const float *xx, const float *zz, float variance, int64_t N, int M,
@@ -157,7 +165,8 @@ int tsvgp_cov_f32(int kind, const float *T, const float *X, const float *inv_ls,
  *     reference experiments/uci_regression.py:159-160, docs/notebooks/mnist.py:117-192 with D = 784).  G [N x ldk] holds the
  *     Gram block x~ z~^T on entry; on return W = -2 variance V * k'(r2) with V = g0 beta^T - 2 g1 * U (padding zero), and
  *     vpart [tsvgp_gram_to_gradw_parts(N, M)] one partial sum of V k(r2) per workgroup (d ELBO / d variance = their sum).
- *     g0, g1: element stride gstride; beta: element stride bstride; U [N x ldu].  The caller finishes in M x D:
+ *     g0, g1: element stride gstride; beta: element stride bstride; U [N x ldu].  ldk and ldu even, G and U on a boundary of two
+ *     elements (16 bytes in fp64, 8 in fp32; TSVGP_EINVAL otherwise, before any launch).  The caller finishes in M x D:
  *     dZ = (W^T x~ - z~ * colsum W) / l,  d l_d = (sum_n x~_nd^2 rowsum_n - 2 sum_m z~_md (W^T x~)_md + sum_m z~_md^2 colsum_m) / l_d. */
 int64_t tsvgp_gram_to_gradw_parts(int64_t N, int M);
 int tsvgp_gram_to_gradw_f64(int kind, double *G, const double *xx, const double *zz, double variance, const double *U,

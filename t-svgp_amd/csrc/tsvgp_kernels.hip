@@ -4072,6 +4072,8 @@ int gram_to_kernel(int kind, T* K, const T* xx, const T* zz, T variance, int64_t
     const int64_t rows_pad = (N + TILE - 1) / TILE * TILE;
     const int cols_pad = (M + TILE - 1) / TILE * TILE;
     if (ldk < cols_pad || (ldk % 2) != 0 || rows_pad > 0x7fffffff) return TSVGP_EINVAL;
+    // a thread loads and stores its two columns as one vector at K + n * ldk + m (m, ldk even): 16 bytes in fp64, 8 in fp32
+    if ((reinterpret_cast<uintptr_t>(K) & (2 * sizeof(T) - 1)) != 0) return TSVGP_EINVAL;
     // grid.y is limited to 65535: rows go through y (and z when there are more)
     const dim3 block(NTHREADS);
     const unsigned gx = (unsigned)((cols_pad / 2 + NTHREADS - 1) / NTHREADS);
@@ -4854,6 +4856,9 @@ int gram_to_gradw(int kind, T* G, const T* xx, const T* zz, T variance, const T*
     const int64_t rows_pad = (N + TILE - 1) / TILE * TILE;
     const int cols_pad = (M + TILE - 1) / TILE * TILE;
     if (ldk < cols_pad || (ldk % 2) != 0 || ldu < cols_pad || (ldu % 2) != 0 || rows_pad > 0x7fffffff) return TSVGP_EINVAL;
+    // a thread moves its two columns of G and of U as one vector each (m, ldk, ldu even): 16 bytes in fp64, 8 in fp32
+    if ((reinterpret_cast<uintptr_t>(G) & (2 * sizeof(T) - 1)) != 0 || (reinterpret_cast<uintptr_t>(U) & (2 * sizeof(T) - 1)) != 0)
+        return TSVGP_EINVAL;
     const dim3 block(NTHREADS);
     const unsigned gx = (unsigned)((cols_pad / 2 + NTHREADS - 1) / NTHREADS);
     for (int64_t r0 = 0; r0 < rows_pad; r0 += 65535) {
@@ -4884,6 +4889,9 @@ int kernel_fill(int kind, const T* X, const T* Z, const T* inv_ls, const T* vari
     const int cols_pad = (M + TILE - 1) / TILE * TILE;
     if (ldk < cols_pad || (ldk % 2) != 0) return TSVGP_EINVAL;
     if (P > 1 && (strideK < rows_pad * ldk || (strideK % 2) != 0)) return TSVGP_EINVAL;
+    // a thread stores its columns as one vector at K + p * strideK + n * ldk + m (m, ldk, strideK even): 16 bytes in fp64; 8 in fp32,
+    // which takes the 16-byte stores of four columns per thread only where the layout below allows them
+    if ((reinterpret_cast<uintptr_t>(K) & (2 * sizeof(T) - 1)) != 0) return TSVGP_EINVAL;
     if (D > 32) return TSVGP_EINVAL;  // input dimensions are padded to a compile-time size (1, 2, 4, 8, 16, 32)
     FillBatch<T> var{};
     for (int q = 0; q < P; ++q) var.v[q] = variance[q];

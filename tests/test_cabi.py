@@ -116,6 +116,44 @@ def test_potrf_rejects_layouts_its_16_byte_row_accesses_cannot_take(entry):
             assert lib.tsvgp_potrf_inv_f64(a, M, lay["lda"], lay["batch"], lay["stride"], inf, w, x, xt, t, 0, None) == 1, which
 
 
+@pytest.mark.parametrize("sfx,ctype", [("f64", "c_double"), ("f32", "c_float")])
+def test_kernel_matrix_entries_reject_an_output_off_its_vector_boundary(sfx, ctype):
+    """The fill, ``tsvgp_gram_to_kernel_*`` and ``tsvgp_gram_to_gradw_*`` move a thread's two adjacent columns as one vector at
+    K + n*ldk + m with m and ldk even: K (G and U of the gradient form) one element behind a two-element boundary -- 8 bytes off a
+    16-byte boundary in fp64, 4 bytes off an 8-byte boundary in fp32 -- is TSVGP_EINVAL in front of any launch (real host buffers,
+    every pointer non-NULL, every other argument valid: nothing reads them).  The fp32 layouts that only rule out the 16-byte
+    stores -- K 8 bytes off, ldk or strideK 2 modulo 4 -- stay legal and RUN in tests/test_gpu_kernel_values.py."""
+    import ctypes
+
+    lib = pkg()._backend.lib()
+    ct = getattr(ctypes, ctype)
+    esz = ctypes.sizeof(ct)
+    N, M, D, ldk, P = 130, 130, 3, 256, 2
+    Np = 256
+    buf = lambda n: (ct * n)()
+    aligned = lambda a: (ctypes.addressof(a) + 15) // 16 * 16
+    X, Z, il, xx, zz, g0, g1, beta = buf(N * D), buf(M * D), buf(P * D), buf(N), buf(M), buf(N), buf(N), buf(M)
+    K, Ubuf = buf(P * (Np * ldk + 2) + 8), buf(Np * ldk + 8)
+    vpart = (ctypes.c_double * int(lib.tsvgp_gram_to_gradw_parts(N, M)))()
+    var = (ct * P)(1.3, 0.8)
+    adr = ctypes.addressof
+    off = aligned(K) + esz  # one element behind the boundary
+    assert off % (2 * esz) == esz
+    fill = getattr(lib, f"tsvgp_kernel_fill_{sfx}")
+    assert fill(0, adr(X), adr(Z), adr(il), 1.3, off, N, M, D, ldk, None) == 1
+    assert getattr(lib, f"tsvgp_se_fill_{sfx}")(adr(X), adr(Z), adr(il), 1.3, off, N, M, D, ldk, None) == 1
+    batched = getattr(lib, f"tsvgp_kernel_fill_batched_{sfx}")
+    assert batched(0, adr(X), adr(Z), adr(il), adr(var), off, Np * ldk + 2, N, M, D, ldk, P, None) == 1
+    assert batched(0, adr(X), adr(Z), adr(il), adr(var), aligned(K), Np * ldk + 1, N, M, D, ldk, P, None) == 1  # K + strideK off it
+    assert getattr(lib, f"tsvgp_gram_to_kernel_{sfx}")(3, off, adr(xx), adr(zz), 1.3, N, M, ldk, None) == 1
+    gradw = getattr(lib, f"tsvgp_gram_to_gradw_{sfx}")
+    tail = (adr(g0), adr(g1), 1, adr(beta), 1, N, M, ldk, adr(vpart), None)
+    assert gradw(2, off, adr(xx), adr(zz), 1.3, aligned(Ubuf), ldk, *tail) == 1
+    assert gradw(2, aligned(K), adr(xx), adr(zz), 1.3, aligned(Ubuf) + esz, ldk, *tail) == 1
+    # an odd ldk was rejected before and still is
+    assert fill(0, adr(X), adr(Z), adr(il), 1.3, aligned(K), N, M, D, ldk + 1, None) == 1
+
+
 def test_product_path_fails_loudly_without_gpu():
     """No CPU fallback: with no ROCm device the model refuses to run the E-step (it never routes through the oracle)."""
     import numpy as np
