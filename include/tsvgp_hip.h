@@ -571,6 +571,25 @@ int tsvgp_greedy_select_f64(int kind, const double *X, const double *inv_ls, dou
                             double *d, int64_t *indices, double *pivots, int32_t *count, void *work, int64_t N, int M, int D,
                             void *stream);
 
+/* (10) Pathwise function draws (Matheron's rule; Wilson, Borovitskiy, Terenin, Mostowsky, Deisenroth 2020 [ext]: nothing in the
+ *     reference draws functions): S sample paths of one latent GP evaluated at N points without any N-sized matrix,
+ *        out[s, n] = sum_{l < L} ( W[s, l] cos(Omega_l . x~_n) + W[s, L + l] sin(Omega_l . x~_n) )
+ *                  + sum_{m < M} V[s, m] * variance * k_kind(r(x_n, z_m)),        x~ = x * inv_ls,
+ *     the first sum a random-feature draw of the prior (the caller scales W by sqrt(variance / L)), the second the update that
+ *     carries it through the inducing values (V = K6^-1 (u - g(Z))); r and k as tsvgp_kernel_fill_* (same device functions, the
+ *     difference form on the scaled inputs).  X [N x D], Z [M x D], inv_ls [D], Omega [L x D] (unitless frequencies), W [S x 2 L],
+ *     V [S x M], all row-major and contiguous; out [S x ldo], ldo >= N, columns >= N are not written.  M = 0 with V (and Z) NULL
+ *     gives the prior part alone.  1 <= D <= 32, 1 <= S <= TSVGP_PATHWISE_MAX_S (the caller loops over chunks of samples: a row's
+ *     S sums live in registers), N >= 1 and at most 256 * (2^31 - 1), L >= 1, M >= 0, variance finite and > 0; TSVGP_EINVAL
+ *     otherwise, before any launch.  One thread per row; the sine / cosine pair and the kernel value are taken once per (n, l) and
+ *     (n, m) and serve all S samples; Omega, W, Z~ and V go through LDS in chunks of 64.  A row's values depend on that row and the
+ *     operands alone -- not on N, on the other rows or on the launch geometry: the same x gives the same bits in any call.
+ *     No atomics, a summation order fixed by (L, M). */
+#define TSVGP_PATHWISE_MAX_S 16
+int tsvgp_pathwise_f64(int kind, const double *X, const double *Z, const double *inv_ls, double variance, const double *Omega,
+                       const double *W, const double *V, double *out, int64_t N, int M, int L, int D, int S, int64_t ldo,
+                       void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

@@ -11,12 +11,13 @@ from .inducing_variables import (InducingPoints, InducingSelection, SharedIndepe
 from .kernels import Matern32, Matern52, SeparateIndependent, SquaredExponential
 from .likelihoods import Bernoulli, Gaussian, HeteroskedasticTFPConditional, MultiClass, Poisson, RobustMax, Softmax, StudentT
 from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white, t_VGP
+from .pathwise import FunctionSamples
 from .sites import DenseSites, DiagSites, Sites
 
 __all__ = [
     "t_SVGP", "t_SVGP_white", "t_SVGP_sites", "t_VGP", "base_SVGP", "DenseSites", "DiagSites", "Sites", "SquaredExponential", "Gaussian", "Bernoulli", "HeteroskedasticTFPConditional", "Softmax", "StudentT", "Poisson",
     "MultiClass", "RobustMax",
-    "InducingPoints", "select_inducing_points", "InducingSelection",
+    "InducingPoints", "select_inducing_points", "InducingSelection", "FunctionSamples",
     "SeparateIndependent", "SharedIndependentInducingVariables", "Matern32", "Matern52",
     "inducingpoint_wrapper", "Parameter", "default_float", "default_jitter", "HipExtensionError", "build_library",
     "distributed", "util", "training",

@@ -44,6 +44,7 @@ POTRF_RHS_UPPER = 2  # TSVGP_POTRF_RHS_UPPER
 POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
 POTRF_FUSE = 16  # TSVGP_POTRF_FUSE
 VGP_NO_ROWS = 1  # TSVGP_VGP_NO_ROWS
+PATHWISE_MAX_S = 16  # TSVGP_PATHWISE_MAX_S: samples per launch of tsvgp_pathwise_f64
 ABI_VERSION = 5  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
 
 _lib = None
@@ -193,6 +194,8 @@ _PROTOTYPES = {
     "tsvgp_greedy_select_work_bytes": (c_int64, [c_int64, c_int]),
     "tsvgp_greedy_select_f64": (c_int, [c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_pathwise_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                   c_int, c_int, c_int, c_int64, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -19,6 +19,8 @@
 //   kgrad_kernel        kernel-parameter gradient contraction of the M-step.  HBM bound.
 //   greedy_step_kernel, greedy_pick_kernel   greedy conditional-variance selection of inducing points (pivoted Cholesky of
 //                       K(X, X), two launches per step).  HBM bound on the re-read of the transposed factor.
+//   pathwise_kernel     S pathwise function draws at N points: random-feature prior draw + update through the inducing values,
+//                       one thread per row, no N-sized operand.  fp64 VALU bound (one sincos per row and frequency).
 //
 // Tiling shared by the N-sized MFMA kernels: 128x128 output tile per 256-thread workgroup; wave w owns row blocks
 // {w, 7 - w} x all eight 16-column blocks (acc[2][8]); k-chunks of 16 (32 floats in the panel kernels) staged
@@ -5588,6 +5590,142 @@ int greedy_select(int kind, const double* X, const double* inv_ls, double varian
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// pathwise_kernel: S function draws of one latent GP at the rows of X (tsvgp_pathwise_f64),
+//   out[s, n] = sum_l (W[s, l] cos(Omega_l . x~_n) + W[s, L + l] sin(Omega_l . x~_n)) + sum_m V[s, m] variance k(x_n, z_m).
+// One thread per row: x~ (DT registers) and the S sums (SB registers) stay in registers through both sweeps; the frequencies with
+// their 2 S weights, then the scaled inducing points with their S weights, pass through LDS in chunks of PW_CHUNK, every read a
+// wave-uniform address (a broadcast: no bank conflicts).  DT = D and SB = S padded to compile-time sizes, the padding zeros on both
+// sides (a padded sample's weights are zeros and its sums are not stored).  The sine / cosine pair (the device library's fp64
+// sincos with its full argument reduction: |Omega . x~| reaches hundreds) and the kernel profile cost ~100 and ~30 fp64-rate
+// instructions against D + 2 S and D + S fused multiply-adds, so up to S = 16 the work per row is that of one sample.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int PW_ROWS = 256;  // rows (threads) per workgroup
+constexpr int PW_CHUNK = 64;  // frequencies / inducing points per LDS stage
+
+struct PathwiseArgs {
+    const double *X, *Z, *inv_ls, *Omega, *W, *V;
+    double* out;
+    double variance;
+    int64_t N, ldo;
+    int M, L, D, S;
+};
+
+template <int KIND, int DT, int SB>
+__device__ __forceinline__ void pathwise_inducing_sweep(const PathwiseArgs& a, const double (&x)[DT], double (&acc)[SB],
+                                                        double (*Fs)[DT], double (*Cs)[2 * SB], bool active) {
+    const int t = threadIdx.x;
+    for (int m0 = 0; m0 < a.M; m0 += PW_CHUNK) {
+        const int nm = a.M - m0 < PW_CHUNK ? a.M - m0 : PW_CHUNK;
+        __syncthreads();  // the previous chunk has been read
+        for (int idx = t; idx < PW_CHUNK * DT; idx += PW_ROWS) {
+            const int r = idx / DT, d = idx - r * DT;
+            Fs[r][d] = (r < nm && d < a.D) ? a.Z[(int64_t)(m0 + r) * a.D + d] * a.inv_ls[d] : 0.0;
+        }
+        for (int idx = t; idx < PW_CHUNK * SB; idx += PW_ROWS) {
+            const int r = idx / SB, s = idx - r * SB;
+            Cs[r][s] = (r < nm && s < a.S) ? a.V[(int64_t)s * a.M + m0 + r] : 0.0;
+        }
+        __syncthreads();
+        if (active) {
+            for (int r = 0; r < nm; ++r) {
+                double s2 = 0.0;
+#pragma unroll
+                for (int d = 0; d < DT; ++d) {
+                    const double dd = x[d] - Fs[r][d];
+                    s2 = fma(dd, dd, s2);
+                }
+                const double k = a.variance * kernel_profile<KIND>(s2);
+#pragma unroll
+                for (int s = 0; s < SB; ++s) acc[s] = fma(k, Cs[r][s], acc[s]);
+            }
+        }
+    }
+}
+
+template <int DT, int SB>
+__global__ __launch_bounds__(PW_ROWS) void pathwise_kernel(PathwiseArgs a, int kind) {
+    __shared__ __attribute__((aligned(16))) double Fs[PW_CHUNK][DT];      // Omega rows, then scaled rows of Z
+    __shared__ __attribute__((aligned(16))) double Cs[PW_CHUNK][2 * SB];  // [cos weights | sin weights] of a frequency, then V
+    const int t = threadIdx.x;
+    const int64_t n = (int64_t)blockIdx.x * PW_ROWS + t;
+    const bool active = n < a.N;  // (no early return: every thread stages and meets the barriers)
+    double x[DT], acc[SB];
+#pragma unroll
+    for (int d = 0; d < DT; ++d) x[d] = (active && d < a.D) ? a.X[n * a.D + d] * a.inv_ls[d] : 0.0;
+#pragma unroll
+    for (int s = 0; s < SB; ++s) acc[s] = 0.0;
+    for (int l0 = 0; l0 < a.L; l0 += PW_CHUNK) {
+        const int nl = a.L - l0 < PW_CHUNK ? a.L - l0 : PW_CHUNK;
+        if (l0 > 0) __syncthreads();  // the previous chunk has been read
+        for (int idx = t; idx < PW_CHUNK * DT; idx += PW_ROWS) {
+            const int r = idx / DT, d = idx - r * DT;
+            Fs[r][d] = (r < nl && d < a.D) ? a.Omega[(int64_t)(l0 + r) * a.D + d] : 0.0;
+        }
+        for (int idx = t; idx < PW_CHUNK * 2 * SB; idx += PW_ROWS) {
+            const int r = idx / (2 * SB), j = idx - r * (2 * SB);
+            const int half = j / SB, s = j - half * SB;
+            Cs[r][j] = (r < nl && s < a.S) ? a.W[(int64_t)s * 2 * a.L + (int64_t)half * a.L + l0 + r] : 0.0;
+        }
+        __syncthreads();
+        if (active) {
+            for (int r = 0; r < nl; ++r) {
+                double arg = 0.0;
+#pragma unroll
+                for (int d = 0; d < DT; ++d) arg = fma(Fs[r][d], x[d], arg);
+                double sn, cs;
+                sincos(arg, &sn, &cs);
+#pragma unroll
+                for (int s = 0; s < SB; ++s) acc[s] = fma(sn, Cs[r][SB + s], fma(cs, Cs[r][s], acc[s]));
+            }
+        }
+    }
+    if (kind == TSVGP_KERNEL_SE)
+        pathwise_inducing_sweep<TSVGP_KERNEL_SE, DT, SB>(a, x, acc, Fs, Cs, active);
+    else if (kind == TSVGP_KERNEL_MATERN32)
+        pathwise_inducing_sweep<TSVGP_KERNEL_MATERN32, DT, SB>(a, x, acc, Fs, Cs, active);
+    else
+        pathwise_inducing_sweep<TSVGP_KERNEL_MATERN52, DT, SB>(a, x, acc, Fs, Cs, active);
+    if (active) {
+#pragma unroll
+        for (int s = 0; s < SB; ++s)
+            if (s < a.S) a.out[(int64_t)s * a.ldo + n] = acc[s];  // consecutive lanes, consecutive columns
+    }
+}
+
+template <int DT>
+void pathwise_launch(const PathwiseArgs& a, int kind, dim3 grid, hipStream_t st) {
+    if (a.S == 1)
+        hipLaunchKernelGGL((pathwise_kernel<DT, 1>), grid, dim3(PW_ROWS), 0, st, a, kind);
+    else if (a.S <= 4)
+        hipLaunchKernelGGL((pathwise_kernel<DT, 4>), grid, dim3(PW_ROWS), 0, st, a, kind);
+    else
+        hipLaunchKernelGGL((pathwise_kernel<DT, TSVGP_PATHWISE_MAX_S>), grid, dim3(PW_ROWS), 0, st, a, kind);
+}
+
+int pathwise(int kind, const double* X, const double* Z, const double* inv_ls, double variance, const double* Omega, const double* W,
+             const double* V, double* out, int64_t N, int M, int L, int D, int S, int64_t ldo, void* stream) {
+    if (!X || !inv_ls || !Omega || !W || !out || N <= 0 || L <= 0 || M < 0 || D <= 0 || D > 32 || S < 1 ||
+        S > TSVGP_PATHWISE_MAX_S || ldo < N || !(variance > 0.0) || !std::isfinite(variance))
+        return TSVGP_EINVAL;
+    if (M > 0 && (!Z || !V)) return TSVGP_EINVAL;
+    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
+    const int64_t blocks = (N + PW_ROWS - 1) / PW_ROWS;
+    if (blocks > 0x7fffffff) return TSVGP_EINVAL;
+    const PathwiseArgs a = {X, Z, inv_ls, Omega, W, V, out, variance, N, ldo, M, L, D, S};
+    const dim3 grid((unsigned)blocks);
+    hipStream_t st = (hipStream_t)stream;
+    if (D <= 4)
+        pathwise_launch<4>(a, kind, grid, st);
+    else if (D <= 8)
+        pathwise_launch<8>(a, kind, grid, st);
+    else if (D <= 16)
+        pathwise_launch<16>(a, kind, grid, st);
+    else
+        pathwise_launch<32>(a, kind, grid, st);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -5929,6 +6067,11 @@ int tsvgp_greedy_select_f64(int kind, const double* X, const double* inv_ls, dou
                             double* d, int64_t* indices, double* pivots, int32_t* count, void* work, int64_t N, int M, int D,
                             void* stream) {
     return greedy_select(kind, X, inv_ls, variance, floor, C, ldc, d, indices, pivots, count, work, N, M, D, stream);
+}
+int tsvgp_pathwise_f64(int kind, const double* X, const double* Z, const double* inv_ls, double variance, const double* Omega,
+                       const double* W, const double* V, double* out, int64_t N, int M, int L, int D, int S, int64_t ldo,
+                       void* stream) {
+    return pathwise(kind, X, Z, inv_ls, variance, Omega, W, V, out, N, M, L, D, S, ldo, stream);
 }
 int tsvgp_selftest_mfma_f64(const double* a, const double* b, double* c, void* stream) {
     if (!a || !b || !c) return TSVGP_EINVAL;

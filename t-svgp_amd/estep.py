@@ -1345,6 +1345,47 @@ class EStepEngine:
                     "tsvgp_mc_normals")
         return out
 
+    def pathwise(self, X, Z, kernel, Omega, W, V=None) -> torch.Tensor:
+        """S pathwise function draws of one latent GP at the rows of X (``tsvgp_pathwise_f64``), [S, N] fp64:
+
+            out[s, n] = sum_l (W[s, l] cos(Omega_l . x~_n) + W[s, L + l] sin(Omega_l . x~_n)) + sum_m V[s, m] k(x_n, z_m)
+
+        X [N, D <= 32], Z [M, D], ``kernel`` one stationary kernel (lengthscales, variance and profile of k and of x~ = x / l),
+        Omega [L, D], W [S, 2 L] (already scaled by sqrt(variance / L)), V [S, M]; ``V=None``: the first sum alone (Z is not read).
+        fp64 whatever the engine's compute dtype; launches on the current stream, ``PATHWISE_MAX_S`` samples per launch."""
+        if isinstance(kernel, SeparateIndependent):
+            raise ValueError("pathwise: one kernel per call; pass the latent's own kernel")
+        f64 = lambda t: t.to(device=self.device, dtype=torch.float64).contiguous()
+        X, Omega, W = f64(X), f64(Omega), f64(W)
+        if X.dim() != 2 or X.shape[0] < 1:
+            raise ValueError(f"pathwise: X must be [N >= 1, D], got {tuple(X.shape)}")
+        N, D = X.shape
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"pathwise: 1 <= D <= {MAX_INPUT_DIM} (TSVGP_MAX_BATCH, the normal generator's column limit), got {D}")
+        if Omega.dim() != 2 or Omega.shape[0] < 1 or Omega.shape[1] != D:
+            raise ValueError(f"pathwise: Omega must be [L >= 1, D] = [L, {D}], got {tuple(Omega.shape)}")
+        L = Omega.shape[0]
+        if W.dim() != 2 or W.shape[0] < 1 or W.shape[1] != 2 * L:
+            raise ValueError(f"pathwise: W must be [S >= 1, 2 L] = [S, {2 * L}], got {tuple(W.shape)}")
+        S = W.shape[0]
+        M = 0
+        if V is not None:
+            V, Z = f64(V), f64(Z)
+            M = Z.shape[0]
+            if Z.dim() != 2 or Z.shape[1] != D or tuple(V.shape) != (S, M):
+                raise ValueError(f"pathwise: Z must be [M, {D}] and V [S, M] = [{S}, {M}], got {tuple(Z.shape)} and {tuple(V.shape)}")
+        inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
+        variance = kernel.variance.item()
+        out = torch.empty((S, N), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            for s0 in range(0, S, B.PATHWISE_MAX_S):
+                sc = min(B.PATHWISE_MAX_S, S - s0)
+                self._launch("tsvgp_pathwise", lambda: self.lib.tsvgp_pathwise_f64(
+                    int(kernel.kind), X.data_ptr(), _ptr(Z if M else None), inv_ls.data_ptr(), variance, Omega.data_ptr(),
+                    W[s0:s0 + sc].data_ptr(), _ptr(V[s0:s0 + sc] if M else None), out[s0:s0 + sc].data_ptr(), N, M, L, D, sc, N,
+                    self._stream()))
+        return out
+
     # ------------------------------------------------------------------ per-datum diagonal sites (t_SVGP_sites)
     def project_diag(self, X, Z, kernel, w1, w2):
         """The projection of per-datum sites onto the inducing points (reference src/util.py:188-236 with cholesky=False and

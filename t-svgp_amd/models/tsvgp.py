@@ -84,6 +84,7 @@ class base_SVGP(abc.ABC):
         self._engine = None
         self._engine64 = None  # predict_f_samples of an fp32 model: see _sample_engine
         self._sample_draw = 0  # predict_f_samples(draw=None): the next draw number
+        self._function_draw = 0  # sample_functions(draw=None): the next draw number (a counter of its own)
         self.poll_status = True  # how the step's status read waits for the GPU: see _read_flags
         self.data_parallel = None  # None = automatic: shard-reduce whenever torch.distributed has > 1 rank
 
@@ -194,6 +195,35 @@ class base_SVGP(abc.ABC):
         else:
             f = mean[None] + torch.sqrt(var)[None] * eps
         return f[0] if num_samples is None else f
+
+    def sample_functions(self, num_samples, num_features=1024, *, seed=0, draw=None):
+        """``num_samples`` draws from the posterior over the latent FUNCTIONS, as one ``FunctionSamples`` object: ``fs(Xnew)``
+        evaluates the same draws at any Xnew [N, D], [S, N, P], any number of times and at any N -- O(N (L + M) S) work in one HIP
+        kernel, no N-sized matrix (``predict_f_samples`` factors the [N, N] covariance and draws a new function per call).
+        Pathwise conditioning with ``num_features`` = L random features of the stationary kernel (``pathwise.py`` has the algebra
+        and the layout of the random numbers): the mean of the draws is ``predict_f``'s exactly, their covariance
+        ``predict_f(full_cov=True)``'s up to O(variance / sqrt(L)) per prior covariance entry.  fp64 whatever the compute dtype
+        (``_sample_engine``); input dimension D <= 32.  The draws are a pure function of (seed, draw) and of the model's state
+        at the time of the call, which the object keeps a copy of: every rank that makes the same call holds the same functions.
+        ``draw=None`` uses, and then advances, a counter of this model that starts at 0 -- its own, not ``predict_f_samples``'."""
+        from ..pathwise import sample_functions
+
+        eng = self._sample_engine()
+        P = int(self.num_latent_gps)
+        if not (1 <= P <= B.MAX_BATCH):
+            raise ValueError(f"sample_functions draws for at most {B.MAX_BATCH} latent GPs (TSVGP_MAX_BATCH), got {P}")
+        S, L = int(num_samples), int(num_features)
+        if not (1 <= S <= B.MC_MAX_SAMPLES):
+            raise ValueError(f"num_samples must lie in [1, {B.MC_MAX_SAMPLES}], got {num_samples}")
+        if L < 1:
+            raise ValueError(f"num_features must be at least 1, got {num_features}")
+        advance = draw is None
+        if advance:
+            draw = self._function_draw
+        fs = sample_functions(self, eng, S, L, int(seed), int(draw))
+        if advance:
+            self._function_draw = draw + 1  # (a call that raised leaves the counter alone)
+        return fs
 
     def maximum_log_likelihood_objective(self, data):
         return self.elbo(data)
