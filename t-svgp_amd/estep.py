@@ -27,6 +27,7 @@ the mapped pass's pair of it and ``lik_map``) and ``EStepEngine._site_sums``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -37,6 +38,7 @@ import torch
 from . import _backend as B
 from .distributed import world_size
 from .kernels import SeparateIndependent
+from .side_branch import SideBranch, SideStream
 
 MAX_INPUT_DIM = 32  # the fill kernel pads D to a compile-time size (1, 2, 4, 8, 16, 32)
 MAX_INPUT_DIM_GRAD = 16  # tsvgp_kernel_grad_* (M-step): 1, 2, 4, 8, 16; beyond: GEMM form (tsvgp_gram_to_gradw_*)
@@ -133,7 +135,7 @@ class EStepEngine:
         self.nsplit_override = None
         self.syrk_oversubscribe = None  # None: by kernel (see choose_nsplit)
         self._b_tag = None  # identifies the contents of the cached whitened buffer B
-        self._side = None  # side stream of start_fill
+        self._side = SideStream(self.device)  # owner of the side stream (start_fill, the models' epilogue operands)
         self.last_batched = False  # the last pass over separate kernels ran as batched launches
         self.last_trmm_batch = 1  # latents per whitening launch of that pass
         self.profile = None  # set to a dict to record (start, stop) HIP events per kernel launch on the launch stream
@@ -199,6 +201,27 @@ class EStepEngine:
         """Drop the cached work buffers."""
         self._buf.clear()
         self._b_tag = None
+
+    @contextlib.contextmanager
+    def private_buffers(self):
+        """A fresh set of work buffers (and no warm tag) for the body -- a capture, whose graph owns what it allocates: yields
+        the dict for the caller to keep alive and puts the engine's own pair back on exit, also on error."""
+        saved = self._buf, self._b_tag
+        self._buf, self._b_tag = {}, None
+        try:
+            yield self._buf
+        finally:
+            self._buf, self._b_tag = saved
+
+    def fork(self, reads=(), writes=(), **payload):
+        """``SideStream.fork`` on this engine's side stream: the body runs there, the yielded ``SideBranch`` keeps ``reads`` and
+        ``writes`` alive until its ``join()``."""
+        return self._side.fork(reads, writes, **payload)
+
+    @property
+    def side_open(self) -> bool:
+        """Whether a fork has created the side stream yet."""
+        return self._side.stream is not None
 
     def slots(self) -> int:
         if self._slots is None:
@@ -805,9 +828,9 @@ class EStepEngine:
         KfuP = self._get("KfuP", (P, Np, Mp), T)
         stride = Np * Mp
         if prefill is not None:
-            self._take_prefill(prefill, "KfuP", KfuP)
+            prefill.take("KfuP", KfuP)
         else:
-            self._wait_stale_fill()
+            self._side.wait_stale()
             self._fill_batched(X, Z, kernel, KfuP)
         # whitening in place, one launch per run of consecutive whitened latents: B_p = K_p U9_p^-T (upper form)
         runs, start = [], None
@@ -867,7 +890,7 @@ class EStepEngine:
         if mapped or Y is not None:
             self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"))
         if X.shape[0] > 0:
-            if prefill is not None and "KfuP" in prefill:  # the batched fill is already under way (start_fill)
+            if prefill is not None and prefill.name == "KfuP":  # the batched fill is already under way (start_fill)
                 whitened = [p for p in range(P) if self._per_latent(whiten_T, p) is not None]
             else:
                 whitened = self._batch_plan(X.shape[0], Z.shape[0], kernel, P, whiten_T,
@@ -952,11 +975,7 @@ class EStepEngine:
         the batched pass, whose fill this starts, needs all of them direct or whitened)."""
         if self.device.type != "cuda" or X.shape[0] == 0:
             return None
-        # Under stream capture (hipGraph) the side stream JOINS the capture: it waits for an event recorded on the capturing
-        # stream (a fork) and the consumer waits for its event (the join) inside the same capture, so a replayed step runs the
-        # fill beside the prelude exactly as an eager one.  record_stream means nothing to a graph's private pool, so there the
-        # ticket itself keeps every tensor the side stream reads alive until the join (`keep`, below).
-        capturing = torch.cuda.is_current_stream_capturing()
+        # (fork / join, also inside a capture, and what keeps the converted inputs alive: side_branch.py)
         T, dev = self.dtype, self.device
         N, D = X.shape
         M = Z.shape[0]
@@ -971,10 +990,6 @@ class EStepEngine:
         elif (b_tag is not None and self._b_tag == (want, b_tag) and self._buf.get(want) is not None
                 and tuple(self._buf[want].shape) == (Np, Mp)):
             return None
-        main = torch.cuda.current_stream(dev)
-        if self._side is None:
-            self._side = torch.cuda.Stream(dev)
-        side = self._side
         Xc = X.to(device=dev, dtype=T).contiguous()
         Zc = Z.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -982,42 +997,16 @@ class EStepEngine:
             self._buf.pop("Kfu", None)
             self._buf.pop("B", None)
             buf = self._get("KfuP", (P, Np, Mp), T)
-            keep, ticket = (Xc, Zc), dict(KfuP=buf)
-            fill = lambda: self._fill_batched(Xc, Zc, kernel, buf)
+            with self.fork(reads=(Xc, Zc), writes=(buf,), name="KfuP", buf=buf) as branch:
+                self._fill_batched(Xc, Zc, kernel, buf)
         else:
             inv_ls = kernel.inv_lengthscales(D, T, dev)
             variance = kernel.variance.item()
             buf = self._get("Kfu", (Np, Mp), T)
-            keep = (Xc, Zc, inv_ls)
-            ticket = dict(key=(X.data_ptr(), tuple(X.shape), Z.data_ptr(), tuple(Z.shape), id(kernel)), Kfu=buf)
-            fill = lambda: self.se_fill(Xc, Zc, inv_ls, variance, buf, kernel.kind)
-        side.wait_stream(main)  # the buffer's last readers (the previous pass) and the conversions above
-        with torch.cuda.stream(side):
-            fill()
-            done = torch.cuda.Event()
-            done.record(side)
-        if not capturing:
-            for t in keep + (buf,):  # blocks of the main stream's allocator pool that the side stream touches
-                t.record_stream(side)
-        # `keep`: the converted inputs must outlive the side stream's read of them.  Eagerly record_stream sees to that; under
-        # capture nothing does -- a block freed DURING a capture goes straight back to the graph's pool, the next allocation on
-        # the capturing stream (a prelude temporary) takes it, and in the replayed graph that kernel runs BESIDE the forked fill
-        # still reading it.  Found in round 4 by the two-rank fp32 test of BASELINE configs[3] (fp32: Z [M, D] is converted into
-        # such a temporary; fp64 passes its tensors through, which is why three rounds of fp64 tests never saw it): the state
-        # after four replayed steps was off by 1e-5 ... 0.4, differently on every run.  The ticket holds them until ``run`` has
-        # made the consuming stream wait for the fill.
-        return dict(event=done, keep=keep, **ticket)
-
-    def _wait_stale_fill(self):
-        """A fill started for a pass that never ran must not land on top of the one about to start (a capture begins synchronised)."""
-        if self._side is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(self.device).wait_stream(self._side)
-
-    def _take_prefill(self, prefill, key, buf):
-        """Makes the current stream wait for the fill of ``start_fill`` / ``project_diag`` whose ticket names ``buf`` under ``key``."""
-        if prefill.get(key) is not buf:
-            raise RuntimeError("prefill ticket does not belong to this pass")
-        torch.cuda.current_stream(self.device).wait_event(prefill["event"])
+            with self.fork(reads=(Xc, Zc, inv_ls), writes=(buf,), name="Kfu", buf=buf,
+                           key=(X.data_ptr(), tuple(X.shape), Z.data_ptr(), tuple(Z.shape), id(kernel))) as branch:
+                self.se_fill(Xc, Zc, inv_ls, variance, buf, kernel.kind)
+        return branch
 
     # ------------------------------------------------------------------ one N-pass
     def run(self, X, Y, Z, kernel, *, moment_Tm, moment_mode, gamma, lik_id=B.LIK_NONE, lik_param=0.0,
@@ -1112,9 +1101,9 @@ class EStepEngine:
             self._b_tag = None
             Kfu = self._get("Kfu", (Np, Mp), T)
             if prefill is not None:
-                self._take_prefill(prefill, "Kfu", Kfu)
+                prefill.take("Kfu", Kfu)
             else:
-                self._wait_stale_fill()
+                self._side.wait_stale()
                 self.se_fill(X, Z, inv_ls, variance, Kfu, kernel.kind)
             A = Kfu
             if whiten_T is not None and not late_whiten:
@@ -1300,7 +1289,7 @@ class EStepEngine:
         gam = self._padded_gamma(gamma, Mp, P)
         Kfu = self._get("Kfu", (Np, Mp), T)
         tile = self._get("Tt", (Np, Mp), T)
-        self._wait_stale_fill()
+        self._side.wait_stale()
         for p in range(P):
             kp = kernel.kernels[p] if separate else kernel
             inv_ls, variance = kp.inv_lengthscales(D, T, dev), kp.variance.item()
@@ -1406,12 +1395,10 @@ class EStepEngine:
             return zero, torch.zeros((1, M), dtype=torch.float64, device=dev), None
         self._b_tag = None
         Kfu = self._get("Kfu", (Np, Mp), T)
-        self._wait_stale_fill()
+        self._side.wait_stale()
         self.se_fill(X, Z, kernel.inv_lengthscales(D, T, dev), kernel.variance.item(), Kfu, kernel.kind)
         acc2, acc1 = self._site_sums(Kfu, w1, w2, 1, M)
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
-        return acc2, acc1, dict(event=done, Kfu=Kfu, keep=(X, Z))
+        return acc2, acc1, SideBranch.inline(dev, reads=(X, Z), name="Kfu", buf=Kfu)
 
     def diag_sites_moments(self, X, Z, kernel, ticket, *, whiten_T, moment_Tm, moment_mode, gamma, mean_only=False):
         """mean, var [N, 1] in the compute dtype (cached buffers; var None with ``mean_only``) on the K(X, Z) that
@@ -1421,9 +1408,9 @@ class EStepEngine:
         N, M = X.shape[0], Z.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         Kfu = self._buf.get("Kfu")
-        if ticket is None or ticket["Kfu"] is not Kfu:
+        if ticket is None or ticket.buf is not Kfu:
             raise RuntimeError("diag_sites_moments needs the ticket of this engine's last project_diag")
-        torch.cuda.current_stream(dev).wait_event(ticket["event"])
+        ticket.join()
         A = Kfu
         if whiten_T is not None:
             A = self._get("B", (Np, Mp), T)

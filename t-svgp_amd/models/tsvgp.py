@@ -30,7 +30,6 @@ from __future__ import annotations
 import abc
 import functools
 import os
-import time
 import warnings
 
 import numpy as np
@@ -40,6 +39,7 @@ from .. import _backend as B
 from .. import distributed as D_
 from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import EStepStats, per_latent
+from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
 from ..kernels import SeparateIndependent, latent_kernels
 from ..sites import DenseSites
@@ -115,10 +115,7 @@ class base_SVGP(abc.ABC):
         if not self.poll_status:
             torch.cuda.current_stream(flags.device).synchronize()
             return host.clone()
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(flags.device))
-        while not ev.query():
-            time.sleep(0)  # gives up the GIL and the time slice: other Python threads (loaders, logging) keep running
+        poll_current_stream(flags.device)
         return host.clone()
 
     @abc.abstractmethod
@@ -566,10 +563,7 @@ class t_SVGP(base_SVGP):
             beta = eng.site_beta(Dm, K6l, l1)  # K6^-1 m = l1 - D^T D K6 l1: two triangular matrix-vector launches
         else:
             beta = l1 - bmv(Dm, bmv(Dm, K6l), transpose=True)
-        # (Lt rides along because the side stream reads it below: inside a capture nothing else keeps a block of the graph's pool
-        # from being handed to the next allocation of the capturing stream while the forked branch still reads it -- the race
-        # of profiles/r04_c4_fork_capture_race.txt, met again in round 5 through this very tensor)
-        ops = dict(Z=Z, Kzz=Kzz, K6=K6, D=Dm, U_W=U_W, beta=beta, Id=Id, infos=infos, potrf=potrf, Lt=Lt,
+        ops = dict(Z=Z, Kzz=Kzz, K6=K6, D=Dm, U_W=U_W, beta=beta, Id=Id, infos=infos, potrf=potrf,
                    routes=["whitened"] * P_, moment_mode=B.TRI_UPPER, whiten_mode=B.TRI_UPPER,
                    whiten_T=None, project_T=None)
         if whiten_jitter is None:
@@ -579,7 +573,7 @@ class t_SVGP(base_SVGP):
         # What only the EPILOGUE needs of (theta, Z, the old sites): L L^T (tsvgp.py:293), predict_f(Z)'s mean K_uu beta
         # (:249-254) and, for the direct route, K9^-1 = U9^-T U9^-1.  Three M^3 GEMMs that nothing in the N-pass waits for:
         # they go to the side stream (behind the K(X, Z) fill) and run beside the moments kernel instead of in front of
-        # it; ``_apply_site_update`` waits for ops["epi_event"].
+        # it; ``_apply_site_update`` joins the branch, ops["epi_branch"] (EStepEngine.fork keeps what it reads alive until then).
         want_k9inv = routes is not None and "direct" in routes and Uinv9 is not None
 
         def epilogue_operands():
@@ -587,30 +581,15 @@ class t_SVGP(base_SVGP):
             ops["meanZ"] = self._kmv(Kzz, beta)
             if want_k9inv:
                 ops["K9inv"] = Uinv9.transpose(-1, -2) @ Uinv9
+            return [ops[k] for k in ("LLt", "meanZ", "K9inv") if k in ops]
 
-        side = getattr(eng, "_side", None)
-        if not fork:
-            # in line, in front of the moments kernel: a captured launch-bound step (see _step_front); as an experiment at
-            # N = 1e6 it measured 33.83 / 33.90 ms against 33.92 / 33.96 on the side stream -- no difference worth a second path
-            epilogue_operands()
-        elif self.overlap_fill and side is not None and Kzz.is_cuda:
-            capturing = torch.cuda.is_current_stream_capturing()  # the side stream then joins the capture (fork / join by events)
-            main = torch.cuda.current_stream(self.device)
-            ready = torch.cuda.Event()
-            ready.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ready)
-                epilogue_operands()
-                done = torch.cuda.Event()
-                done.record(side)
-            if not capturing:
-                for t in (L, Lt, Kzz, beta) + ((Uinv9,) if want_k9inv else ()):
-                    t.record_stream(side)  # blocks of the main stream's pool read on the side stream
-                for k in ("LLt", "meanZ", "K9inv"):
-                    if k in ops:
-                        ops[k].record_stream(main)  # and the other way round
-            ops["epi_event"] = done
+        if fork and self.overlap_fill and getattr(eng, "side_open", False) and Kzz.is_cuda:
+            with eng.fork(reads=(L, Lt, Kzz, beta) + ((Uinv9,) if want_k9inv else ())) as branch:
+                branch.produced(*epilogue_operands())
+            ops["epi_branch"] = branch
         else:
+            # no side stream yet, or ``fork`` off: in line, in front of the moments kernel -- a captured launch-bound step (see
+            # _step_front); as an experiment at N = 1e6 it measured 33.83 / 33.90 ms against 33.92 / 33.96 on the side stream
             epilogue_operands()
         if lower9:
             # a = K9^-1 k by two triangular products with the lower factor: b = L9^-1 k, a = L9^-T b; the moments act on
@@ -1230,35 +1209,33 @@ class t_SVGP(base_SVGP):
             bl1, bL = torch.empty_like(sl1), torch.empty_like(sL)
             l1p._value, Lp._value = sl1, sL
             graph = torch.cuda.CUDAGraph()
-            saved_buf, saved_tag = eng._buf, eng._b_tag
-            eng._buf, eng._b_tag = {}, None  # the graph's own work buffers (kept alive by the entry)
             try:
-                if not two:
-                    with torch.cuda.graph(graph):
-                        bl1.copy_(sl1)
-                        bL.copy_(sL)
-                        flags = self._step_device(X, Y, lr, jitter, routes, inplace=True)
-                    entry = dict(graph=graph, flags=flags, state=(sl1, sL), backup=(bl1, bL), buf=eng._buf)
-                else:
-                    P_, M_ = self.num_latent_gps, self.num_inducing
-                    with torch.cuda.graph(graph):
-                        bl1.copy_(sl1)
-                        bL.copy_(sL)
-                        st, ops = self._step_front(X, Y, lr, jitter, routes)
-                        if ops.get("epi_event") is not None:  # the side stream's branch ends inside THIS graph
-                            torch.cuda.current_stream(self.device).wait_event(ops["epi_event"])
-                            ops["epi_event"] = None
-                        packed = D_.pack_stats(st, True, eng)
-                    tail = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(tail, pool=graph.pool()):
-                        acc2, acc1, _, nonpos, rows = D_.unpack_stats(packed, P_, M_, True, eng)
-                        flags = self._apply_site_update(None, ops, lr, jitter, inplace=True,
-                                                        reduced=(acc2, acc1, nonpos, rows))
-                    entry = dict(graph=graph, tail=tail, packed=packed, ops=ops, flags=flags, state=(sl1, sL),
-                                 backup=(bl1, bL), buf=eng._buf)
-                if hasattr(self.likelihood, "rng_state"):  # the map's nodes hold this tensor's address
-                    entry["lik_state"] = self.likelihood.rng_state(self.device)
-                self._graphs[key] = entry
+                with eng.private_buffers() as buf:  # the graph's own work buffers (kept alive by the entry)
+                    if not two:
+                        with torch.cuda.graph(graph):
+                            bl1.copy_(sl1)
+                            bL.copy_(sL)
+                            flags = self._step_device(X, Y, lr, jitter, routes, inplace=True)
+                        entry = dict(graph=graph, flags=flags, state=(sl1, sL), backup=(bl1, bL), buf=buf)
+                    else:
+                        P_, M_ = self.num_latent_gps, self.num_inducing
+                        with torch.cuda.graph(graph):
+                            bl1.copy_(sl1)
+                            bL.copy_(sL)
+                            st, ops = self._step_front(X, Y, lr, jitter, routes)
+                            if ops.get("epi_branch") is not None:  # the side stream's branch ends inside THIS graph
+                                ops["epi_branch"].join()
+                            packed = D_.pack_stats(st, True, eng)
+                        tail = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(tail, pool=graph.pool()):
+                            acc2, acc1, _, nonpos, rows = D_.unpack_stats(packed, P_, M_, True, eng)
+                            flags = self._apply_site_update(None, ops, lr, jitter, inplace=True,
+                                                            reduced=(acc2, acc1, nonpos, rows))
+                        entry = dict(graph=graph, tail=tail, packed=packed, ops=ops, flags=flags, state=(sl1, sL),
+                                     backup=(bl1, bL), buf=buf)
+                    if hasattr(self.likelihood, "rng_state"):  # the map's nodes hold this tensor's address
+                        entry["lik_state"] = self.likelihood.rng_state(self.device)
+                    self._graphs[key] = entry
             except RuntimeError as exc:
                 # What torch / HIP raise when an operation is not permitted under stream capture: never try this key again
                 # and say so once (anything else -- a TypeError, a KeyError -- is a bug and propagates).  With several ranks
@@ -1268,8 +1245,6 @@ class t_SVGP(base_SVGP):
                               RuntimeWarning, stacklevel=3)
                 self._graphs[key] = "seen-uncapturable"
                 entry = None
-            finally:
-                eng._buf, eng._b_tag = saved_buf, saved_tag
             if entry is None:
                 return False
         elif not isinstance(entry, dict):
@@ -1335,8 +1310,8 @@ class t_SVGP(base_SVGP):
         st, ops = self._step_front(X, Y, 0.0, jitter, routes)
         acc2, acc1, _, nonpos, _, _ = D_.reduce_stats(st, self.num_latent_gps, self.num_inducing, True, self._reduce(),
                                                       self._get_engine())
-        if ops.get("epi_event") is not None:
-            torch.cuda.current_stream(self.device).wait_event(ops["epi_event"])
+        if ops.get("epi_branch") is not None:
+            ops["epi_branch"].join()
         G1, G0 = self._map_sums(ops, acc2, acc1)
         self._check_step(ops, nonpos)
         return G0, 0.5 * (G1 + G1.transpose(-1, -2))
@@ -1351,8 +1326,8 @@ class t_SVGP(base_SVGP):
             acc2, acc1, nonpos, rows = reduced
         else:
             acc2, acc1, _, nonpos, rows, _ = D_.reduce_stats(st, P, M, True, self._reduce(), eng)
-        if ops.get("epi_event") is not None:  # L L^T, K_uu beta, K9^-1 from the side stream (see _site_operands)
-            torch.cuda.current_stream(self.device).wait_event(ops["epi_event"])
+        if ops.get("epi_branch") is not None:  # L L^T, K_uu beta, K9^-1 from the side stream (see _site_operands)
+            ops["epi_branch"].join()
 
         G1, G0 = self._map_sums(ops, acc2, acc1)
         # tsvgp.py:286-300 in one pass (tsvgp_site_update_f64): with lambda_2 = -1/2 L L^T the matrix to factor is
