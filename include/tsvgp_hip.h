@@ -590,6 +590,24 @@ int tsvgp_pathwise_f64(int kind, const double *X, const double *Z, const double 
                        const double *W, const double *V, double *out, int64_t N, int M, int L, int D, int S, int64_t ldo,
                        void *stream);
 
+/* (10b) The vector-Jacobian product of (10) with respect to the rows of X: with cotangents C [S x ldc] on out,
+ *        dX[n, d] = sum_s C[s, n] * d out[s, n] / d x_nd
+ *                 = inv_ls_d * (  sum_{l < L} Omega[l, d] * ( cos(a_nl) * (sum_s C[s, n] W[s, L + l]) - sin(a_nl) * (sum_s C[s, n] W[s, l]) )
+ *                               + sum_{m < M} 2 (x~_nd - z~_md) * variance * k'_kind(s2_nm) * (sum_s C[s, n] V[s, m]) ),
+ *        a_nl = Omega_l . x~_n,   x~ = x * inv_ls,   z~ = z * inv_ls,   s2_nm = |x~_n - z~_m|^2,
+ *     k' the derivative of the profile with respect to s2, the device function of tsvgp_kernel_grad_* (the Matern kernels take
+ *     r = sqrt(max(s2, 1e-36)): on an inducing point the factor x~ - z~ makes the term an exact zero, no special case).  X, Z,
+ *     inv_ls, Omega, W, V exactly as in (10); C [S x ldc], ldc >= N, columns >= N are not read; dX [N x D] row-major and contiguous
+ *     like X, rows >= N of a larger buffer are not written.  M = 0 with V (and Z) NULL differentiates the prior part alone.  The
+ *     limits of (10) on N, M, L, D, S and variance; TSVGP_EINVAL otherwise, before any launch.  A full Jacobian [S, N, D] would
+ *     need S D sums per row; the product with C needs D and shares the sine / cosine pair and the profile among the samples as
+ *     (10) does.  One thread per row: x~, the row's S cotangents and its D sums stay in registers, the LDS stages are those of
+ *     (10).  A row's dX depends on that row, its column of C and the operands alone -- not on N, on the other rows or on the launch
+ *     geometry: the same row gets the same bits in any call.  No atomics, a summation order fixed by (L, M). */
+int tsvgp_pathwise_vjp_f64(int kind, const double *X, const double *Z, const double *inv_ls, double variance, const double *Omega,
+                           const double *W, const double *V, const double *C, int64_t ldc, double *dX, int64_t N, int M, int L,
+                           int D, int S, void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

@@ -196,6 +196,8 @@ _PROTOTYPES = {
                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_pathwise_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                    c_int, c_int, c_int, c_int64, c_void_p]),
+    "tsvgp_pathwise_vjp_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

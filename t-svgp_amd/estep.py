@@ -1334,14 +1334,9 @@ class EStepEngine:
                     "tsvgp_mc_normals")
         return out
 
-    def pathwise(self, X, Z, kernel, Omega, W, V=None) -> torch.Tensor:
-        """S pathwise function draws of one latent GP at the rows of X (``tsvgp_pathwise_f64``), [S, N] fp64:
-
-            out[s, n] = sum_l (W[s, l] cos(Omega_l . x~_n) + W[s, L + l] sin(Omega_l . x~_n)) + sum_m V[s, m] k(x_n, z_m)
-
-        X [N, D <= 32], Z [M, D], ``kernel`` one stationary kernel (lengthscales, variance and profile of k and of x~ = x / l),
-        Omega [L, D], W [S, 2 L] (already scaled by sqrt(variance / L)), V [S, M]; ``V=None``: the first sum alone (Z is not read).
-        fp64 whatever the engine's compute dtype; launches on the current stream, ``PATHWISE_MAX_S`` samples per launch."""
+    def _pathwise_operands(self, X, Z, kernel, Omega, W, V):
+        """The operands of ``pathwise`` / ``pathwise_vjp`` on the device in fp64, checked: (X, Z, Omega, W, V, inv_ls, variance, N, M,
+        L, D, S), M = 0 and Z = V = None without an update."""
         if isinstance(kernel, SeparateIndependent):
             raise ValueError("pathwise: one kernel per call; pass the latent's own kernel")
         f64 = lambda t: t.to(device=self.device, dtype=torch.float64).contiguous()
@@ -1363,17 +1358,54 @@ class EStepEngine:
             M = Z.shape[0]
             if Z.dim() != 2 or Z.shape[1] != D or tuple(V.shape) != (S, M):
                 raise ValueError(f"pathwise: Z must be [M, {D}] and V [S, M] = [{S}, {M}], got {tuple(Z.shape)} and {tuple(V.shape)}")
+        if M == 0:
+            Z = V = None
         inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
-        variance = kernel.variance.item()
+        return X, Z, Omega, W, V, inv_ls, kernel.variance.item(), N, M, L, D, S
+
+    def pathwise(self, X, Z, kernel, Omega, W, V=None) -> torch.Tensor:
+        """S pathwise function draws of one latent GP at the rows of X (``tsvgp_pathwise_f64``), [S, N] fp64:
+
+            out[s, n] = sum_l (W[s, l] cos(Omega_l . x~_n) + W[s, L + l] sin(Omega_l . x~_n)) + sum_m V[s, m] k(x_n, z_m)
+
+        X [N, D <= 32], Z [M, D], ``kernel`` one stationary kernel (lengthscales, variance and profile of k and of x~ = x / l),
+        Omega [L, D], W [S, 2 L] (already scaled by sqrt(variance / L)), V [S, M]; ``V=None``: the first sum alone (Z is not read).
+        fp64 whatever the engine's compute dtype; launches on the current stream, ``PATHWISE_MAX_S`` samples per launch."""
+        X, Z, Omega, W, V, inv_ls, variance, N, M, L, D, S = self._pathwise_operands(X, Z, kernel, Omega, W, V)
         out = torch.empty((S, N), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             for s0 in range(0, S, B.PATHWISE_MAX_S):
                 sc = min(B.PATHWISE_MAX_S, S - s0)
                 self._launch("tsvgp_pathwise", lambda: self.lib.tsvgp_pathwise_f64(
-                    int(kernel.kind), X.data_ptr(), _ptr(Z if M else None), inv_ls.data_ptr(), variance, Omega.data_ptr(),
+                    int(kernel.kind), X.data_ptr(), _ptr(Z), inv_ls.data_ptr(), variance, Omega.data_ptr(),
                     W[s0:s0 + sc].data_ptr(), _ptr(V[s0:s0 + sc] if M else None), out[s0:s0 + sc].data_ptr(), N, M, L, D, sc, N,
                     self._stream()))
         return out
+
+    def pathwise_vjp(self, X, Z, kernel, Omega, W, V, C) -> torch.Tensor:
+        """The vector-Jacobian product of ``pathwise`` with respect to X (``tsvgp_pathwise_vjp_f64``), [N, D] fp64:
+
+            dX[n, d] = sum_s C[s, n] d out[s, n] / d X[n, d]
+
+        The operands of ``pathwise`` (``V=None``: the prior part alone) and the cotangents C [S, N].  ``PATHWISE_MAX_S`` samples
+        per launch on the current stream; the chunks' results are added in chunk order on the device (no host read, the same bits
+        every time)."""
+        X, Z, Omega, W, V, inv_ls, variance, N, M, L, D, S = self._pathwise_operands(X, Z, kernel, Omega, W, V)
+        if not isinstance(C, torch.Tensor) or tuple(C.shape) != (S, N):
+            raise ValueError(f"pathwise_vjp: C must be [S, N] = [{S}, {N}], got {tuple(getattr(C, 'shape', ()))}")
+        C = C.to(device=self.device, dtype=torch.float64).contiguous()
+        dX = torch.empty((N, D), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            for s0 in range(0, S, B.PATHWISE_MAX_S):
+                sc = min(B.PATHWISE_MAX_S, S - s0)
+                part = dX if s0 == 0 else torch.empty_like(dX)
+                self._launch("tsvgp_pathwise_vjp", lambda: self.lib.tsvgp_pathwise_vjp_f64(
+                    int(kernel.kind), X.data_ptr(), _ptr(Z), inv_ls.data_ptr(), variance, Omega.data_ptr(),
+                    W[s0:s0 + sc].data_ptr(), _ptr(V[s0:s0 + sc] if M else None), C[s0:s0 + sc].data_ptr(), N, part.data_ptr(),
+                    N, M, L, D, sc, self._stream()))
+                if s0 > 0:
+                    dX += part
+        return dX
 
     # ------------------------------------------------------------------ per-datum diagonal sites (t_SVGP_sites)
     def project_diag(self, X, Z, kernel, w1, w2):

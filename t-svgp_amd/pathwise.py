@@ -72,14 +72,66 @@ class FunctionSamples:
         self.num_features = int(Omega[0].shape[0])
         self.seed, self.draw = int(seed), int(draw)
 
-    def __call__(self, Xnew) -> torch.Tensor:
-        eng = self._engine
+    def _rows(self, Xnew) -> torch.Tensor:
+        """Xnew on the engine's device in fp64, checked (torch's own ``.to``: gradients pass through it to the caller's leaf)."""
         X = Xnew if isinstance(Xnew, torch.Tensor) else torch.as_tensor(Xnew)
-        X = X.to(device=eng.device, dtype=torch.float64)
+        X = X.to(device=self._engine.device, dtype=torch.float64)
         if X.dim() != 2 or X.shape[1] != self.Z.shape[1]:
             raise ValueError(f"Xnew must be [N, D] = [N, {self.Z.shape[1]}], got {tuple(X.shape)}")
+        return X
+
+    def _evaluate(self, X) -> torch.Tensor:
+        eng = self._engine
         f = [eng.pathwise(X, self.Z, k, self.Omega[p], self.W[p], self._Vt[p]) for p, k in enumerate(self._kernels)]
         return torch.stack(f, dim=2)  # [S, N, P]
+
+    def __call__(self, Xnew) -> torch.Tensor:
+        """The draws at the rows of Xnew, [S, N, P].  With grad mode on and ``Xnew`` a tensor that requires grad, the result takes
+        part in autograd: the same values bit for bit, and a backward that is one ``vjp`` (first derivatives only: a second
+        derivative raises torch's error for once-differentiable functions).  No graph is kept between calls."""
+        X = self._rows(Xnew)
+        if torch.is_grad_enabled() and X.requires_grad:
+            return _Evaluate.apply(X, self)
+        return self._evaluate(X)
+
+    def vjp(self, Xnew, cotangent) -> torch.Tensor:
+        """sum_{s, p} cotangent[s, n, p] d f_{s, p}(x_n) / d x_n, [N, D] fp64 on the model's device: the vector-Jacobian product of
+        ``fs(Xnew)`` with a cotangent [S, N, P], one ``tsvgp_pathwise_vjp_f64`` per latent (no [S, N, D] Jacobian, no N-sized
+        matrix), summed over the latents in their order.  Exact, not a finite difference, and the same bits for the same row
+        and cotangent column whatever else is in the call.  A draw is differentiable everywhere for every kernel offered: the
+        random-feature part is smooth, and the update term sum_m k(x, z_m) V[s, m] is at least C^1 (the first odd power of
+        |x~ - z~| in the profile is the third for Matern-3/2 and the fifth for Matern-5/2; the squared exponential is smooth): at
+        an inducing point the gradient of its own term is zero.  Matern-1/2, whose profile has a kink at every inducing point,
+        is not offered."""
+        eng = self._engine
+        X = self._rows(Xnew).detach()
+        C = cotangent if isinstance(cotangent, torch.Tensor) else torch.as_tensor(cotangent)
+        C = C.detach().to(device=eng.device, dtype=torch.float64)
+        want = (self.num_samples, X.shape[0], len(self._kernels))
+        if tuple(C.shape) != want:
+            raise ValueError(f"cotangent must be [S, N, P] = {list(want)}, got {tuple(C.shape)}")
+        dX = None
+        for p, k in enumerate(self._kernels):
+            part = eng.pathwise_vjp(X, self.Z, k, self.Omega[p], self.W[p], self._Vt[p], C[:, :, p])
+            dX = part if dX is None else dX.add_(part)
+        return dX
+
+
+class _Evaluate(torch.autograd.Function):
+    """``FunctionSamples.__call__`` for an input that requires grad: forward is the plain evaluation, backward one ``vjp`` at the
+    saved (already converted) input."""
+
+    @staticmethod
+    def forward(ctx, X, fs):
+        ctx.fs = fs
+        ctx.save_for_backward(X)
+        return fs._evaluate(X.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (X,) = ctx.saved_tensors
+        return ctx.fs.vjp(X, grad), None
 
 
 def _private_copy(kernel):
