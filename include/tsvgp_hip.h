@@ -608,6 +608,37 @@ int tsvgp_pathwise_vjp_f64(int kind, const double *X, const double *Z, const dou
                            const double *W, const double *V, const double *C, int64_t ldc, double *dX, int64_t N, int M, int L,
                            int D, int S, void *stream);
 
+/* (11) Input gradient of the marginal moments of one latent GP (predict_f under torch autograd; GPflow users get it from
+ *     tf.GradientTape over predict_f [ext]).  With mean[n] = k_n^T beta, var[n] = variance - k_n^T Q k_n, k_n = K(Z, x_n), Q
+ *     symmetric, cotangents cm, cv of (mean, var) and U = K(X, Z) Q (the caller's GEMM):
+ *        dX[n, d] (+)= sum_{m < M} (cm[n] beta[m] - 2 cv[n] U[n, m]) * variance * f'(s_nm) * 2 s_d * inv_ls_d,
+ *        s_d = (x_nd - z_md) * inv_ls_d,   s_nm = sum_d s_d^2,   K = variance * f(s),
+ *     f' the device function of tsvgp_kernel_grad_* (the Matern profiles take r = sqrt(max(s, 1e-36)): on an inducing point the
+ *     factor s_d makes the term an exact zero) -- the dZ term of (8) summed over m per row instead of over n per column.
+ *     One latent per call.  X [N x D], Z [M x D], inv_ls [D] row-major and contiguous; U [N x ldu]; cm, cv with element stride
+ *     cstride (a column of an [N x P] array), beta with stride bstride; dX [N x D] fp64, row-major and contiguous: accumulate = 0
+ *     writes it, accumulate != 0 adds to what is there; rows >= N of a larger buffer are not written.  Columns >= M of U are
+ *     not read, whatever they hold; X, cm, cv are not read beyond N.
+ *     TSVGP_EINVAL before any launch: a NULL pointer; N <= 0; M <= 0; D < 1 or D > 32; a kind other than SE, Matern-3/2,
+ *     Matern-5/2; cstride <= 0 or bstride <= 0; ldu < M; and what the 16-byte row loads of U need: U off a 16-byte boundary
+ *     or ldu no multiple of 16 / sizeof(T) (2 doubles, 4 floats).
+ *     One launch.  Lanes run along m, 16 bytes of a row of U each (a wave sweeps 128 columns in fp64, 256 in fp32), a workgroup
+ *     takes tsvgp_moments_vjp_rows(D) rows; z~ and beta sit in LDS, tsvgp_moments_vjp_stage_*(D) columns at a time (-1 from
+ *     either: D out of range): a wider M is walked in stages of that many columns inside the kernel, in column order, and dX
+ *     receives the whole sum at the end -- accumulate != 0 gives old + sum, bit for bit what a write followed by an addition
+ *     gives.  Arithmetic in T, accumulation in fp64, no atomics, every sum's order fixed by (M, D): dX[n] has the same bits
+ *     whatever N is, wherever row n stands and whatever the other rows hold.  HBM traffic is one read of U, but the launch is bound by instruction issue, not by HBM:
+ *     measured 4 (fp64, D = 8) and 8 (fp32, D = 16) times the time of that read at N = 1e6, M = 1024. */
+int tsvgp_moments_vjp_rows(int D);
+int tsvgp_moments_vjp_stage_f64(int D);
+int tsvgp_moments_vjp_stage_f32(int D);
+int tsvgp_moments_vjp_f64(int kind, const double *X, const double *Z, const double *inv_ls, double variance, const double *U,
+                          int64_t ldu, const double *cm, const double *cv, int cstride, const double *beta, int bstride, int64_t N,
+                          int M, int D, double *dX, int accumulate, void *stream);
+int tsvgp_moments_vjp_f32(int kind, const float *X, const float *Z, const float *inv_ls, float variance, const float *U, int64_t ldu,
+                          const float *cm, const float *cv, int cstride, const float *beta, int bstride, int64_t N, int M, int D,
+                          double *dX, int accumulate, void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

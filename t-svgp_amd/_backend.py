@@ -198,6 +198,13 @@ _PROTOTYPES = {
                                    c_int, c_int, c_int, c_int64, c_void_p]),
     "tsvgp_pathwise_vjp_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "tsvgp_moments_vjp_rows": (c_int, [c_int]),
+    "tsvgp_moments_vjp_stage_f64": (c_int, [c_int]),
+    "tsvgp_moments_vjp_stage_f32": (c_int, [c_int]),
+    "tsvgp_moments_vjp_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "tsvgp_moments_vjp_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -742,6 +742,96 @@ class EStepEngine:
               + torch.einsum("md,m->d", Zs64 * Zs64, colsum)) * il
         return vpart.sum(), dl, dZ
 
+    def moments_vjp(self, X, Z, kernel, U, cm, cv, beta, dX, accumulate=False):
+        """Input gradient of the marginal moments of ONE latent GP (``tsvgp_moments_vjp_*``), into dX [N, D] fp64 (contiguous):
+
+            dX[n, d] (+)= sum_m (cm[n] beta[m] - 2 cv[n] U[n, m]) dK[n, m] / dX[n, d],     U = K(X, Z) Q
+
+        X [N, D <= 32], Z [M, D]; U [>= N, ldu >= M] in the compute dtype with 16-byte aligned rows (the engine's [Np, Mp] buffers
+        are); cm, cv: 1-D views of N elements in the compute dtype with one element stride (columns of an [N, P] array); beta [M].
+        ``accumulate``: add to dX instead of writing it.  One launch on the current stream."""
+        T, dev = self.dtype, self.device
+        X = X.to(device=dev, dtype=T).contiguous()
+        Z = Z.to(device=dev, dtype=T).contiguous()
+        N, D = X.shape
+        M = Z.shape[0]
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"moments_vjp: 1 <= D <= {MAX_INPUT_DIM} (the compile-time sizes of tsvgp_moments_vjp_*), got {D}")
+        if Z.shape[1] != D or U.dim() != 2 or U.dtype != T or U.shape[0] < N or U.shape[1] < M or U.stride(1) != 1:
+            raise ValueError(f"moments_vjp: Z must be [M, {D}] and U [>= {N}, >= {M}] in {T}, got {tuple(Z.shape)} and {tuple(U.shape)}")
+        if not (cm.dim() == cv.dim() == 1 and cm.shape[0] == cv.shape[0] == N and cm.dtype == cv.dtype == T
+                and (N == 1 or cm.stride(0) == cv.stride(0) >= 1)):
+            raise ValueError(f"moments_vjp: cm and cv must be 1-D views of N = {N} elements in {T} with one stride")
+        if tuple(dX.shape) != (N, D) or dX.dtype != torch.float64 or not dX.is_contiguous():
+            raise ValueError(f"moments_vjp: dX must be a contiguous fp64 [{N}, {D}]")
+        bt = beta.to(device=dev, dtype=T).contiguous()
+        if tuple(bt.shape) != (M,):
+            raise ValueError(f"moments_vjp: beta must be [M] = [{M}], got {tuple(bt.shape)}")
+        inv_ls = kernel.inv_lengthscales(D, T, dev)
+        cstride = max(int(cm.stride(0)), 1)
+        with torch.cuda.device(dev):
+            self._launch("tsvgp_moments_vjp", lambda: self._fn("tsvgp_moments_vjp")(
+                int(kernel.kind), X.data_ptr(), Z.data_ptr(), inv_ls.data_ptr(), kernel.variance.item(), U.data_ptr(), U.stride(0),
+                cm.data_ptr(), cv.data_ptr(), cstride, bt.data_ptr(), 1, N, M, D, dX.data_ptr(), 1 if accumulate else 0,
+                self._stream()))
+        return dX
+
+    def predict_vjp(self, X, Z, kernel, beta, Q, cm, cv=None) -> torch.Tensor:
+        """The vector-Jacobian product of the marginal prediction with respect to the rows of X, [N, D] fp64:
+
+            mean[n, p] = k_n^T beta_p,   var[n, p] = k(x, x) - k_n^T Q_p k_n,   dX = sum_p (cm_p d mean_p + cv_p d var_p) / dX
+
+        X [N, D <= 32], Z [M, D]; ``kernel``: one kernel shared by the latents, a ``SeparateIndependent`` or a list of one kernel
+        per latent; beta [M, P] and Q [P, M, M] (symmetric) fp64; cm, cv [N, P] (``cv=None``: zeros, the mean alone).
+        Per kernel one K(X, Z) fill, per latent U = K_fu Q_p by the BLAS library into the engine's "U" buffer (the dense branch of
+        ``t_SVGP.elbo_and_grads``, in the compute dtype) and one ``moments_vjp``, latents in index order.  The N-sized memory is
+        the engine's reusable "Kfu" and "U" buffers."""
+        T, dev = self.dtype, self.device
+        X = X.detach().to(device=dev, dtype=T).contiguous()
+        Z = Z.detach().to(device=dev, dtype=T).contiguous()
+        if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != X.shape[1] or X.shape[0] < 1:
+            raise ValueError(f"predict_vjp: X must be [N >= 1, D] and Z [M, D] with equal D, got {tuple(X.shape)} and {tuple(Z.shape)}")
+        N, D = X.shape
+        M = Z.shape[0]
+        if D > MAX_INPUT_DIM:
+            raise ValueError(f"predict_vjp: the input dimension is limited to {MAX_INPUT_DIM} (the compile-time sizes of the K(X, Z) "
+                             f"fill and of tsvgp_moments_vjp_*), got D = {D}")
+        beta = beta.detach().to(device=dev, dtype=torch.float64)
+        Q = Q.detach().to(device=dev, dtype=torch.float64)
+        Q = Q[None] if Q.dim() == 2 else Q
+        P = Q.shape[0]
+        if tuple(beta.shape) != (M, P) or tuple(Q.shape) != (P, M, M):
+            raise ValueError(f"predict_vjp: beta must be [M, P] and Q [P, M, M] with M = {M}, got {tuple(beta.shape)} and {tuple(Q.shape)}")
+        # contiguous copies: autograd hands a backward expanded (stride 0) gradients after a plain .sum(), and the launch reads the
+        # columns of both arrays with one element stride
+        cm = cm.detach().to(device=dev, dtype=T).contiguous()
+        if tuple(cm.shape) != (N, P) or (cv is not None and tuple(cv.shape) != (N, P)):
+            raise ValueError(f"predict_vjp: the cotangents must be [N, P] = [{N}, {P}]")
+        cv = torch.zeros_like(cm) if cv is None else cv.detach().to(device=dev, dtype=T).contiguous()
+        if isinstance(kernel, SeparateIndependent):
+            kernels = list(kernel.kernels)
+        elif isinstance(kernel, (list, tuple)):
+            kernels = list(kernel)
+        else:
+            kernels = [kernel]
+        if len(kernels) not in (1, P):
+            raise ValueError(f"predict_vjp: one kernel or one per latent (P = {P}), got {len(kernels)}")
+        if len(kernels) == P and all(k is kernels[0] for k in kernels):
+            kernels = kernels[:1]  # the same object for every latent: one fill
+        Np, Mp = B.round_up(N), B.round_up(M)
+        self._b_tag = None  # "Kfu" is rewritten below
+        self._side.wait_stale()
+        Kfu = self._get("Kfu", (Np, Mp), T)
+        Ubuf = self._get("U", (Np, Mp), T)
+        dX = torch.empty((N, D), dtype=torch.float64, device=dev)
+        for p in range(P):
+            kern = kernels[p if len(kernels) > 1 else 0]
+            if p == 0 or len(kernels) > 1:
+                self.se_fill(X, Z, kern.inv_lengthscales(D, T, dev), kern.variance.item(), Kfu, kern.kind)
+            torch.mm(Kfu, self._pad_square(0.5 * (Q[p] + Q[p].T), Mp, "pad_Q"), out=Ubuf)
+            self.moments_vjp(X, Z, kern, Ubuf, cm[:, p], cv[:, p], beta[:, p], dX, accumulate=p > 0)
+        return dX
+
     def selftest_mfma(self, dtype=None):
         """Runs one MFMA and returns (a, b, c) for a host-side check of the fragment maps."""
         dtype = dtype or self.dtype

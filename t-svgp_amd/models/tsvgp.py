@@ -65,6 +65,31 @@ def _ktmv(K: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     return bmv(K, v, transpose=True)
 
 
+class _PredictF(torch.autograd.Function):
+    """``predict_f`` for an input that requires grad: forward is the plain prediction (the same launches, the same bits),
+    backward one ``EStepEngine.predict_vjp`` on what forward captured -- all of it M-sized: beta [M, P], Q [P, M, M], a copy of Z
+    and private copies of the kernels, so a parameter assigned between forward and backward does not reach the gradient."""
+
+    @staticmethod
+    def forward(ctx, X, model):
+        from ..pathwise import _private_copy
+
+        mean, var, beta, Q = model._predict_marginal(X.detach(), want_operands=True)
+        ctx.engine = model._get_engine()
+        if isinstance(model.kernel, SeparateIndependent):
+            ctx.kernels = [_private_copy(k) for k in model.kernel.kernels]
+        else:
+            ctx.kernels = [_private_copy(model.kernel)]
+        ctx.save_for_backward(X, model._Z().detach().clone(), beta.detach().clone(), Q.detach().clone())
+        return mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mean, grad_var):
+        X, Z, beta, Q = ctx.saved_tensors
+        return ctx.engine.predict_vjp(X, Z, ctx.kernels, beta, Q, grad_mean, grad_var), None
+
+
 class base_SVGP(abc.ABC):
     """Mirror of the reference's ``base_SVGP`` (tsvgp.py:32-114): ELBO, prior KL and predict_f for a model that
     exposes q(u) through ``get_mean_chol_cov_inducing_posterior``."""
@@ -221,6 +246,47 @@ class base_SVGP(abc.ABC):
         if advance:
             self._function_draw = draw + 1  # (a call that raised leaves the counter alone)
         return fs
+
+    # -- input gradients of the marginal prediction ---------------------------------------------------------------
+    def _predict_marginal(self, Xd, want_operands=False):
+        """(mean, var) [N, P] fp64 of ``predict_f`` at the rows Xd (on the device); ``want_operands``: also (beta [M, P],
+        Q [P, M, M]) with mean = k^T beta and var = k(x, x) - k^T Q k on the route the call took."""
+        raise NotImplementedError
+
+    def _predict_operands(self):
+        """(beta [M, P], Q [P, M, M]) of ``_predict_marginal`` without an N-pass, factorisation statuses checked."""
+        raise NotImplementedError
+
+    def _grad_rows(self, Xnew):
+        """Xnew on the device in fp64 through torch's own (differentiable) conversion when ``predict_f`` is to take part in
+        autograd -- a tensor that requires grad, grad mode on -- else None."""
+        if isinstance(Xnew, torch.Tensor) and Xnew.requires_grad and torch.is_grad_enabled():
+            return Xnew.to(device=self.device, dtype=torch.float64)
+        return None
+
+    def predict_f_vjp(self, Xnew, cot_mean, cot_var=None):
+        """sum_p (cot_mean[n, p] d mean[n, p] + cot_var[n, p] d var[n, p]) / d Xnew[n, :], [N, D] fp64 on the model's device: the
+        vector-Jacobian product of ``predict_f(Xnew)`` (default flags) with cotangents [N, P] on its two outputs
+        (``cot_var=None``: the mean alone).  Exact, not a finite difference: with mean = k^T beta and var = k(x, x) - k^T Q k on
+        the route ``predict_f`` takes, one K(Xnew, Z) fill per kernel, one GEMM U = K Q_p and one ``tsvgp_moments_vjp_*`` launch
+        per latent (``EStepEngine.predict_vjp``); input dimension D <= 32.  ``predict_f`` itself takes part in torch autograd
+        with respect to a Xnew that requires grad, and ``predict_y`` / ``predict_log_density`` with it."""
+        X = Xnew if isinstance(Xnew, torch.Tensor) else torch.as_tensor(np.asarray(Xnew))
+        X = X.detach().to(device=self.device, dtype=torch.float64)
+        P = int(self.num_latent_gps)
+        as_cot = lambda c: (c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))).detach().to(
+            device=self.device, dtype=torch.float64)
+        cm = as_cot(cot_mean)
+        cv = None if cot_var is None else as_cot(cot_var)
+        if X.dim() != 2 or tuple(cm.shape) != (X.shape[0], P) or (cv is not None and tuple(cv.shape) != (X.shape[0], P)):
+            raise ValueError(f"predict_f_vjp: Xnew must be [N, D] and the cotangents [N, P] = [N, {P}], got {tuple(X.shape)}, "
+                             f"{tuple(cm.shape)}" + ("" if cv is None else f" and {tuple(cv.shape)}"))
+        if X.shape[1] > 32:
+            raise ValueError(f"predict_f_vjp: the input dimension is limited to 32 (the compile-time sizes of the K(X, Z) fill and "
+                             f"of tsvgp_moments_vjp_*), got D = {X.shape[1]}")
+        eng = self._get_engine()
+        beta, Q = self._predict_operands()
+        return eng.predict_vjp(X, self._Z(), self.kernel, beta, Q, cm, cv)
 
     def maximum_log_likelihood_objective(self, data):
         return self.elbo(data)
@@ -677,6 +743,8 @@ class t_SVGP(base_SVGP):
         """Posterior prediction at new input Xnew [N, D] (tsvgp.py:97-114): mean = k^T beta, var = knn - |D k|^2 on
         K(Xnew, Z) itself -- the reference's conditional only involves K_uu + 1e-6 I (tsvgp.py:209-211), and so does this
         form (no factor of K_uu + 1e-9 I, no N-sized whitening).
+        With the default flags, grad mode on and ``Xnew`` a tensor that requires grad, the result takes part in torch autograd with
+        respect to Xnew: the same values bit for bit, a backward that is one ``EStepEngine.predict_vjp`` (first derivatives only).
         With ``full_cov`` the joint covariance over the rows of Xnew, cov [P, N, N] = K(Xnew, Xnew) - (D k)^T (D k) per latent
         (``EStepEngine.full_cov``); with ``full_output_cov`` [N, P, P], diagonal: the latents are independent a posteriori.  With
         more than one rank Xnew is local: there is no collective."""
@@ -684,12 +752,26 @@ class t_SVGP(base_SVGP):
             raise NotImplementedError(self._BOTH_COV)
         if full_cov:
             return self._joint(Xnew)
-        Xnew = self._as_device(Xnew)
+        Xg = None if full_output_cov else self._grad_rows(Xnew)
+        if Xg is not None:
+            return _PredictF.apply(Xg, self)
+        mean, var = self._predict_marginal(self._as_device(Xnew))
+        return mean, (torch.diag_embed(var) if full_output_cov else var)
+
+    def _predict_marginal(self, Xd, want_operands=False):
         ops = self._site_operands()
-        st = self._get_engine().run(Xnew, None, ops["Z"], self.kernel, moment_Tm=ops["D"], moment_mode=ops["moment_mode"],
+        st = self._get_engine().run(Xd, None, ops["Z"], self.kernel, moment_Tm=ops["D"], moment_mode=ops["moment_mode"],
                                     gamma=ops["beta"], want_moments=True)
         self._check_step(ops, st.nonpos)
-        return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
+        if want_operands:
+            return st.mean, st.var, ops["beta"], ops["D"].transpose(-1, -2) @ ops["D"]
+        return st.mean, st.var
+
+    def _predict_operands(self):
+        ops = self._site_operands()
+        Q = ops["D"].transpose(-1, -2) @ ops["D"]  # as elbo_and_grads
+        self._check_step(ops, torch.zeros(1, dtype=torch.float64, device=self.device))
+        return ops["beta"], Q
 
     def _joint(self, Xnew, padded=False, engine=None):
         ops = self._site_operands()

@@ -40,7 +40,7 @@ from ..base import default_jitter, to_tensor
 from ..estep import EStepStats
 from ..kernels import SeparateIndependent
 from ..sites import DiagSites
-from .tsvgp import base_SVGP
+from .tsvgp import _PredictF, base_SVGP
 from .tsvgp_white import t_SVGP_white
 
 
@@ -61,6 +61,7 @@ class t_SVGP_sites(base_SVGP):
     _use_direct = t_SVGP_white._use_direct
     _routed = t_SVGP_white._routed
     _white_joint = t_SVGP_white._joint
+    _beta_q = staticmethod(t_SVGP_white._beta_q)
 
     def __init__(self, data, kernel, likelihood, inducing_variable, *, mean_function=None, num_latent_gps: int = 1,
                  lambda_1=None, lambda_2=None, num_latent=1, compute_dtype=None, device=None, projection="auto",
@@ -182,21 +183,25 @@ class t_SVGP_sites(base_SVGP):
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """tsvgp_sites.py:180-191: gpflow conditional(q_mu, q_sqrt = chol S, white=False), which is
         mean = k^T R^-1 l, var = kff - k^T (K6^-1 - R^-1) k with R = K6 + L + 1e-9 I: t_SVGP_white's moments on (l, L).
-        ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1]."""
+        ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1].  With the default flags and a Xnew that
+        requires grad the result takes part in torch autograd (``t_SVGP.predict_f``)."""
         if full_cov and full_output_cov:
             raise NotImplementedError(self._BOTH_COV)
         if full_cov:
             return self._joint(Xnew)
+        Xg = None if full_output_cov else self._grad_rows(Xnew)
+        if Xg is not None:
+            return _PredictF.apply(Xg, self)
+        mean, var = self._predict_marginal(self._as_device(Xnew))
+        return mean, (torch.diag_embed(var) if full_output_cov else var)
+
+    def _predict_marginal(self, Xd, want_operands=False):
         l, L, _ = self._project()
-        Xd = self._as_device(Xnew)
+        return t_SVGP_white._predict_marginal(self, Xd, want_operands, l, L)
 
-        def go(direct, two_product):
-            ops = self._operands(lambda_1=l, lambda_2=L, direct=direct, two_product=two_product)
-            st = self._run(Xd, None, ops, B.LIK_NONE, want_moments=True)
-            self._check(ops, st.nonpos)
-            return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
-
-        return self._routed(go)
+    def _predict_operands(self):
+        l, L, _ = self._project()
+        return t_SVGP_white._predict_operands(self, l, L)
 
     def _joint(self, Xnew, padded=False, engine=None):
         """t_SVGP_white's joint covariance on the projected (l, L)."""

@@ -45,7 +45,7 @@ from ..base import default_jitter, to_tensor
 from ..kernels import SeparateIndependent
 from ..sites import DenseSites
 from ..util import cholesky_deferred, cond2_estimate, info_sum, rev_cholesky
-from .tsvgp import base_SVGP
+from .tsvgp import _PredictF, base_SVGP
 
 
 class _DirectRouteFailed(Exception):
@@ -283,18 +283,51 @@ class t_SVGP_white(base_SVGP):
         return 0.5 * (log_det + torch.sum(tmp * tmp) - float(A.shape[0]) + torch.sum(torch.square(LA.transpose(-1, -2) @ Rl)))
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
-        """tsvgp_white.py:122-132.  ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1]."""
+        """tsvgp_white.py:122-132.  ``full_cov``: cov [1, N, N] over the rows of Xnew; ``full_output_cov``: [N, 1, 1].  With the
+        default flags and a Xnew that requires grad the result takes part in torch autograd (``t_SVGP.predict_f``)."""
         if full_cov and full_output_cov:
             raise NotImplementedError(self._BOTH_COV)
         if full_cov:
             return self._joint(Xnew)
-        Xd = self._as_device(Xnew)
+        Xg = None if full_output_cov else self._grad_rows(Xnew)
+        if Xg is not None:
+            return _PredictF.apply(Xg, self)
+        mean, var = self._predict_marginal(self._as_device(Xnew))
+        return mean, (torch.diag_embed(var) if full_output_cov else var)
 
+    @staticmethod
+    def _beta_q(ops):
+        """(beta [M, 1], Q [1, M, M]) of the route ``ops`` was built for: mean = k^T beta, var = kff - k^T Q k.  Direct: the
+        operands act on k already (gamma, Q = Lq Lq^T with moment_Tm = Lq^T).  Whitened: b = U6^-1 k, so beta = U6^-T gamma and
+        Q = U6^-T T^T T U6^-1.  Two-product: var = kff - |b|^2 + |T2 b|^2, Q = U6^-T (I - T2^T T2) U6^-1."""
+        Tm = ops["moment_Tm"][0]
+        inner = Tm.transpose(-1, -2) @ Tm
+        if ops.get("direct"):
+            return ops["gamma"], inner[None]
+        Ui = ops["Uinv6"]
+        if ops.get("two_product"):
+            inner = ops["Id"] - inner
+        return Ui.transpose(-1, -2) @ ops["gamma"], (Ui.transpose(-1, -2) @ inner @ Ui)[None]
+
+    def _predict_marginal(self, Xd, want_operands=False, lambda_1=None, lambda_2=None):
         def go(direct, two_product):
-            ops = self._operands(direct=direct, two_product=two_product)
+            ops = self._operands(lambda_1=lambda_1, lambda_2=lambda_2, direct=direct, two_product=two_product)
             st = self._run(Xd, None, ops, B.LIK_NONE, want_moments=True)
             self._check(ops, st.nonpos)
-            return st.mean, (torch.diag_embed(st.var) if full_output_cov else st.var)
+            return (st.mean, st.var) + (self._beta_q(ops) if want_operands else ())
+
+        return self._routed(go)
+
+    def _predict_operands(self, lambda_1=None, lambda_2=None):
+        """The route is ``_routed``'s, as for ``predict_f``, with the factorisation statuses checked and no N-pass.  Under
+        ``projection="auto"`` a ``predict_f`` whose N-pass finds a non-positive variance on the direct route falls back to the
+        whitened one and marks the direct route failed (``_direct_failed``, until the kernel parameters or Z change): a
+        ``predict_f_vjp`` that FOLLOWS that call takes the whitened operands too and agrees with autograd bit for bit; one made
+        before it differentiates the direct route's (beta, Q), which equal the whitened ones to rounding only."""
+        def go(direct, two_product):
+            ops = self._operands(lambda_1=lambda_1, lambda_2=lambda_2, direct=direct, two_product=two_product)
+            self._check(ops, torch.zeros(1, dtype=torch.float64, device=self.device))
+            return self._beta_q(ops)
 
         return self._routed(go)
 

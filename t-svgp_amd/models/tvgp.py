@@ -49,7 +49,8 @@ from ..sites import DiagSites
 class t_VGP:
     """Class for the t-VGP model (reference src/models/tvgp.py:18-193).  Likelihoods: Gaussian and Bernoulli, the arms of the fused
     row sweep (``tsvgp_vgp_rows_f64``); ``StudentT`` and ``Poisson``, whose map is a kernel of its own behind the moments of
-    ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here."""
+    ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here.  Like ``sample_functions``, the input gradients of the prediction
+    (``predict_f_vjp``, ``predict_f`` under torch autograd) belong to the sparse models only: ``predict_f`` here returns no graph."""
 
     def __init__(self, data, kernel, likelihood, mean_function=None, num_latent=1, *, device=None):
         x_data, y_data = data
