@@ -639,6 +639,37 @@ int tsvgp_moments_vjp_f32(int kind, const float *X, const float *Z, const float 
                           const float *cm, const float *cv, int cstride, const float *beta, int bstride, int64_t N, int M, int D,
                           double *dX, int accumulate, void *stream);
 
+/* (12) Lloyd's k-means for inducing points (the reference's drivers name KMeans(n_clusters=M).fit(X).cluster_centers_ as the
+ *     alternative to Z = X[:M]; [ext]: nothing in the reference runs it): the two N-sized steps of one iteration.  The scaled
+ *     squared distance is the difference form of (9) in its operation order, with no contraction:
+ *        s(x, c) = sum_{q = 0 .. D-1} dd_q^2,   a = x_q * inv_ls_q,  b = c_q * inv_ls_q,  dd = a - b,  s = fma(dd, dd, s).
+ *     tsvgp_kmeans_assign_f64: labels[n] = the lowest m with s(x_n, c_m) minimal, dist[n] = that s, for n < N.  X [N x D],
+ *     C [M x D] row-major and contiguous, inv_ls [D]; labels [N] int32, dist [N]; part [tsvgp_kmeans_assign_parts(N, D)]: one
+ *     partial sum of dist per workgroup of tsvgp_kmeans_assign_rows(D) rows (the sum of the last workgroup runs over its rows
+ *     < N), which the caller adds up for the inertia.  Nothing of size N * M is written or read.  A row's label and distance
+ *     are a function of that row, C and inv_ls alone: the same bits for any N, any position of the row in X and any launch
+ *     geometry, so a call on X + a * D with N = b - a gives the slice [a, b) of the full call.  Lanes run along rows, 2 or 4 rows
+ *     per lane, the centres pass through LDS scaled, tsvgp_kmeans_assign_chunk() at a time, walked in index order with a strict
+ *     comparison.  Compute bound: 3 N M D fp64 operations.  A NaN distance never wins; a row whose distances are all NaN gets
+ *     label 0 and dist +inf.
+ *     tsvgp_kmeans_update_f64: C_new[m] = the mean of the rows X[order[i]], i in [offsets[m], offsets[m + 1]), summed in fp64 in
+ *     an order fixed by the segment's length (256 / DP interleaved slots, DP = D rounded up to a power of two, each added in
+ *     increasing i, then a pairwise tree over the slots) and divided by the count; an empty segment copies C_old[m] bit for bit.
+ *     order [N] int64 (the caller's stable sort of the labels), offsets [M + 1] int64 non-decreasing from 0 to N, C_old and
+ *     C_new [M x D] (distinct buffers).  One workgroup per cluster: the bits of C_new[m] depend on that segment's rows and their
+ *     order alone, not on M, on the other segments or on the grid.  No atomics.  A row number outside [0, N) is not
+ *     dereferenced and a segment is clipped to [0, N).
+ *     Both: N >= 1, M >= 1, 1 <= D <= 32, no NULL pointer, every buffer on the boundary of its element type (8 bytes; labels
+ *     4); TSVGP_EINVAL otherwise, before any launch.  tsvgp_kmeans_assign_parts is -1 for N < 1, D out of range or N beyond
+ *     rows * (2^31 - 1); tsvgp_kmeans_assign_rows is -1 for D out of range.  One launch each. */
+int tsvgp_kmeans_assign_rows(int D);
+int tsvgp_kmeans_assign_chunk(void);
+int64_t tsvgp_kmeans_assign_parts(int64_t N, int D);
+int tsvgp_kmeans_assign_f64(const double *X, const double *C, const double *inv_ls, int32_t *labels, double *dist, double *part,
+                            int64_t N, int M, int D, void *stream);
+int tsvgp_kmeans_update_f64(const double *X, const int64_t *order, const int64_t *offsets, const double *C_old, double *C_new,
+                            int64_t N, int M, int D, void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

@@ -16,7 +16,7 @@ _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libtsvgp_hip.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "tsvgp_hip.h")
-SOURCES = [os.path.join(CSRC, "tsvgp_kernels.hip"), os.path.join(CSRC, "tsvgp_chol.hip")]
+SOURCES = [os.path.join(CSRC, "tsvgp_kernels.hip"), os.path.join(CSRC, "tsvgp_chol.hip"), os.path.join(CSRC, "tsvgp_kmeans.hip")]
 HEADERS = [HEADER_PATH, os.path.join(CSRC, "tsvgp_chol.h")]
 # per-source compiler switches: the small-matrix kernels keep their MFMA accumulators in VGPRs (the AGPR form the compiler
 # picks for a one-wave-per-SIMD kernel ran the panel kernel's dependent MFMA chains ~1.5x slower in a stamped lab build of that
@@ -205,6 +205,11 @@ _PROTOTYPES = {
                                       c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
     "tsvgp_moments_vjp_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                       c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "tsvgp_kmeans_assign_rows": (c_int, [c_int]),
+    "tsvgp_kmeans_assign_chunk": (c_int, []),
+    "tsvgp_kmeans_assign_parts": (c_int64, [c_int64, c_int]),
+    "tsvgp_kmeans_assign_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_kmeans_update_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -1721,3 +1721,58 @@ class EStepEngine:
                 indices.data_ptr(), pivots.data_ptr(), count.data_ptr(), work.data_ptr(), N, M, D, self._stream()))
         n = int(count.item())  # the one device -> host read (it also keeps C alive until the launches are through)
         return indices[:n], pivots[:n], d[:N], n
+
+    def kmeans_assign(self, X, C, inv_ls):
+        """The assignment step of Lloyd's k-means (``tsvgp_kmeans_assign_f64``): for every row of X [N, D <= 32] the lowest m
+        whose centre C[m] is nearest in the scaled coordinates x * inv_ls, without any N x M array.  fp64 whatever the engine's
+        compute dtype.  Returns ``(labels [N] int32, dist [N], inertia 0-dim)`` on the device: dist the minimal scaled squared
+        distance, inertia the sum of the per-workgroup partial sums (one fixed-shape reduction: the same bits in every call of
+        the same N and D)."""
+        if X.dim() != 2 or X.shape[0] < 1 or C.dim() != 2 or C.shape[0] < 1 or C.shape[1] != X.shape[1]:
+            raise ValueError(f"kmeans_assign: X [N >= 1, D] and C [M >= 1, D], got {tuple(X.shape)} and {tuple(C.shape)}")
+        N, D = X.shape
+        M = C.shape[0]
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"kmeans_assign: 1 <= D <= {MAX_INPUT_DIM}, got {D}")
+        X = X.to(device=self.device, dtype=torch.float64).contiguous()
+        C = C.to(device=self.device, dtype=torch.float64).contiguous()
+        inv_ls = inv_ls.to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(inv_ls.shape) != (D,):
+            raise ValueError(f"kmeans_assign: inv_ls must be [{D}], got {tuple(inv_ls.shape)}")
+        nparts = int(self.lib.tsvgp_kmeans_assign_parts(N, D))
+        if nparts <= 0:
+            raise ValueError(f"kmeans_assign: no launch geometry for N = {N}, D = {D}")
+        labels = torch.empty((N,), dtype=torch.int32, device=self.device)
+        dist = torch.empty((N,), dtype=torch.float64, device=self.device)
+        part = torch.empty((nparts,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_kmeans_assign", lambda: self.lib.tsvgp_kmeans_assign_f64(
+                X.data_ptr(), C.data_ptr(), inv_ls.data_ptr(), labels.data_ptr(), dist.data_ptr(), part.data_ptr(), N, M, D,
+                self._stream()))
+        return labels, dist, part.sum()
+
+    def kmeans_update(self, X, labels, C_old):
+        """The centroid step of Lloyd's k-means (``tsvgp_kmeans_update_f64``): C_new[m] = the mean of the rows of X labelled m,
+        summed in a fixed order (no atomics), or C_old[m] bit for bit when there is none.  The segments come from torch: a stable
+        sort of the labels (rows of a cluster in increasing row number), ``bincount`` and ``cumsum``.  Returns
+        ``(C_new [M, D], counts [M] int64)`` on the device."""
+        if X.dim() != 2 or X.shape[0] < 1 or C_old.dim() != 2 or C_old.shape[0] < 1 or C_old.shape[1] != X.shape[1]:
+            raise ValueError(f"kmeans_update: X [N >= 1, D] and C_old [M >= 1, D], got {tuple(X.shape)} and {tuple(C_old.shape)}")
+        N, D = X.shape
+        M = C_old.shape[0]
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"kmeans_update: 1 <= D <= {MAX_INPUT_DIM}, got {D}")
+        if tuple(labels.shape) != (N,):
+            raise ValueError(f"kmeans_update: labels must be [{N}], got {tuple(labels.shape)}")
+        X = X.to(device=self.device, dtype=torch.float64).contiguous()
+        C_old = C_old.to(device=self.device, dtype=torch.float64).contiguous()
+        labels = labels.to(device=self.device)
+        order = torch.sort(labels, stable=True).indices
+        counts = torch.bincount(labels, minlength=M)[:M]  # (a label >= M has no segment: its rows are left out)
+        offsets = torch.zeros((M + 1,), dtype=torch.int64, device=self.device)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        C_new = torch.empty_like(C_old)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_kmeans_update", lambda: self.lib.tsvgp_kmeans_update_f64(
+                X.data_ptr(), order.data_ptr(), offsets.data_ptr(), C_old.data_ptr(), C_new.data_ptr(), N, M, D, self._stream()))
+        return C_new, counts

@@ -103,3 +103,124 @@ def select_inducing_points(X, kernel, num_inducing, *, threshold=0.0, device=Non
     Xd = X.to(engine.device) if isinstance(X, torch.Tensor) else to_tensor(X, device=engine.device)
     indices, pivots, residual, count = engine.greedy_select(Xd, kernel, int(num_inducing), threshold)
     return InducingSelection(Z=Xd[indices], indices=indices, pivots=pivots, residual=residual, trace=residual.sum(), count=count)
+
+
+@dataclass
+class KMeansInducing:
+    """What ``kmeans_inducing_points`` returns (tensors on the device the clustering ran on)."""
+
+    Z: torch.Tensor  # [M, D] fp64 cluster centres in the original coordinates: feeds the model constructors and InducingPoints
+    labels: torch.Tensor  # [N] int64: the centre of Z nearest to each row (the lowest index on equal distances)
+    counts: torch.Tensor  # [M] int64 rows per centre; 0 for a centre that lost all its rows (it stays where it was)
+    inertia: torch.Tensor  # 0-dim: sum of the scaled squared distances of ``labels`` to ``Z``
+    inertia_history: torch.Tensor  # [n_iter] the inertia each iteration's assignment found, non-increasing
+    n_iter: int  # iterations run
+    converged: bool  # the labels stopped changing (or the centres moved by at most ``tol``) within ``max_iter``
+
+
+def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, max_iter=25, tol=0.0,
+                           device=None) -> KMeansInducing:
+    """Lloyd's k-means cluster centres of X as inducing points -- the usual initialisation of sparse GPs, the reference drivers'
+    ``KMeans(n_clusters=M).fit(X).cluster_centers_``.  It needs no kernel, returns centres that are not rows of X, and minimises
+    the quantisation error the Nystrom residual grows from; ``select_inducing_points`` is the other standard choice, and its
+    result is a good start for this one.
+
+    Deterministic: nothing is drawn, there is no seed, two calls agree bit for bit.  ``init`` is ``"first"`` (X[:M], the
+    reference's own initialisation), an [M, D] array of starting centres, or an ``InducingSelection`` (its Z; ``count`` must be
+    M).  ``lengthscales`` (None = ones, a scalar or [D]) are the kernel's: distances are taken in the coordinates it sees, x / l,
+    and the centres are returned in the original ones.  With il = 1 / l and s(x, c) = sum_q ((x_q il_q) - (c_q il_q))^2:
+
+        C = init
+        for it = 1 .. max_iter:
+            labels[n] = the lowest m with s(x_n, c_m) minimal;  inertia_it = sum_n min_m s
+            if it > 1 and labels == previous labels: converged, stop        (C is already their mean)
+            C_new[m] = mean of the rows labelled m, or C[m] unchanged if none        (an empty cluster keeps its centre)
+            shift = max_m s(C_new[m], C[m]);  C = C_new
+            if tol > 0 and shift <= tol^2: converged, stop
+        if the loop did not end on unchanged labels: one more assignment, so labels / counts / inertia belong to the returned Z
+
+    Runs on the ROCm device (X is moved there; ``device`` picks one) through ``EStepEngine.kmeans_assign`` and
+    ``kmeans_update``; there is no CPU fallback.  The arithmetic is fp64 whatever X is.  One scalar goes to the host per
+    iteration (did any label change); no N x M array exists at any point.  Out of scope: more than 32 input columns, seeded
+    initialisations (k-means++), relocating empty clusters, mini-batches, and a row-sharded X -- a sharded caller clusters on
+    one rank or on a subsample."""
+    name = "kmeans_inducing_points"
+    if isinstance(lengthscales, SeparateIndependent):
+        raise ValueError(f"{name}: SeparateIndependent holds one kernel per latent; pass the lengthscales of the latent you mean")
+    if isinstance(X, Parameter):
+        X = X.value
+    if not hasattr(X, "shape"):
+        X = np.asarray(X, dtype=np.float64)
+    shape = tuple(X.shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{name}: X must be a non-empty [N, D] array, got shape {shape}")
+    N, D = shape
+    if D > MAX_INPUT_DIM:
+        raise ValueError(f"{name}: at most {MAX_INPUT_DIM} input columns, got {D}")
+    if isinstance(num_inducing, bool) or int(num_inducing) != num_inducing or not 1 <= int(num_inducing) <= N:
+        raise ValueError(f"{name}: num_inducing must be an integer in [1, N = {N}], got {num_inducing}")
+    M = int(num_inducing)
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"{name}: max_iter must be an integer >= 1, got {max_iter}")
+    tol = float(tol)
+    if not tol >= 0.0 or tol == float("inf"):
+        raise ValueError(f"{name}: tol must be finite and >= 0, got {tol}")
+    if lengthscales is None:
+        ls = np.ones(D)
+    else:
+        if isinstance(lengthscales, Parameter):
+            lengthscales = lengthscales.value
+        if isinstance(lengthscales, torch.Tensor):
+            lengthscales = lengthscales.detach().cpu().numpy()
+        ls = np.asarray(lengthscales, dtype=np.float64)
+        if ls.ndim == 0:
+            ls = np.full(D, float(ls))
+        if ls.shape != (D,):
+            raise ValueError(f"{name}: lengthscales must be None, a scalar or [{D}], got shape {ls.shape}")
+        if not np.all(np.isfinite(ls)) or not np.all(ls > 0.0):
+            raise ValueError(f"{name}: lengthscales must be finite and > 0, got {ls}")
+    start = None
+    if isinstance(init, InducingSelection):
+        if init.count != M or tuple(init.Z.shape) != (M, D):
+            raise ValueError(f"{name}: init holds {init.count} rows of shape {tuple(init.Z.shape)}, num_inducing = {M} rows of "
+                             f"{D} columns are needed (the selection stopped early, or it was made for another M)")
+        start = init.Z
+    elif isinstance(init, str):
+        if init != "first":
+            raise ValueError(f"{name}: init must be 'first', an [M, D] array or an InducingSelection, got {init!r}")
+    else:
+        start = init.value if isinstance(init, Parameter) else init
+        if not hasattr(start, "shape"):
+            start = np.asarray(start, dtype=np.float64)
+        if tuple(start.shape) != (M, D):
+            raise ValueError(f"{name}: init must have shape ({M}, {D}), got {tuple(start.shape)}")
+    engine = EStepEngine(torch.float64, device)
+    dev = engine.device
+    Xd = (X.to(dev) if isinstance(X, torch.Tensor) else to_tensor(X, device=dev)).to(torch.float64).contiguous()
+    if start is None:
+        C = Xd[:M].clone()
+    else:
+        C = (start.detach().to(dev) if isinstance(start, torch.Tensor) else to_tensor(start, device=dev)).to(torch.float64).contiguous()
+    il = 1.0 / to_tensor(ls, device=dev).to(torch.float64)
+    history, prev, counts = [], None, None
+    converged, on_labels = False, False
+    for it in range(1, int(max_iter) + 1):
+        labels, dist, inertia = engine.kmeans_assign(Xd, C, il)
+        history.append(inertia)
+        if prev is not None and torch.equal(labels, prev):  # the iteration's one host read
+            converged = on_labels = True
+            break
+        prev = labels
+        C_new, counts = engine.kmeans_update(Xd, labels, C)
+        if tol > 0.0:
+            dd = C_new * il - C * il
+            shift = float((dd * dd).sum(dim=1).max())
+        C = C_new
+        if tol > 0.0 and shift <= tol * tol:
+            converged = True
+            break
+    if not on_labels:
+        labels, dist, inertia = engine.kmeans_assign(Xd, C, il)
+        counts = torch.bincount(labels, minlength=M)
+    return KMeansInducing(Z=C, labels=labels.to(torch.int64), counts=counts.to(torch.int64), inertia=inertia,
+                          inertia_history=torch.stack(history), n_iter=it, converged=converged)
