@@ -670,6 +670,40 @@ int tsvgp_kmeans_assign_f64(const double *X, const double *C, const double *inv_
 int tsvgp_kmeans_update_f64(const double *X, const int64_t *order, const int64_t *offsets, const double *C_old, double *C_new,
                             int64_t N, int M, int D, void *stream);
 
+/* (13) k-means++ seeding for (12) (Arthur, Vassilvitskii 2007, with scikit-learn's greedy local trials [ext]: the seeding behind
+ *     the KMeans(n_clusters=M, random_state=0) the reference's drivers name): M rows of X, each drawn with probability
+ *     proportional to its scaled squared distance s (12) to the nearest row already taken, the best of L draws kept.
+ *        u(r, j) = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53 in [0, 1), exact in fp64, with
+ *                  (x0, x1, ., .) = Philox4x32-10(counter = (r, j, 0x6B2B2B, 0), key = (seed & 0xffffffff, seed >> 32))  (see (4a))
+ *        round 0:  i_0 = min(floor(u(0, 0) * N), N - 1);   mind[n] = s(x_n, x_{i_0});   pot_0 = sum_n mind[n]
+ *        round r = 1 .. M-1, for j < L:  t_j = u(r, j) * pot_{r-1};   cand_j = the lowest n whose running sum of mind through n
+ *                  exceeds t_j (rows in increasing n);   newpot_j = sum_n min(mind[n], s(x_n, x_{cand_j}))
+ *                  j* = the lowest j with newpot_j minimal;  i_r = cand_{j*};  mind[n] = min(mind[n], s(x_n, x_{i_r}));  pot_r = newpot_{j*}
+ *     A row of zero mass (mind[n] == 0: a taken row or a duplicate of one) is never a candidate while any row has mass; a
+ *     t_j at or above the top of the running sum takes the last row of positive mass; with no mass left (fewer than M
+ *     distinct rows) nothing is divided, every candidate is N - 1, the rounds complete and pot_hist shows the zeros.
+ *     Summation order (fixed by N, D, L alone -- no floating-point atomics, two calls agree bit for bit): the sums over n are
+ *     taken per workgroup of tsvgp_kmeanspp_rows(D) consecutive rows in the tree of (12)'s partial inertia, then over the
+ *     workgroups b (16 slots, slot k adds b = k, k + 16, ... in that order, then a pairwise tree over the slots).  The running
+ *     sum is hierarchical: the same per-workgroup sums, in 256 chunks of ceil(B / 256) consecutive workgroups (each chunk
+ *     added in order, a Hillis-Steele scan over the chunks), the workgroups of one chunk in order, and inside one workgroup
+ *     its rows in increasing n (rows / 256 consecutive rows per lane added in order, the same scan over the lanes).  Each
+ *     level takes the highest position of positive mass whose running sum before it is <= t_j.
+ *     X [N x D] row-major and contiguous, FINITE (not checked here), inv_ls [D]; indices [M] int64 in the order chosen;
+ *     dist [N]: the final mind, bit for bit tsvgp_kmeans_assign_f64's dist against X[indices]; pot_hist [M]: pot_r;
+ *     cand, cand_pot, unif [M x L] row-major: cand_j, newpot_j and u(r, j) of every round, row 0 holding i_0, pot_0 and
+ *     u(0, 0) in column 0; entries no round uses are -1, +inf and 0.  work: tsvgp_kmeanspp_work(N, D, L) doubles (one partial
+ *     sum per workgroup and candidate; -1 for N < 1, D or L out of range, or N beyond rows * (2^31 - 1)).
+ *     N >= 1, 1 <= M <= N, 1 <= D <= 32, 1 <= L <= TSVGP_KMEANSPP_MAX_TRIALS, no NULL pointer, every buffer on an 8-byte
+ *     boundary; TSVGP_EINVAL otherwise, before any launch.  The call enqueues 2 M + 2 launches on `stream` (one fill, per centre
+ *     one grid over n and L workgroups that reduce, choose and draw the next round's candidates, one last grid over n) and
+ *     reads nothing back; no workgroup waits for another.  X is read once per centre; nothing of size N x M or N x L exists. */
+#define TSVGP_KMEANSPP_MAX_TRIALS 16
+int tsvgp_kmeanspp_rows(int D);
+int64_t tsvgp_kmeanspp_work(int64_t N, int D, int L);
+int tsvgp_kmeanspp_f64(const double *X, const double *inv_ls, int64_t seed, int M, int L, int64_t *indices, double *dist,
+                       double *pot_hist, int64_t *cand, double *cand_pot, double *unif, double *work, int64_t N, int D, void *stream);
+
 /* Device self-test of the MFMA fragment maps used above (writes a 16x16 product C = A*B, k = 4, for host checking).
  * a [16 x 4], b [4 x 16], c [16 x 16] row-major. */
 int tsvgp_selftest_mfma_f64(const double *a, const double *b, double *c, void *stream);

@@ -6,8 +6,9 @@ The directory name carries a hyphen (as the project layout prescribes), so impor
 from . import _backend, distributed, training, util
 from ._backend import HipExtensionError, build_library
 from .base import Parameter, default_float, default_jitter
-from .inducing_variables import (InducingPoints, InducingSelection, KMeansInducing, SharedIndependentInducingVariables,
-                                 inducingpoint_wrapper, kmeans_inducing_points, select_inducing_points)
+from .inducing_variables import (InducingPoints, InducingSelection, KMeansInducing, KMeansSeeding,
+                                 SharedIndependentInducingVariables, inducingpoint_wrapper, kmeans_inducing_points, kmeanspp_seeds,
+                                 select_inducing_points)
 from .kernels import Matern32, Matern52, SeparateIndependent, SquaredExponential
 from .likelihoods import Bernoulli, Gaussian, HeteroskedasticTFPConditional, MultiClass, Poisson, RobustMax, Softmax, StudentT
 from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white, t_VGP
@@ -17,7 +18,8 @@ from .sites import DenseSites, DiagSites, Sites
 __all__ = [
     "t_SVGP", "t_SVGP_white", "t_SVGP_sites", "t_VGP", "base_SVGP", "DenseSites", "DiagSites", "Sites", "SquaredExponential", "Gaussian", "Bernoulli", "HeteroskedasticTFPConditional", "Softmax", "StudentT", "Poisson",
     "MultiClass", "RobustMax",
-    "InducingPoints", "select_inducing_points", "InducingSelection", "kmeans_inducing_points", "KMeansInducing", "FunctionSamples",
+    "InducingPoints", "select_inducing_points", "InducingSelection", "kmeans_inducing_points", "KMeansInducing", "kmeanspp_seeds", "KMeansSeeding",
+    "FunctionSamples",
     "SeparateIndependent", "SharedIndependentInducingVariables", "Matern32", "Matern52",
     "inducingpoint_wrapper", "Parameter", "default_float", "default_jitter", "HipExtensionError", "build_library",
     "distributed", "util", "training",

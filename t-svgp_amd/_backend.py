@@ -45,6 +45,7 @@ POTRF_DIAG_V1 = 4  # TSVGP_POTRF_DIAG_V1
 POTRF_FUSE = 16  # TSVGP_POTRF_FUSE
 VGP_NO_ROWS = 1  # TSVGP_VGP_NO_ROWS
 PATHWISE_MAX_S = 16  # TSVGP_PATHWISE_MAX_S: samples per launch of tsvgp_pathwise_f64
+KMEANSPP_MAX_TRIALS = 16  # TSVGP_KMEANSPP_MAX_TRIALS: local trials per centre of tsvgp_kmeanspp_f64
 ABI_VERSION = 5  # TSVGP_ABI_VERSION of include/tsvgp_hip.h these prototypes were written for
 
 _lib = None
@@ -210,6 +211,10 @@ _PROTOTYPES = {
     "tsvgp_kmeans_assign_parts": (c_int64, [c_int64, c_int]),
     "tsvgp_kmeans_assign_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_kmeans_update_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_kmeanspp_rows": (c_int, [c_int]),
+    "tsvgp_kmeanspp_work": (c_int64, [c_int64, c_int, c_int]),
+    "tsvgp_kmeanspp_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int64, c_int, c_void_p]),
     "tsvgp_selftest_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -1776,3 +1776,39 @@ class EStepEngine:
             self._launch("tsvgp_kmeans_update", lambda: self.lib.tsvgp_kmeans_update_f64(
                 X.data_ptr(), order.data_ptr(), offsets.data_ptr(), C_old.data_ptr(), C_new.data_ptr(), N, M, D, self._stream()))
         return C_new, counts
+
+    def kmeanspp(self, X, inv_ls, M: int, L: int, seed: int):
+        """k-means++ seeding with L greedy local trials per centre (``tsvgp_kmeanspp_f64``): M rows of X [N, D <= 32], each
+        drawn with probability proportional to its scaled squared distance to the nearest row already taken.  fp64 whatever
+        the engine's compute dtype; X must be finite (the caller checks).  One call, 2 M + 2 launches, no host read; the
+        workspace is one double per workgroup and trial.  Returns ``(indices [M] int64, dist [N], pot_hist [M],
+        cand [M, L] int64, cand_pot [M, L], unif [M, L])`` on the device."""
+        if X.dim() != 2 or X.shape[0] < 1:
+            raise ValueError(f"kmeanspp: X must be [N >= 1, D], got {tuple(X.shape)}")
+        N, D = X.shape
+        M, L, seed = int(M), int(L), int(seed)
+        if D < 1 or D > MAX_INPUT_DIM:
+            raise ValueError(f"kmeanspp: 1 <= D <= {MAX_INPUT_DIM}, got {D}")
+        if not 1 <= M <= N:
+            raise ValueError(f"kmeanspp: 1 <= M <= N = {N}, got {M}")
+        if not 1 <= L <= B.KMEANSPP_MAX_TRIALS:
+            raise ValueError(f"kmeanspp: 1 <= L <= {B.KMEANSPP_MAX_TRIALS}, got {L}")
+        if not -2 ** 63 <= seed < 2 ** 63:
+            raise ValueError(f"kmeanspp: seed must fit a signed 64-bit integer, got {seed}")
+        X = X.to(device=self.device, dtype=torch.float64).contiguous()
+        inv_ls = inv_ls.to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(inv_ls.shape) != (D,):
+            raise ValueError(f"kmeanspp: inv_ls must be [{D}], got {tuple(inv_ls.shape)}")
+        nwork = int(self.lib.tsvgp_kmeanspp_work(N, D, L))
+        if nwork <= 0:
+            raise ValueError(f"kmeanspp: no launch geometry for N = {N}, D = {D}, L = {L}")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        indices = torch.empty((M,), dtype=torch.int64, device=self.device)
+        cand = torch.empty((M, L), dtype=torch.int64, device=self.device)
+        dist, pot_hist, work = torch.empty((N,), **f64), torch.empty((M,), **f64), torch.empty((nwork,), **f64)
+        cand_pot, unif = torch.empty((M, L), **f64), torch.empty((M, L), **f64)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_kmeanspp", lambda: self.lib.tsvgp_kmeanspp_f64(
+                X.data_ptr(), inv_ls.data_ptr(), seed, M, L, indices.data_ptr(), dist.data_ptr(), pot_hist.data_ptr(),
+                cand.data_ptr(), cand_pot.data_ptr(), unif.data_ptr(), work.data_ptr(), N, D, self._stream()))
+        return indices, dist, pot_hist, cand, cand_pot, unif

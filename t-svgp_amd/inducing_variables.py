@@ -1,11 +1,13 @@
 """``gpflow.inducing_variables.InducingPoints`` / ``inducingpoint_wrapper`` mirror (reference tsvgp.py:22,150)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
+from ._backend import KMEANSPP_MAX_TRIALS
 from .base import Parameter, to_tensor
 from .estep import MAX_INPUT_DIM, EStepEngine
 from .kernels import SeparateIndependent
@@ -105,46 +107,8 @@ def select_inducing_points(X, kernel, num_inducing, *, threshold=0.0, device=Non
     return InducingSelection(Z=Xd[indices], indices=indices, pivots=pivots, residual=residual, trace=residual.sum(), count=count)
 
 
-@dataclass
-class KMeansInducing:
-    """What ``kmeans_inducing_points`` returns (tensors on the device the clustering ran on)."""
-
-    Z: torch.Tensor  # [M, D] fp64 cluster centres in the original coordinates: feeds the model constructors and InducingPoints
-    labels: torch.Tensor  # [N] int64: the centre of Z nearest to each row (the lowest index on equal distances)
-    counts: torch.Tensor  # [M] int64 rows per centre; 0 for a centre that lost all its rows (it stays where it was)
-    inertia: torch.Tensor  # 0-dim: sum of the scaled squared distances of ``labels`` to ``Z``
-    inertia_history: torch.Tensor  # [n_iter] the inertia each iteration's assignment found, non-increasing
-    n_iter: int  # iterations run
-    converged: bool  # the labels stopped changing (or the centres moved by at most ``tol``) within ``max_iter``
-
-
-def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, max_iter=25, tol=0.0,
-                           device=None) -> KMeansInducing:
-    """Lloyd's k-means cluster centres of X as inducing points -- the usual initialisation of sparse GPs, the reference drivers'
-    ``KMeans(n_clusters=M).fit(X).cluster_centers_``.  It needs no kernel, returns centres that are not rows of X, and minimises
-    the quantisation error the Nystrom residual grows from; ``select_inducing_points`` is the other standard choice, and its
-    result is a good start for this one.
-
-    Deterministic: nothing is drawn, there is no seed, two calls agree bit for bit.  ``init`` is ``"first"`` (X[:M], the
-    reference's own initialisation), an [M, D] array of starting centres, or an ``InducingSelection`` (its Z; ``count`` must be
-    M).  ``lengthscales`` (None = ones, a scalar or [D]) are the kernel's: distances are taken in the coordinates it sees, x / l,
-    and the centres are returned in the original ones.  With il = 1 / l and s(x, c) = sum_q ((x_q il_q) - (c_q il_q))^2:
-
-        C = init
-        for it = 1 .. max_iter:
-            labels[n] = the lowest m with s(x_n, c_m) minimal;  inertia_it = sum_n min_m s
-            if it > 1 and labels == previous labels: converged, stop        (C is already their mean)
-            C_new[m] = mean of the rows labelled m, or C[m] unchanged if none        (an empty cluster keeps its centre)
-            shift = max_m s(C_new[m], C[m]);  C = C_new
-            if tol > 0 and shift <= tol^2: converged, stop
-        if the loop did not end on unchanged labels: one more assignment, so labels / counts / inertia belong to the returned Z
-
-    Runs on the ROCm device (X is moved there; ``device`` picks one) through ``EStepEngine.kmeans_assign`` and
-    ``kmeans_update``; there is no CPU fallback.  The arithmetic is fp64 whatever X is.  One scalar goes to the host per
-    iteration (did any label change); no N x M array exists at any point.  Out of scope: more than 32 input columns, seeded
-    initialisations (k-means++), relocating empty clusters, mini-batches, and a row-sharded X -- a sharded caller clusters on
-    one rank or on a subsample."""
-    name = "kmeans_inducing_points"
+def _rows_and_count(name, X, num_inducing, lengthscales):
+    """The checks of X and num_inducing the k-means functions share: (X, N, D, M)."""
     if isinstance(lengthscales, SeparateIndependent):
         raise ValueError(f"{name}: SeparateIndependent holds one kernel per latent; pass the lengthscales of the latent you mean")
     if isinstance(X, Parameter):
@@ -159,35 +123,160 @@ def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, 
         raise ValueError(f"{name}: at most {MAX_INPUT_DIM} input columns, got {D}")
     if isinstance(num_inducing, bool) or int(num_inducing) != num_inducing or not 1 <= int(num_inducing) <= N:
         raise ValueError(f"{name}: num_inducing must be an integer in [1, N = {N}], got {num_inducing}")
-    M = int(num_inducing)
+    return X, N, D, int(num_inducing)
+
+
+def _lengthscales(name, lengthscales, D):
+    """None, a scalar or [D], finite and > 0, as a NumPy [D]."""
+    if lengthscales is None:
+        return np.ones(D)
+    if isinstance(lengthscales, Parameter):
+        lengthscales = lengthscales.value
+    if isinstance(lengthscales, torch.Tensor):
+        lengthscales = lengthscales.detach().cpu().numpy()
+    ls = np.asarray(lengthscales, dtype=np.float64)
+    if ls.ndim == 0:
+        ls = np.full(D, float(ls))
+    if ls.shape != (D,):
+        raise ValueError(f"{name}: lengthscales must be None, a scalar or [{D}], got shape {ls.shape}")
+    if not np.all(np.isfinite(ls)) or not np.all(ls > 0.0):
+        raise ValueError(f"{name}: lengthscales must be finite and > 0, got {ls}")
+    return ls
+
+
+def _trials(name, n_local_trials, M):
+    """n_local_trials: None = scikit-learn's 2 + floor(ln M), else an integer in [1, KMEANSPP_MAX_TRIALS]."""
+    if n_local_trials is None:
+        return min(2 + int(math.log(M)), KMEANSPP_MAX_TRIALS)
+    if isinstance(n_local_trials, bool) or int(n_local_trials) != n_local_trials or not 1 <= int(n_local_trials) <= KMEANSPP_MAX_TRIALS:
+        raise ValueError(f"{name}: n_local_trials must be None or an integer in [1, {KMEANSPP_MAX_TRIALS}], got {n_local_trials}")
+    return int(n_local_trials)
+
+
+def _seed(name, seed):
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 63:
+        raise ValueError(f"{name}: seed must be an integer in [0, 2^63), got {seed}")
+    return int(seed)
+
+
+@dataclass
+class KMeansSeeding:
+    """What ``kmeanspp_seeds`` returns (tensors on the device the seeding ran on)."""
+
+    Z: torch.Tensor  # [M, D] = X[indices]: feeds kmeans_inducing_points(init=...), the model constructors and InducingPoints
+    indices: torch.Tensor  # [M] int64 row numbers into X, in the order chosen
+    dist: torch.Tensor  # [N] scaled squared distance of each row to the nearest seed (0 at the seeds and their duplicates)
+    potential: torch.Tensor  # 0-dim: the sum of ``dist`` = potential_history[-1]
+    potential_history: torch.Tensor  # [M] the potential after each centre, non-increasing
+    candidates: torch.Tensor  # [M, L] int64: the rows each round drew (row 0: the first centre in column 0; -1 where unused)
+    trial_potentials: torch.Tensor  # [M, L] the potential each candidate would leave (+inf where unused); the lowest won
+    uniforms: torch.Tensor  # [M, L] the uniform behind each candidate (0 where unused)
+    seed: int
+    n_local_trials: int
+
+
+def kmeanspp_seeds(X, num_inducing, *, lengthscales=None, seed=0, n_local_trials=None, device=None) -> KMeansSeeding:
+    """k-means++ seeding (Arthur and Vassilvitskii 2007) as scikit-learn's ``KMeans`` runs it by default: ``num_inducing`` rows
+    of X, the first uniform, every later one drawn with probability proportional to its scaled squared distance to the nearest
+    row already taken, the best of ``n_local_trials`` draws kept (None = 2 + floor(ln M), at most 16).  It needs no kernel and
+    no N x M array, and it is the start ``kmeans_inducing_points(init="k-means++")`` runs Lloyd's iterations from.
+
+    Random, but a pure function of (X, lengthscales, seed, n_local_trials): the uniforms come from the package's counter-based
+    generator (Philox4x32-10), every sum has a fixed order, and two calls agree bit for bit.  ``lengthscales`` as in
+    ``kmeans_inducing_points``.  With fewer than M distinct rows the call still returns M rows (duplicates, the potential 0).
+
+    Runs on the ROCm device through ``EStepEngine.kmeanspp`` (one call, two launches per centre, X read once per centre);
+    there is no CPU fallback.  X must be finite: that is checked once on the device (the one host read of the call)."""
+    name = "kmeanspp_seeds"
+    X, N, D, M = _rows_and_count(name, X, num_inducing, lengthscales)
+    ls = _lengthscales(name, lengthscales, D)
+    seed, L = _seed(name, seed), _trials(name, n_local_trials, M)
+    engine = EStepEngine(torch.float64, device)
+    dev = engine.device
+    Xd = (X.to(dev) if isinstance(X, torch.Tensor) else to_tensor(X, device=dev)).to(torch.float64).contiguous()
+    return _kmeanspp(name, engine, Xd, 1.0 / to_tensor(ls, device=dev).to(torch.float64), M, L, seed)
+
+
+def _kmeanspp(name, engine, Xd, il, M, L, seed) -> KMeansSeeding:
+    if not bool(torch.isfinite(Xd).all()):
+        raise ValueError(f"{name}: X must be finite for k-means++ seeding (a NaN or an infinite entry has no distance)")
+    indices, dist, pot_hist, cand, cand_pot, unif = engine.kmeanspp(Xd, il, M, L, seed)
+    return KMeansSeeding(Z=Xd[indices], indices=indices, dist=dist, potential=pot_hist[M - 1].clone(), potential_history=pot_hist,
+                         candidates=cand, trial_potentials=cand_pot, uniforms=unif, seed=seed, n_local_trials=L)
+
+
+@dataclass
+class KMeansInducing:
+    """What ``kmeans_inducing_points`` returns (tensors on the device the clustering ran on)."""
+
+    Z: torch.Tensor  # [M, D] fp64 cluster centres in the original coordinates: feeds the model constructors and InducingPoints
+    labels: torch.Tensor  # [N] int64: the centre of Z nearest to each row (the lowest index on equal distances)
+    counts: torch.Tensor  # [M] int64 rows per centre; 0 for a centre that lost all its rows (it stays where it was)
+    inertia: torch.Tensor  # 0-dim: sum of the scaled squared distances of ``labels`` to ``Z``
+    inertia_history: torch.Tensor  # [n_iter] the inertia each iteration's assignment found, non-increasing
+    n_iter: int  # iterations run
+    converged: bool  # the labels stopped changing (or the centres moved by at most ``tol``) within ``max_iter``
+    # the KMeansSeeding the run started from (init="k-means++" or a KMeansSeeding), else None.  A plain attribute, set on the
+    # result, not a dataclass field: the seven fields above, their order and the positional constructor stay what they were
+    seeding = None
+
+
+def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, max_iter=25, tol=0.0, seed=None,
+                           n_local_trials=None, device=None) -> KMeansInducing:
+    """Lloyd's k-means cluster centres of X as inducing points -- the usual initialisation of sparse GPs, the reference drivers'
+    ``KMeans(n_clusters=M).fit(X).cluster_centers_``.  It needs no kernel, returns centres that are not rows of X, and minimises
+    the quantisation error the Nystrom residual grows from; ``select_inducing_points`` is the other standard choice, and its
+    result is a good start for this one.
+
+    Two calls agree bit for bit.  ``init`` is ``"first"`` (X[:M], the reference's own initialisation), an [M, D] array of
+    starting centres, an ``InducingSelection`` (its Z; ``count`` must be M), ``"k-means++"`` (``kmeanspp_seeds`` with ``seed``,
+    default 0, and ``n_local_trials``: scikit-learn's default start, and the one that needs no kernel) or a ``KMeansSeeding``
+    made for this M; the last two leave the seeding in the result's ``seeding``.  ``seed`` and ``n_local_trials`` with any
+    other ``init`` are an error; without them nothing is drawn.  ``lengthscales`` (None = ones, a scalar or [D]) are the
+    kernel's: distances are taken in the coordinates it sees, x / l, and the centres are returned in the original ones.  With il = 1 / l and s(x, c) = sum_q ((x_q il_q) - (c_q il_q))^2:
+
+        C = init
+        for it = 1 .. max_iter:
+            labels[n] = the lowest m with s(x_n, c_m) minimal;  inertia_it = sum_n min_m s
+            if it > 1 and labels == previous labels: converged, stop        (C is already their mean)
+            C_new[m] = mean of the rows labelled m, or C[m] unchanged if none        (an empty cluster keeps its centre)
+            shift = max_m s(C_new[m], C[m]);  C = C_new
+            if tol > 0 and shift <= tol^2: converged, stop
+        if the loop did not end on unchanged labels: one more assignment, so labels / counts / inertia belong to the returned Z
+
+    Runs on the ROCm device (X is moved there; ``device`` picks one) through ``EStepEngine.kmeans_assign`` and
+    ``kmeans_update``; there is no CPU fallback.  The arithmetic is fp64 whatever X is.  One scalar goes to the host per
+    iteration (did any label change); no N x M array exists at any point.  Out of scope: more than 32 input columns, fp32
+    arithmetic, relocating empty clusters, mini-batches, and a row-sharded X -- a sharded caller clusters on one rank or on a
+    subsample."""
+    name = "kmeans_inducing_points"
+    X, N, D, M = _rows_and_count(name, X, num_inducing, lengthscales)
     if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
         raise ValueError(f"{name}: max_iter must be an integer >= 1, got {max_iter}")
     tol = float(tol)
     if not tol >= 0.0 or tol == float("inf"):
         raise ValueError(f"{name}: tol must be finite and >= 0, got {tol}")
-    if lengthscales is None:
-        ls = np.ones(D)
-    else:
-        if isinstance(lengthscales, Parameter):
-            lengthscales = lengthscales.value
-        if isinstance(lengthscales, torch.Tensor):
-            lengthscales = lengthscales.detach().cpu().numpy()
-        ls = np.asarray(lengthscales, dtype=np.float64)
-        if ls.ndim == 0:
-            ls = np.full(D, float(ls))
-        if ls.shape != (D,):
-            raise ValueError(f"{name}: lengthscales must be None, a scalar or [{D}], got shape {ls.shape}")
-        if not np.all(np.isfinite(ls)) or not np.all(ls > 0.0):
-            raise ValueError(f"{name}: lengthscales must be finite and > 0, got {ls}")
-    start = None
-    if isinstance(init, InducingSelection):
+    ls = _lengthscales(name, lengthscales, D)
+    plusplus = isinstance(init, str) and init == "k-means++"
+    if not plusplus and (seed is not None or n_local_trials is not None):
+        raise ValueError(f"{name}: seed and n_local_trials belong to init='k-means++', not to the init given")
+    if plusplus:
+        seed, trials = _seed(name, 0 if seed is None else seed), _trials(name, n_local_trials, M)
+    start, seeding = None, None
+    if isinstance(init, KMeansSeeding):
+        if tuple(init.indices.shape) != (M,) or tuple(init.Z.shape) != (M, D):
+            raise ValueError(f"{name}: init holds {tuple(init.indices.shape)[0]} rows of shape {tuple(init.Z.shape)}, num_inducing = "
+                             f"{M} rows of {D} columns are needed (the seeding was made for another M)")
+        start, seeding = init.Z, init
+    elif isinstance(init, InducingSelection):
         if init.count != M or tuple(init.Z.shape) != (M, D):
             raise ValueError(f"{name}: init holds {init.count} rows of shape {tuple(init.Z.shape)}, num_inducing = {M} rows of "
                              f"{D} columns are needed (the selection stopped early, or it was made for another M)")
         start = init.Z
     elif isinstance(init, str):
-        if init != "first":
-            raise ValueError(f"{name}: init must be 'first', an [M, D] array or an InducingSelection, got {init!r}")
+        if init != "first" and not plusplus:
+            raise ValueError(f"{name}: init must be 'first', 'k-means++', an [M, D] array, an InducingSelection or a "
+                             f"KMeansSeeding, got {init!r}")
     else:
         start = init.value if isinstance(init, Parameter) else init
         if not hasattr(start, "shape"):
@@ -197,11 +286,14 @@ def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, 
     engine = EStepEngine(torch.float64, device)
     dev = engine.device
     Xd = (X.to(dev) if isinstance(X, torch.Tensor) else to_tensor(X, device=dev)).to(torch.float64).contiguous()
+    il = 1.0 / to_tensor(ls, device=dev).to(torch.float64)
+    if plusplus:
+        seeding = _kmeanspp(name, engine, Xd, il, M, trials, seed)
+        start = seeding.Z
     if start is None:
         C = Xd[:M].clone()
     else:
         C = (start.detach().to(dev) if isinstance(start, torch.Tensor) else to_tensor(start, device=dev)).to(torch.float64).contiguous()
-    il = 1.0 / to_tensor(ls, device=dev).to(torch.float64)
     history, prev, counts = [], None, None
     converged, on_labels = False, False
     for it in range(1, int(max_iter) + 1):
@@ -222,5 +314,7 @@ def kmeans_inducing_points(X, num_inducing, *, init="first", lengthscales=None, 
     if not on_labels:
         labels, dist, inertia = engine.kmeans_assign(Xd, C, il)
         counts = torch.bincount(labels, minlength=M)
-    return KMeansInducing(Z=C, labels=labels.to(torch.int64), counts=counts.to(torch.int64), inertia=inertia,
-                          inertia_history=torch.stack(history), n_iter=it, converged=converged)
+    res = KMeansInducing(Z=C, labels=labels.to(torch.int64), counts=counts.to(torch.int64), inertia=inertia,
+                         inertia_history=torch.stack(history), n_iter=it, converged=converged)
+    res.seeding = seeding
+    return res
