@@ -56,6 +56,9 @@ extern "C" {
 #define TSVGP_LIK_POISSON 6   /* gpflow.likelihoods.Poisson(binsize), exp link, closed form: tsvgp_lik_map_scalar_* only */
 #define TSVGP_LIK_MULTICLASS 7 /* gpflow.likelihoods.MultiClass(C) with the RobustMax link over C coupled latents, 20-pt
                                   Gauss-Hermite over the labelled latent: tsvgp_lik_map_robustmax_* only */
+#define TSVGP_LIK_GAMMA 8     /* gpflow.likelihoods.Gamma(shape), exp link, closed form (shape = 1: gpflow.likelihoods.Exponential):
+                                 tsvgp_lik_map_scalar_* only */
+#define TSVGP_LIK_ORDINAL 9   /* gpflow.likelihoods.Ordinal(bin_edges), 20-pt Gauss-Hermite: tsvgp_lik_map_ordinal_* only */
 #define TSVGP_LIK_NOCROP 0x100 /* OR-ed into the selector: leave g1 = d ve/d var uncropped (reference
                                   src/models/tsvgp_white.py:188-191 has no crop; src/models/tsvgp.py:262-263 has) */
 #define TSVGP_LIK_MEANONLY 0x200 /* OR-ed into the selector (NONE or GAUSSIAN only): skip the variance product.  Under a
@@ -261,24 +264,58 @@ int tsvgp_lik_map_robustmax_f32(const float *mean, const float *var, const float
                                 float *g1, double *ve_partial, int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 
 /* (4b') The scalar likelihoods without an arm in the moments kernels (GPflow 2.2.1 [ext]), one latent column per call, behind the
- *     moments like (4b): lik = TSVGP_LIK_STUDENT_T (param0 = scale > 0, param1 = df > 0) or TSVGP_LIK_POISSON (param0 = binsize > 0,
- *     exp link; param1 ignored), optionally | TSVGP_LIK_NOCROP.
+ *     moments like (4b): lik = TSVGP_LIK_STUDENT_T (param0 = scale > 0, param1 = df > 0), TSVGP_LIK_POISSON (param0 = binsize > 0,
+ *     exp link; param1 ignored) or TSVGP_LIK_GAMMA (param0 = shape a > 0, exp link: scale = exp(f); param1 ignored), optionally
+ *     | TSVGP_LIK_NOCROP.
  *        StudentT  log p(y | f) = lgamma((df+1)/2) - lgamma(df/2) - 1/2 log(df pi) - log scale - (df+1)/2 log1p(((y-f)/scale)^2 / df);
  *                  ve by 20-point Gauss-Hermite, g0 = sum_i w_i l'(f_i), g1 = sum_i w_i l'(f_i) z_i / (2 sqrt(var)), f_i = mean + sqrt(var) z_i
  *                  (the derivative of the quadrature sum, what tf.GradientTape returns at reference src/models/tsvgp.py:256-259)
  *        Poisson   ve = y (mean + log b) - b exp(mean + var/2) - lgamma(y + 1),  g0 = y - b exp(mean + var/2),  g1 = -1/2 b exp(mean + var/2)
+ *        Gamma     the closed form under the exp link, e = y exp(-mean + var/2):
+ *                  ve = -a mean - lgamma(a) + (a - 1) log y - e,  g0 = -a + e,  g1 = -e / 2,  d ve / d a = -mean - digamma(a) + log y.
+ *                  At a == 1 exactly (gpflow.likelihoods.Exponential) the term (a - 1) log y is skipped, not multiplied, so y = 0
+ *                  is a legal target there.
  *     mean, var, Y: row n at element n * in_stride (a column of an [N x P] array: in_stride = P), read for n < N only;
  *     g0, g1: row n at element n * out_stride, written for every n < Np (rows >= N zero; g1 cropped at -1e-8 unless
  *     TSVGP_LIK_NOCROP, a NaN stays NaN); ve_partial [Np / 128] (fp64 per-128-row sums of ve); dparam_partial [Np / 128] or NULL
- *     (StudentT only: per-128-row sums of d ve / d scale, for the M-step; must be NULL for Poisson); nonpos_partial [Np / 128]:
- *     rows with var <= 0 or a non-finite mean.  Arithmetic in fp64 for either array type; the log-gamma terms that no row changes
- *     are taken once on the host.  No atomics, a summation order fixed by the shape: two calls agree bit for bit. */
+ *     (per-128-row sums of the parameter derivative for the M-step: StudentT d ve / d scale, Gamma d ve / d shape; must be NULL
+ *     for Poisson); nonpos_partial [Np / 128]: rows with var <= 0 or a non-finite mean; under Gamma also rows with y < 0, or
+ *     with y == 0 at a != 1, whose ve is NaN.  Arithmetic in fp64 for either array type; the log-gamma (and digamma) terms that
+ *     no row changes are taken once on the host.  No atomics, a summation order fixed by the shape: two calls agree bit for bit. */
 int tsvgp_lik_map_scalar_f64(const double *mean, const double *var, const double *Y, int64_t in_stride, int lik, double param0,
                              double param1, double *g0, double *g1, int64_t out_stride, double *ve_partial, double *dparam_partial,
                              int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
 int tsvgp_lik_map_scalar_f32(const float *mean, const float *var, const float *Y, int64_t in_stride, int lik, double param0,
                              double param1, float *g0, float *g1, int64_t out_stride, double *ve_partial, double *dparam_partial,
                              int32_t *nonpos_partial, int64_t N, int64_t Np, void *stream);
+
+/* (4b''') The Ordinal likelihood map (gpflow.likelihoods.Ordinal(bin_edges), GPflow 2.2.1 [ext]): one latent, K = n_edges + 1 ordered
+ *     bins, one latent column per call with the conventions of (4b').  With y the row's label in {0 .. K-1},
+ *        up = edges[y] (+inf for y = K-1),   lo = edges[y-1] (-inf for y = 0),   a = (up - f) / sigma,   b = (lo - f) / sigma,
+ *        Phi~(x) = Phi(x) (1 - 2e-3) + 1e-3,   phi = Phi~(a) - Phi~(b),   log p(y | f) = log(phi + 1e-6),
+ *     ve is the 20-point Gauss-Hermite sum over f_i = mean + sqrt(var) z_i (the nodes and weights of StudentT) and g0, g1,
+ *     dparam are the derivatives of that sum (reference src/models/tsvgp.py:256-263), N the standard normal density:
+ *        l'(f)       = -(1 - 2e-3) (N(a) - N(b)) / (sigma (phi + 1e-6)),     g0 = sum_i w_i l'(f_i),
+ *        d l/d sigma = -(1 - 2e-3) (a N(a) - b N(b)) / (sigma (phi + 1e-6)), g1 = sum_i w_i l'(f_i) z_i / (2 sqrt(var)),
+ *     the terms of an infinite edge being 0.  phi is evaluated as (1 - 2e-3) (Phi(a) - Phi(b)) from erfc on the side where both
+ *     tail masses are small, so a bin in the far upper tail keeps its digits.
+ *     edges [n_edges] fp64 in device memory for either array type, 1 <= n_edges <= TSVGP_ORDINAL_MAX_EDGES (staged into LDS once
+ *     per workgroup).  THE CALLER guarantees that they are finite and strictly increasing: the entry cannot read device memory
+ *     and does not check them.  sigma > 0, finite.  flags = TSVGP_LIK_ORDINAL, optionally | TSVGP_LIK_NOCROP.  Y holds the labels
+ *     in the array type; a label that is not an integer in [0, K) is never used as an address, makes its row's ve, g0, g1 NaN
+ *     and counts the row in nonpos_partial (the MultiClass convention).  mean, var, Y, in_stride, g0, g1, out_stride (rows >= N
+ *     zero; g1 cropped at -1e-8 unless TSVGP_LIK_NOCROP, a NaN stays NaN), ve_partial, nonpos_partial [Np / 128] as in (4b');
+ *     dparam_partial [Np / 128] or NULL: per-128-row sums of d ve / d sigma.  Arithmetic in fp64 for either array type.  No
+ *     atomics, a summation order fixed by the shape: two calls agree bit for bit. */
+#define TSVGP_ORDINAL_MAX_EDGES 255
+int tsvgp_lik_map_ordinal_f64(const double *mean, const double *var, const double *Y, int64_t in_stride, int flags,
+                              const double *edges, int n_edges, double sigma, double *g0, double *g1, int64_t out_stride,
+                              double *ve_partial, double *dparam_partial, int32_t *nonpos_partial, int64_t N, int64_t Np,
+                              void *stream);
+int tsvgp_lik_map_ordinal_f32(const float *mean, const float *var, const float *Y, int64_t in_stride, int flags,
+                              const double *edges, int n_edges, double sigma, float *g0, float *g1, int64_t out_stride,
+                              double *ve_partial, double *dparam_partial, int32_t *nonpos_partial, int64_t N, int64_t Np,
+                              void *stream);
 
 /* (4c) The per-datum site step of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-148) fused with the likelihood map of
  *     (4): mean, var, Y [N x P] -> g0, g1 as tsvgp_lik_map_* (never cropped: TSVGP_LIK_NOCROP semantics whatever lik says), then

@@ -11,13 +11,14 @@ from .inducing_variables import (InducingPoints, InducingSelection, KMeansInduci
                                  select_inducing_points)
 from .kernels import Matern32, Matern52, SeparateIndependent, SquaredExponential
 from .likelihoods import Bernoulli, Gaussian, HeteroskedasticTFPConditional, MultiClass, Poisson, RobustMax, Softmax, StudentT
+from .likelihoods import Exponential, Gamma, Ordinal
 from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white, t_VGP
 from .pathwise import FunctionSamples
 from .sites import DenseSites, DiagSites, Sites
 
 __all__ = [
     "t_SVGP", "t_SVGP_white", "t_SVGP_sites", "t_VGP", "base_SVGP", "DenseSites", "DiagSites", "Sites", "SquaredExponential", "Gaussian", "Bernoulli", "HeteroskedasticTFPConditional", "Softmax", "StudentT", "Poisson",
-    "MultiClass", "RobustMax",
+    "MultiClass", "RobustMax", "Gamma", "Exponential", "Ordinal",
     "InducingPoints", "select_inducing_points", "InducingSelection", "kmeans_inducing_points", "KMeansInducing", "kmeanspp_seeds", "KMeansSeeding",
     "FunctionSamples",
     "SeparateIndependent", "SharedIndependentInducingVariables", "Matern32", "Matern52",

@@ -31,8 +31,13 @@ LIK_SOFTMAX = 4  # C coupled latents, Monte Carlo: tsvgp_lik_map_softmax_* only
 LIK_MULTICLASS = 7  # C coupled latents, RobustMax link, 20-point Gauss-Hermite: tsvgp_lik_map_robustmax_* only
 COUPLED_LIKS = (LIK_HETERO, LIK_SOFTMAX, LIK_MULTICLASS)  # likelihoods whose row couples its latents (Y [N, 1])
 LIK_STUDENT_T, LIK_POISSON = 5, 6  # one latent per target column, no arm in the moments kernels: tsvgp_lik_map_scalar_* only
-SCALAR_MAP_LIKS = (LIK_STUDENT_T, LIK_POISSON)
-MAPPED_LIKS = COUPLED_LIKS + SCALAR_MAP_LIKS  # likelihoods whose map runs behind the moments, not in their epilogue
+LIK_GAMMA = 8  # Gamma(shape) under the exp link (shape = 1: Exponential): a third arm of tsvgp_lik_map_scalar_*
+LIK_ORDINAL = 9  # Ordinal(bin_edges): one latent per target column like the scalar maps, an entry of its own: tsvgp_lik_map_ordinal_*
+SCALAR_MAP_LIKS = (LIK_STUDENT_T, LIK_POISSON, LIK_GAMMA)
+ORDINAL_LIKS = (LIK_ORDINAL,)
+COLUMN_MAP_LIKS = SCALAR_MAP_LIKS + ORDINAL_LIKS  # Y [N, P], one launch of the map per latent column
+MAPPED_LIKS = COUPLED_LIKS + COLUMN_MAP_LIKS  # likelihoods whose map runs behind the moments, not in their epilogue
+ORDINAL_MAX_EDGES = 255  # TSVGP_ORDINAL_MAX_EDGES
 LIK_NOCROP = 0x100
 LIK_MEANONLY = 0x200
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 2, 3
@@ -150,6 +155,10 @@ _PROTOTYPES = {
                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_lik_map_scalar_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int64,
                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_ordinal_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lik_map_ordinal_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_diag_site_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_diag_site_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,

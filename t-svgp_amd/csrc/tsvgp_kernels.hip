@@ -1675,21 +1675,28 @@ __global__ __launch_bounds__(TILE) void lik_map_hetero_kernel(const T* __restric
 // and gpflow.likelihoods.Poisson (exp link) [ext], GPflow 2.2.1 -- as a map of their own behind the moments, one latent column
 // per launch: (mean, var, Y) with element stride istride -> g0 = d ve / d mean, g1 = d ve / d var with element stride ostride
 // (rows >= N zero; g1 cropped at -1e-8 unless TSVGP_LIK_NOCROP, a NaN stays NaN as under np.minimum), per-128-row sums of ve and
-// (StudentT, dparam_partial != nullptr) of d ve / d scale, and the count of rows with var <= 0 or a non-finite mean.
+// (StudentT: d ve / d scale, Gamma: d ve / d shape; dparam_partial != nullptr) of the parameter derivative, and the count of rows
+// with var <= 0 or a non-finite mean (Gamma: or a target outside its support).
 //   StudentT (p0 = scale s, p1 = df nu, c0 = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log s from the host):
 //     log p(y | f) = c0 - (nu+1)/2 log1p(r^2 / nu),  r = (y - f) / s;  ve and the derivative OF THE 20-point Gauss-Hermite sum:
 //     g0 = sum_i w_i l'(f_i),  g1 = sum_i w_i l'(f_i) z_i / (2 sqrt v),  f_i = m + sqrt(v) z_i,  l' = (nu+1) r / (s nu (1 + r^2/nu)),
 //     d l / d s = ((nu+1) u / (1 + u) - 1) / s with u = r^2 / nu.
 //   Poisson (p0 = binsize b, c0 = log b): the closed form GPflow takes under the exp link,
 //     ve = y (m + log b) - b exp(m + v/2) - lgamma(y + 1),  g0 = y - b exp(m + v/2),  g1 = -1/2 b exp(m + v/2).
+//   Gamma (p0 = shape a, c0 = lgamma(a), c1 = digamma(a) from the host; gpflow.likelihoods.Gamma with its exp link, scale = exp(f);
+//   a == 1 is gpflow.likelihoods.Exponential): closed like Poisson's, with e = y exp(-m + v/2),
+//     ve = -a m - lgamma(a) + (a - 1) log y - e,  g0 = -a + e,  g1 = -e / 2,  d ve / d a = -m - digamma(a) + log y;
+//     at a == 1 exactly the term (a - 1) log y is skipped, not multiplied: y = 0 is then a legal target.  A row with y < 0, or with
+//     y == 0 at a != 1, is counted with the bad rows and its ve is NaN.
 // fp64 arithmetic for either array type (the map moves 5 N elements and is bound by them).  One thread per row, one workgroup per
 // 128 rows; the sums are wave-reduced and written once per workgroup, no atomics: two calls agree bit for bit.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(TILE) void lik_map_scalar_kernel(const T* __restrict__ mean, const T* __restrict__ var,
                                                               const T* __restrict__ Y, int64_t istride, int lik, double p0,
-                                                              double p1, double c0, T* __restrict__ g0o, T* __restrict__ g1o,
-                                                              int64_t ostride, double* __restrict__ ve_partial,
+                                                              double p1, double c0, double c1, T* __restrict__ g0o,
+                                                              T* __restrict__ g1o, int64_t ostride,
+                                                              double* __restrict__ ve_partial,
                                                               double* __restrict__ dparam_partial,
                                                               int32_t* __restrict__ nonpos_partial, int64_t N) {
     __shared__ double red[TILE / 64], redp[TILE / 64];
@@ -1701,6 +1708,7 @@ __global__ __launch_bounds__(TILE) void lik_map_scalar_kernel(const T* __restric
     int bad = 0;
     if (live) {
         const double m = (double)mean[n * istride], v = (double)var[n * istride], y = (double)Y[n * istride];
+        bool ybad = false;
         if ((lik & 0xFF) == TSVGP_LIK_STUDENT_T) {
             const double sd = sqrt(v), inv_s = 1.0 / p0, nu1 = p1 + 1.0, inv_nu = 1.0 / p1;
             double a0 = 0.0, a1 = 0.0;
@@ -1718,6 +1726,19 @@ __global__ __launch_bounds__(TILE) void lik_map_scalar_kernel(const T* __restric
             g0 = a0;
             g1 = a1 / (2.0 * sd);
             dp *= inv_s;
+        } else if ((lik & 0xFF) == TSVGP_LIK_GAMMA) {
+            const double e = y * exp(-m + 0.5 * v);
+            const bool unit = p0 == 1.0;  // Exponential: no power of y in the density
+            const double ly = (!unit || dparam_partial) ? log(y) : 0.0;
+            ve = -p0 * m - c0 - e;
+            if (!unit) ve += (p0 - 1.0) * ly;
+            g0 = -p0 + e;
+            g1 = -0.5 * e;
+            dp = -m - c1 + ly;
+            if (!(y > 0.0 || (unit && y == 0.0))) {  // outside the support (a NaN target too)
+                ve = __builtin_nan("");
+                ybad = true;
+            }
         } else {  // TSVGP_LIK_POISSON
             const double e = p0 * exp(m + 0.5 * v);
             ve = y * (m + c0) - e - lgamma(y + 1.0);
@@ -1725,7 +1746,110 @@ __global__ __launch_bounds__(TILE) void lik_map_scalar_kernel(const T* __restric
             g1 = -0.5 * e;
         }
         if (!(lik & TSVGP_LIK_NOCROP) && g1 > -1e-8) g1 = -1e-8;  // reference tsvgp.py:262-263
-        bad = (v > 0.0 && isfinite(m)) ? 0 : 1;
+        bad = (v > 0.0 && isfinite(m) && !ybad) ? 0 : 1;
+    }
+    g0o[n * ostride] = (T)g0;  // rows >= N of the padded outputs: zeros
+    g1o[n * ostride] = (T)g1;
+    double s = ve, d = dp;
+    int c = bad;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        d += __shfl_xor(d, o);
+        c += __shfl_xor(c, o);
+    }
+    if (lane == 0) {
+        red[w] = s;
+        redp[w] = d;
+        redi[w] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        ve_partial[blockIdx.x] = red[0] + red[1];
+        if (dparam_partial) dparam_partial[blockIdx.x] = redp[0] + redp[1];
+        nonpos_partial[blockIdx.x] = redi[0] + redi[1];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// lik_map_ordinal_kernel: gpflow.likelihoods.Ordinal(bin_edges) [ext], GPflow 2.2.1 -- one latent, K = n_edges + 1 ordered bins,
+// label y in {0 .. K-1}; one latent column per launch with the strides, outputs and partials of lik_map_scalar_kernel.  With
+// up = edges[y] (+inf for y = K-1), lo = edges[y-1] (-inf for y = 0), a = (up - f) / sigma, b = (lo - f) / sigma,
+//     Phi~(x) = Phi(x) (1 - 2e-3) + 1e-3,   phi = Phi~(a) - Phi~(b),   log p(y | f) = log(phi + 1e-6),
+// ve the 20-point Gauss-Hermite sum over f_i = m + sqrt(v) z_i and g0, g1, dparam the derivatives OF THAT SUM:
+//     l'(f) = -(1 - 2e-3) (N(a) - N(b)) / (sigma (phi + 1e-6)),   d l / d sigma = -(1 - 2e-3) (a N(a) - b N(b)) / (sigma (phi + 1e-6)),
+//     g0 = sum_i w_i l'(f_i),   g1 = sum_i w_i l'(f_i) z_i / (2 sqrt v),   dparam = sum_n sum_i w_i d l / d sigma
+// (N the standard normal density; the terms of an infinite edge are 0).  The two jitters 1e-3 cancel in phi, and what is left,
+// (1 - 2e-3) (Phi(a) - Phi(b)), is taken from erfc on the side where both arguments are small: Phi(a) - Phi(b) = Q(b) - Q(a) when
+// b > 0 -- the difference of two values near 1 would lose every digit of a far-tail bin.  The edges are staged into LDS once per
+// workgroup (at most 255 doubles); the label selects two of them and is checked first: one that is no integer in [0, K) reads
+// edge 0, makes the row's ve, g0, g1 NaN and counts the row as bad (lik_map_robustmax_kernel's convention).  Per row 40 erfc,
+// 40 exp, 20 log: the map is bound by fp64 VALU work, not by its 5 N elements.  fp64 arithmetic for either array type; one thread
+// per row, one workgroup per 128 rows, wave-reduced sums written once per workgroup, no atomics.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ordinal_node(double a, double b, bool a_inf, bool b_inf, double& logp, double& dl, double& ds) {
+    const bool flip = b > 0.0;  // both arguments in the upper tail: take the difference of the upper tail masses
+    const double hi = flip ? -b : a, lw = flip ? -a : b;
+    const double phi = (0.5 * (1.0 - 2e-3)) * (erfc(-0.70710678118654752440 * hi) - erfc(-0.70710678118654752440 * lw));
+    const double q = phi + 1e-6;
+    const double na = a_inf ? 0.0 : 0.39894228040143267794 * exp(-0.5 * a * a);
+    const double nb = b_inf ? 0.0 : 0.39894228040143267794 * exp(-0.5 * b * b);
+    const double r = (1.0 - 2e-3) / q;
+    logp = log(q);
+    dl = -(na - nb) * r;
+    ds = -((a_inf ? 0.0 : a * na) - (b_inf ? 0.0 : b * nb)) * r;
+}
+
+template <typename T>
+__global__ __launch_bounds__(TILE) void lik_map_ordinal_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                               const T* __restrict__ Y, int64_t istride, int flags,
+                                                               const double* __restrict__ edges, int n_edges, double sigma,
+                                                               T* __restrict__ g0o, T* __restrict__ g1o, int64_t ostride,
+                                                               double* __restrict__ ve_partial,
+                                                               double* __restrict__ dparam_partial,
+                                                               int32_t* __restrict__ nonpos_partial, int64_t N) {
+    __shared__ double ed[TSVGP_ORDINAL_MAX_EDGES + 1];
+    __shared__ double red[TILE / 64], redp[TILE / 64];
+    __shared__ int redi[TILE / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n = (int64_t)blockIdx.x * TILE + t;
+    const bool live = n < N;
+    for (int i = t; i < n_edges; i += TILE) ed[i] = edges[i];
+    __syncthreads();
+    double g0 = 0.0, g1 = 0.0, ve = 0.0, dp = 0.0;
+    int bad = 0;
+    if (live) {
+        const double m = (double)mean[n * istride], v = (double)var[n * istride], y = (double)Y[n * istride];
+        const bool ok = y >= 0.0 && y <= (double)n_edges && y == floor(y);
+        const int k = ok ? (int)y : 0;  // 0 <= k <= n_edges: ed[k] is read for k < n_edges, ed[k - 1] for k > 0
+        const bool top = k == n_edges, bottom = k == 0;
+        const double inf = __builtin_inf();
+        const double up = top ? inf : ed[k], lo = bottom ? -inf : ed[k - 1];
+        const double sd = sqrt(v), inv_s = 1.0 / sigma;
+        const double a0 = (up - m) * inv_s, b0 = (lo - m) * inv_s, dz = sd * inv_s;
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll 2
+        for (int i = 0; i < 10; ++i) {  // node pairs +-z: f = m +- sd z, so a = a0 -+ dz z
+            const double z = GH_X[i], wi = GH_W[i];
+            double lp, dlp, dsp, lm, dlm, dsm;
+            ordinal_node(a0 - dz * z, b0 - dz * z, top, bottom, lp, dlp, dsp);
+            ordinal_node(a0 + dz * z, b0 + dz * z, top, bottom, lm, dlm, dsm);
+            ve += wi * (lp + lm);
+            s0 += wi * (dlp + dlm);
+            s1 += wi * z * (dlp - dlm);
+            dp += wi * (dsp + dsm);
+        }
+        g0 = s0 * inv_s;
+        g1 = s1 * inv_s / (2.0 * sd);
+        dp *= inv_s;
+        if (!(flags & TSVGP_LIK_NOCROP) && g1 > -1e-8) g1 = -1e-8;  // reference tsvgp.py:262-263; a NaN stays NaN
+        if (!ok) {
+            const double poison = __builtin_nan("");
+            ve = poison;
+            g0 = poison;
+            g1 = poison;
+        }
+        bad = (v > 0.0 && isfinite(m) && ok) ? 0 : 1;
     }
     g0o[n * ostride] = (T)g0;  // rows >= N of the padded outputs: zeros
     g1o[n * ostride] = (T)g1;
@@ -5029,6 +5153,19 @@ int lik_map_hetero(const T* mean, const T* var, const T* Y, int flags, T* g0, T*
     return launch_status();
 }
 
+// digamma(x), x > 0, on the host (the Gamma arm's d lgamma(a) / d a): the recurrence up to x >= 10, then the asymptotic series,
+// whose first dropped term is 691 / (32760 x^12) < 3e-14 there.
+static double digamma_host(double x) {
+    double r = 0.0;
+    while (x < 10.0) {
+        r -= 1.0 / x;
+        x += 1.0;
+    }
+    const double f = 1.0 / (x * x);
+    return r + std::log(x) - 0.5 / x -
+           f * (1.0 / 12.0 - f * (1.0 / 120.0 - f * (1.0 / 252.0 - f * (1.0 / 240.0 - f * (1.0 / 132.0)))));
+}
+
 template <typename T>
 int lik_map_scalar(const T* mean, const T* var, const T* Y, int64_t in_stride, int lik, double param0, double param1, T* g0, T* g1,
                    int64_t out_stride, double* ve_partial, double* dparam_partial, int32_t* nonpos_partial, int64_t N, int64_t Np,
@@ -5037,7 +5174,7 @@ int lik_map_scalar(const T* mean, const T* var, const T* Y, int64_t in_stride, i
     if (in_stride < 1 || out_stride < 1) return TSVGP_EINVAL;
     if (lik & ~(0xFF | TSVGP_LIK_NOCROP)) return TSVGP_EINVAL;
     const int base = lik & 0xFF;
-    double c0;
+    double c0, c1 = 0.0;
     if (base == TSVGP_LIK_STUDENT_T) {
         if (!(param0 > 0.0) || !(param1 > 0.0) || !std::isfinite(param0) || !std::isfinite(param1)) return TSVGP_EINVAL;
         // the terms of log p that no row changes, once, on the host
@@ -5046,11 +5183,30 @@ int lik_map_scalar(const T* mean, const T* var, const T* Y, int64_t in_stride, i
     } else if (base == TSVGP_LIK_POISSON) {
         if (!(param0 > 0.0) || !std::isfinite(param0) || dparam_partial) return TSVGP_EINVAL;
         c0 = std::log(param0);
+    } else if (base == TSVGP_LIK_GAMMA) {
+        if (!(param0 > 0.0) || !std::isfinite(param0)) return TSVGP_EINVAL;
+        c0 = std::lgamma(param0);
+        c1 = digamma_host(param0);
     } else {
         return TSVGP_EINVAL;
     }
     hipLaunchKernelGGL(lik_map_scalar_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(TILE), 0, (hipStream_t)stream, mean, var, Y,
-                       in_stride, lik, param0, param1, c0, g0, g1, out_stride, ve_partial, dparam_partial, nonpos_partial, N);
+                       in_stride, lik, param0, param1, c0, c1, g0, g1, out_stride, ve_partial, dparam_partial, nonpos_partial, N);
+    return launch_status();
+}
+
+template <typename T>
+int lik_map_ordinal(const T* mean, const T* var, const T* Y, int64_t in_stride, int flags, const double* edges, int n_edges,
+                    double sigma, T* g0, T* g1, int64_t out_stride, double* ve_partial, double* dparam_partial,
+                    int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    if (!mean || !var || !Y || !g0 || !g1 || !ve_partial || !nonpos_partial || N <= 0 || Np < N || (Np % TILE)) return TSVGP_EINVAL;
+    if (in_stride < 1 || out_stride < 1) return TSVGP_EINVAL;
+    if ((flags & ~TSVGP_LIK_NOCROP) != TSVGP_LIK_ORDINAL) return TSVGP_EINVAL;
+    if (!edges || n_edges < 1 || n_edges > TSVGP_ORDINAL_MAX_EDGES) return TSVGP_EINVAL;
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return TSVGP_EINVAL;
+    if (Np / TILE > 0x7fffffff) return TSVGP_EINVAL;  // the grid's block count is 31 bits
+    hipLaunchKernelGGL(lik_map_ordinal_kernel<T>, dim3((unsigned)(Np / TILE)), dim3(TILE), 0, (hipStream_t)stream, mean, var, Y,
+                       in_stride, flags, edges, n_edges, sigma, g0, g1, out_stride, ve_partial, dparam_partial, nonpos_partial, N);
     return launch_status();
 }
 
@@ -6209,6 +6365,19 @@ int tsvgp_lik_map_scalar_f64(const double* mean, const double* var, const double
                              int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
     return lik_map_scalar<double>(mean, var, Y, in_stride, lik, param0, param1, g0, g1, out_stride, ve_partial, dparam_partial,
                                   nonpos_partial, N, Np, stream);
+}
+int tsvgp_lik_map_ordinal_f64(const double* mean, const double* var, const double* Y, int64_t in_stride, int flags,
+                              const double* edges, int n_edges, double sigma, double* g0, double* g1, int64_t out_stride,
+                              double* ve_partial, double* dparam_partial, int32_t* nonpos_partial, int64_t N, int64_t Np,
+                              void* stream) {
+    return lik_map_ordinal<double>(mean, var, Y, in_stride, flags, edges, n_edges, sigma, g0, g1, out_stride, ve_partial,
+                                   dparam_partial, nonpos_partial, N, Np, stream);
+}
+int tsvgp_lik_map_ordinal_f32(const float* mean, const float* var, const float* Y, int64_t in_stride, int flags, const double* edges,
+                              int n_edges, double sigma, float* g0, float* g1, int64_t out_stride, double* ve_partial,
+                              double* dparam_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
+    return lik_map_ordinal<float>(mean, var, Y, in_stride, flags, edges, n_edges, sigma, g0, g1, out_stride, ve_partial,
+                                  dparam_partial, nonpos_partial, N, Np, stream);
 }
 int tsvgp_lik_map_scalar_f32(const float* mean, const float* var, const float* Y, int64_t in_stride, int lik, double param0,
                              double param1, float* g0, float* g1, int64_t out_stride, double* ve_partial, double* dparam_partial,

@@ -19,7 +19,7 @@ A likelihood that couples the latents of a row (``LIK_HETERO``: two latents, ``L
 the moments kernels' per-latent epilogue: its pass runs the moments of every latent with no likelihood (mean, var), then its map
 on them, then the site sums of the route -- ``run`` with P = latent_dim on one kernel, ``_run_batched`` on separate kernels, and a
 two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments
-kernels (``LIK_STUDENT_T``, ``LIK_POISSON``; Y [N x P], one column per latent) take the same passes.  Every map from
+kernels (``LIK_STUDENT_T``, ``LIK_POISSON``, ``LIK_GAMMA``, ``LIK_ORDINAL``; Y [N x P], one column per latent) take the same passes.  Every map from
 (mean, var, Y) to (g0, g1, ve, nonpos) that runs as a launch of its own, the Gaussian / Bernoulli one of the stored-tile and
 two-product passes included, goes through ``EStepEngine.lik_map``.  The two other N-sized launches of a pass have one entry each
 as well, for the shared operand [Np, Mp] and the per-latent one [P, Np, Mp] alike: ``EStepEngine.moments`` (``_moments_then_map`` is
@@ -58,7 +58,8 @@ class EStepStats:
     g0: Optional[torch.Tensor] = None  # [N, P]
     g1: Optional[torch.Tensor] = None  # [N, P]
     tile: Optional[torch.Tensor] = None  # [Np, Mp] the stored triangular product t_n = Tm k_n (run(keep_tile=True))
-    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d (likelihood parameter) over the rows (LIK_STUDENT_T: scale)
+    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d (likelihood parameter) over the rows (LIK_STUDENT_T: scale,
+    # LIK_GAMMA: shape, LIK_ORDINAL: sigma)
 
 
 @dataclass
@@ -69,7 +70,7 @@ class LikMapResult:
     g1: torch.Tensor  # [Np, P] d ve / d var (rows >= N zero)
     ve_partial: torch.Tensor  # fp64 sums of ve per 128 rows: [Np / 128], or [P, Np / 128] from the per-column scalar map
     nonpos_partial: torch.Tensor  # int32 counts of rows with var <= 0, the same shape
-    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d scale over the rows (LIK_STUDENT_T only)
+    dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d parameter over the rows (StudentT, Gamma, Ordinal)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -572,6 +573,10 @@ class EStepEngine:
           LIK_MULTICLASS                ``tsvgp_lik_map_robustmax_*``  P = C; ``lik_param`` is the MultiClass object: its epsilon
           LIK_STUDENT_T, LIK_POISSON    ``tsvgp_lik_map_scalar_*``     ``lik_param`` = (param0, param1); one launch per column, each with
                                         its own run of the partials [P, Np / 128]; StudentT: ``dparam`` = sum d ve / d scale
+          LIK_GAMMA                     ``tsvgp_lik_map_scalar_*``     ``lik_param`` = (shape, 0) (Exponential: (1, 0, False), no ``dparam``);
+                                        ``dparam`` = sum d ve / d shape
+          LIK_ORDINAL                   ``tsvgp_lik_map_ordinal_*``    ``lik_param`` is the Ordinal object: its fp64 edges on this device
+                                        and sigma; launches and partials as the scalar maps'; ``dparam`` = sum d ve / d sigma
         Outputs the caller does not hand in are cached buffers of their own ("coupled_g0/g1", "ve_partial" / "nonpos_partial",
         "scalar_*"): the site sums read them where they are, and a one-latent pass of the same call (``site_grads``) does not
         overwrite them."""
@@ -579,7 +584,7 @@ class EStepEngine:
         lik = lik_id & 0xFF
         P = mean.shape[1]
         nblk = Np // B.TILE
-        scalar = lik in B.SCALAR_MAP_LIKS
+        scalar = lik in B.COLUMN_MAP_LIKS  # one launch per latent column
         g0 = self._get("coupled_g0", (Np, P), T) if g0 is None else g0
         g1 = self._get("coupled_g1", (Np, P), T) if g1 is None else g1
         key, shape = ("scalar_", (P, nblk)) if scalar else ("", (nblk,))
@@ -610,13 +615,23 @@ class EStepEngine:
                                      f"{tuple(Y.shape)}")
                 if not (mean.is_contiguous() and var.is_contiguous() and Y.is_contiguous()):
                     raise ValueError("the scalar likelihood map reads contiguous [N, P] arrays")
-                p0, p1 = (float(x) for x in lik_param)
-                dpar = self._get("scalar_dparam_partial", (P, nblk), torch.float64) if lik == B.LIK_STUDENT_T else None
-                fn = self._fn("tsvgp_lik_map_scalar", T)
+                # a likelihood with a trainable parameter: StudentT's scale, Gamma's shape, Ordinal's sigma (Exponential, the Gamma
+                # arm at shape 1, has none and says so with a third entry: (1, 0, False))
+                trainable = lik in (B.LIK_STUDENT_T, B.LIK_GAMMA, B.LIK_ORDINAL) and not (
+                    lik == B.LIK_GAMMA and len(lik_param) > 2 and not lik_param[2])
+                dpar = self._get("scalar_dparam_partial", (P, nblk), torch.float64) if trainable else None
+                if lik == B.LIK_ORDINAL:  # ``lik_param`` is the Ordinal object: its edges on this device, its sigma
+                    edges, sigma = lik_param.device_edges(self.device), float(lik_param.sigma.item())
+                    fn = self._fn("tsvgp_lik_map_ordinal", T)
+                    name, args = "tsvgp_lik_map_ordinal", (int(lik_id), edges.data_ptr(), int(edges.numel()), sigma)
+                else:
+                    p0, p1 = float(lik_param[0]), float(lik_param[1])
+                    fn = self._fn("tsvgp_lik_map_scalar", T)
+                    name, args = "tsvgp_lik_map_scalar", (int(lik_id), p0, p1)
                 for p in range(P):
                     off = p * mean.element_size()
-                    self._launch("tsvgp_lik_map_scalar", lambda: fn(
-                        ins[0] + off, ins[1] + off, ins[2] + off, P, int(lik_id), p0, p1, outs[0] + off, outs[1] + off, P,
+                    self._launch(name, lambda: fn(
+                        ins[0] + off, ins[1] + off, ins[2] + off, P, *args, outs[0] + off, outs[1] + off, P,
                         ve_partial[p].data_ptr(), _ptr(None if dpar is None else dpar[p]), nonpos_partial[p].data_ptr(), N, Np,
                         self._stream()))
                 res.dparam = None if dpar is None else dpar.sum()

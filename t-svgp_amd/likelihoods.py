@@ -2,7 +2,9 @@
 ``HeteroskedasticTFPConditional`` (Normal with an Exp scale over two latents, 20 x 20 Gauss-Hermite), ``Softmax`` (C latents,
 Monte Carlo with an in-kernel counter-based generator: ``tsvgp_lik_map_softmax_*``), ``StudentT`` (20-point Gauss-Hermite) and
 ``Poisson`` (exp link, closed form): the last two one latent per target column, ``tsvgp_lik_map_scalar_*`` behind the moments;
-``MultiClass`` (C latents, ``RobustMax`` link, 20-point Gauss-Hermite over the labelled latent: ``tsvgp_lik_map_robustmax_*``).
+``MultiClass`` (C latents, ``RobustMax`` link, 20-point Gauss-Hermite over the labelled latent: ``tsvgp_lik_map_robustmax_*``);
+``Gamma`` and ``Exponential`` (exp link, closed form: a third arm of ``tsvgp_lik_map_scalar_*``) and ``Ordinal`` (ordered bins over
+one latent, 20-point Gauss-Hermite: ``tsvgp_lik_map_ordinal_*``), one latent per target column like StudentT and Poisson.
 
 Their N-sized maps -- variational expectations and the (mean, var) gradients the E-step needs
 (reference src/models/tsvgp.py:256-263) -- run inside the fused HIP moments kernel
@@ -164,6 +166,199 @@ class Poisson:
 def _named(obj, name: str) -> bool:
     """``obj`` is a class called ``name`` or an instance of one (tfp.distributions.Normal, tfp.bijectors.Exp())."""
     return getattr(obj, "__name__", type(obj).__name__) == name
+
+
+def mapped_parameter(likelihood):
+    """("likelihood_<name>", Parameter) of the one trainable parameter whose derivative the likelihood's own map returns
+    (``LikMapResult.dparam``): StudentT's scale, Gamma's shape, Ordinal's sigma; None for every other likelihood."""
+    name = {B.LIK_STUDENT_T: "scale", B.LIK_GAMMA: "shape", B.LIK_ORDINAL: "sigma"}.get(getattr(likelihood, "lik_id", None))
+    par = getattr(likelihood, name, None) if name else None  # (Exponential is the Gamma arm without a shape)
+    return (f"likelihood_{name}", par) if isinstance(par, Parameter) else None
+
+
+def _require_exp_link(cls: str, invlink, kwargs):
+    if invlink is not None and invlink is not torch.exp and invlink is not np.exp and not _named(invlink, "exp"):
+        raise NotImplementedError(f"{cls}: only the exp inverse link is implemented, got {invlink!r}")
+    if kwargs:
+        raise NotImplementedError(f"{cls}: unsupported arguments {sorted(kwargs)}")
+
+
+class _ScalarQuadrature:
+    """The predictive helpers of GPflow's ``ScalarLikelihood`` [ext] over the 20 Gauss-Hermite nodes, for a likelihood that gives
+    ``log_prob(F, Y)``, ``conditional_mean(F)`` and ``conditional_variance(F)`` elementwise; Y [N, P], one column per latent."""
+
+    latent_dim = 1
+    num_gauss_hermite_points = 20
+
+    def _nodes(self, Fmu, Fvar):
+        z, logw = _gh_nodes(Fmu, self.num_gauss_hermite_points)
+        return Fmu[..., None] + torch.sqrt(Fvar)[..., None] * z, logw
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        """E[y] = E_q[E[y | f]], Var[y] = E_q[Var[y | f] + E[y | f]^2] - E[y]^2 over the 20 nodes."""
+        F, logw = self._nodes(Fmu, Fvar)
+        w = torch.exp(logw)
+        cm = self.conditional_mean(F)
+        ey = torch.sum(w * cm, dim=-1)
+        return ey, torch.sum(w * (self.conditional_variance(F) + cm * cm), dim=-1) - ey * ey
+
+    def predict_log_density(self, Fmu, Fvar, Y):
+        """log sum_i w_i p(y | f_i) over the 20 nodes, in log space, summed over the columns; [N]."""
+        F, logw = self._nodes(Fmu, Fvar)
+        return torch.sum(torch.logsumexp(self.log_prob(F, Y[..., None]) + logw, dim=-1), dim=-1)
+
+
+class Gamma(_ScalarQuadrature):
+    """gpflow.likelihoods.Gamma(invlink, shape) [ext] (GPflow 2.2.1) with its default exp inverse link: y ~ Gamma(shape a,
+    scale exp(f)), ``shape`` a trainable positive parameter; any other ``invlink`` raises NotImplementedError.  Y [N, P] strictly
+    positive, one independent column per latent.  Under the exp link the variational expectations are closed
+    (``tsvgp_lik_map_scalar_*`` with TSVGP_LIK_GAMMA, on the GPU); the predictive helpers take 20-point Gauss-Hermite as GPflow's
+    ``ScalarLikelihood`` does.  ``t_SVGP`` and ``t_SVGP_white`` take it; ``t_SVGP_sites`` and ``t_VGP``, whose likelihood is fused
+    into another kernel, do not."""
+
+    lik_id = B.LIK_GAMMA
+
+    def __init__(self, invlink=None, shape=1.0, **kwargs):
+        _require_exp_link("Gamma", invlink, kwargs)
+        if not float(shape) > 0.0 or not math.isfinite(float(shape)):
+            raise ValueError(f"Gamma: shape must be positive and finite, got {shape!r}")
+        self.shape = Parameter(shape)
+
+    @property
+    def lik_param(self):
+        """(shape, 0): the two scalars ``tsvgp_lik_map_scalar_*`` takes."""
+        return (self.shape.item(), 0.0)
+
+    def graph_key(self):
+        """Nothing beside the stamped ``shape`` is baked into a captured step."""
+        return ()
+
+    def _shape(self) -> float:
+        return self.shape.item()
+
+    def log_prob(self, F, Y):
+        """-a f - lgamma(a) + (a - 1) log y - y exp(-f); at a == 1 the power of y is skipped (y = 0 is then a target)."""
+        a = self._shape()
+        out = -a * F - math.lgamma(a) - Y * torch.exp(-F)
+        return out if a == 1.0 else out + (a - 1.0) * torch.log(Y)
+
+    def conditional_mean(self, F):
+        return self._shape() * torch.exp(F)
+
+    def conditional_variance(self, F):
+        return self._shape() * torch.exp(2.0 * F)
+
+
+class Exponential(Gamma):
+    """gpflow.likelihoods.Exponential(invlink) [ext] (GPflow 2.2.1) with its default exp inverse link: y ~ Exp(rate exp(-f)),
+    log p = -f - y exp(-f), E[y | f] = exp(f), Var[y | f] = exp(2 f).  It is the Gamma arm of the map at shape 1 exactly, where the
+    power of y drops out of the density -- y = 0 is a legal waiting time -- and it has no trainable parameter.  Y [N, P] >= 0."""
+
+    def __init__(self, invlink=None, **kwargs):
+        _require_exp_link("Exponential", invlink, kwargs)
+
+    @property
+    def lik_param(self):
+        """(1, 0, False): the Gamma arm's two scalars and "no parameter derivative"."""
+        return (1.0, 0.0, False)
+
+    def _shape(self) -> float:
+        return 1.0
+
+
+class Ordinal(_ScalarQuadrature):
+    """gpflow.likelihoods.Ordinal(bin_edges) [ext] (GPflow 2.2.1): K = len(bin_edges) + 1 ordered classes over ONE latent,
+    Y [N, P] labels 0 .. K-1 (one independent column per latent),
+        p(y = k | f) = Phi~((e_k - f) / sigma) - Phi~((e_{k-1} - f) / sigma),   e_{-1} = -inf, e_{K-1} = +inf,
+    Phi~ the probit with GPflow's 1e-3 jitter and ``sigma`` a trainable positive parameter (1.0); log p carries GPflow's + 1e-6.
+    ``bin_edges`` are fixed at construction: 1-D, finite, strictly increasing, at most ``B.ORDINAL_MAX_EDGES`` of them.  The
+    variational expectations and their gradients run on the GPU (``tsvgp_lik_map_ordinal_*``, 20-point Gauss-Hermite, the edges
+    in an fp64 device tensor kept on this object); the predictive helpers take the same nodes.  ``t_SVGP`` and ``t_SVGP_white``
+    take it; ``t_SVGP_sites`` and ``t_VGP`` do not."""
+
+    lik_id = B.LIK_ORDINAL
+    _CHUNK = 1 << 22  # elements per [rows, P, 20, K] evaluation of predict_mean_and_var
+
+    def __init__(self, bin_edges, **kwargs):
+        if kwargs:
+            raise NotImplementedError(f"Ordinal: unsupported arguments {sorted(kwargs)}")
+        edges = np.array(bin_edges.detach().cpu().numpy() if torch.is_tensor(bin_edges) else bin_edges, dtype=np.float64)
+        if edges.ndim != 1 or not 1 <= edges.size <= B.ORDINAL_MAX_EDGES:
+            raise ValueError(f"Ordinal: bin_edges must be 1-D with 1 to {B.ORDINAL_MAX_EDGES} entries, got shape {edges.shape}")
+        if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0):
+            raise ValueError("Ordinal: bin_edges must be finite and strictly increasing")
+        edges.setflags(write=False)  # the map's kernel trusts the order: nothing edits them after this check
+        self.bin_edges = edges
+        self.num_bins = edges.size + 1
+        self.sigma = Parameter(1.0)
+        self._edges_dev = {}  # device -> fp64 [K - 1]: made once per device (a captured graph holds its address)
+
+    # the engine takes the likelihood's scalars through ``lik_param``; this one hands over itself (edges and sigma)
+    @property
+    def lik_param(self):
+        return self
+
+    def graph_key(self):
+        """What a captured step bakes in beside the stamped ``sigma``: the edges."""
+        return tuple(self.bin_edges.tolist())
+
+    def device_edges(self, device) -> torch.Tensor:
+        """The edges the map reads: one fp64 tensor per device for the life of this object."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        edges = self._edges_dev.get(device)
+        if edges is None:
+            edges = self._edges_dev[device] = torch.tensor(self.bin_edges.tolist(), dtype=torch.float64).to(device)
+        return edges
+
+    def _scaled_edges(self, ref):
+        """(a, b) numerators: upper edges [K] with +inf last, lower edges [K] with -inf first, in the dtype and on the device of ``ref``."""
+        e = torch.tensor(self.bin_edges.tolist(), dtype=ref.dtype, device=ref.device)
+        inf = torch.full((1,), float("inf"), dtype=ref.dtype, device=ref.device)
+        return torch.cat([e, inf]), torch.cat([-inf, e])
+
+    @staticmethod
+    def _probit(x):
+        return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) * (1.0 - 2e-3) + 1e-3
+
+    def log_prob(self, F, Y):
+        """log(Phi~(a) - Phi~(b) + 1e-6); the difference, (1 - 2e-3)(Phi(a) - Phi(b)), from erfc on the side where both tail masses
+        are small (as the kernel takes it).  A label that is no integer in [0, K) gives NaN."""
+        up, lo = self._scaled_edges(F)
+        Yf = torch.broadcast_to(Y.to(F.dtype), F.shape)
+        ok = (Yf >= 0) & (Yf <= self.num_bins - 1) & (Yf == torch.floor(Yf))
+        k = torch.where(ok, Yf, torch.zeros_like(Yf)).long()
+        s = self.sigma.value.to(F.device, F.dtype)
+        a, b = (up[k] - F) / s, (lo[k] - F) / s
+        flip = b > 0
+        hi, lw = torch.where(flip, -b, a), torch.where(flip, -a, b)
+        r = math.sqrt(0.5)
+        phi = 0.5 * (1.0 - 2e-3) * (torch.special.erfc(-r * hi) - torch.special.erfc(-r * lw))
+        return torch.where(ok, torch.log(phi + 1e-6), torch.full_like(phi, float("nan")))
+
+    def _phi(self, F):
+        """[..., K]: the probability of every bin at F, without the 1e-6 (GPflow's ``_make_phi``)."""
+        up, lo = self._scaled_edges(F)
+        s = self.sigma.value.to(F.device, F.dtype)
+        return self._probit((up - F[..., None]) / s) - self._probit((lo - F[..., None]) / s)
+
+    def conditional_mean(self, F):
+        ks = torch.arange(self.num_bins, dtype=F.dtype, device=F.device)
+        return self._phi(F) @ ks
+
+    def conditional_variance(self, F):
+        ks = torch.arange(self.num_bins, dtype=F.dtype, device=F.device)
+        phi = self._phi(F)
+        return phi @ (ks * ks) - torch.square(phi @ ks)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        """E[y | f] = sum_k k phi_k, Var[y | f] = sum_k k^2 phi_k - E[y | f]^2 under the 20 nodes, row chunk by row chunk."""
+        per_row = max(1, int(np.prod(Fmu.shape[1:]))) * self.num_gauss_hermite_points * self.num_bins
+        rows = max(1, self._CHUNK // per_row)
+        parts = [_ScalarQuadrature.predict_mean_and_var(self, Fmu[lo:lo + rows], Fvar[lo:lo + rows])
+                 for lo in range(0, max(Fmu.shape[0], 1), rows)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
 
 class HeteroskedasticTFPConditional:

@@ -42,6 +42,7 @@ from ..estep import EStepStats, per_latent
 from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
 from ..kernels import SeparateIndependent, latent_kernels
+from ..likelihoods import mapped_parameter
 from ..sites import DenseSites
 from ..util import (
     bmv,
@@ -846,8 +847,9 @@ class t_SVGP(base_SVGP):
         which splits into an N-sized contraction with dK_fu (HIP: fill, moments, the site sums a1 = sum g0 k,
         A2 = sum g1 k k^T, U = K_fu Q, and ``tsvgp_kernel_grad``) and an M x M part in which a1, A2 are constants
         (torch autograd over K_uu(theta, Z), its factorisations and the KL).
-        Returns (elbo, {"variance", "lengthscales", "Z", "likelihood_variance" (Gaussian only), "likelihood_scale" (StudentT
-        only: the sum of d ve / d scale comes out of the likelihood map's own pass)}), gradients of the ELBO
+        Returns (elbo, {"variance", "lengthscales", "Z", "likelihood_variance" (Gaussian only), "likelihood_scale" (StudentT),
+        "likelihood_shape" (Gamma) or "likelihood_sigma" (Ordinal): the sum of d ve / d parameter comes out of the likelihood map's
+        own pass}), gradients of the ELBO
         with respect to the constrained parameter values; with one kernel per latent (``SeparateIndependent``) the kernel
         entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales".  With more than one rank ``data`` is this
         rank's shard."""
@@ -926,8 +928,8 @@ class t_SVGP(base_SVGP):
             st.acc2, st.acc1 = torch.cat([s_.acc2 for s_ in parts], dim=0), torch.cat([s_.acc1 for s_ in parts], dim=0)
         if mapped:
             st.ve_sum, st.nonpos = stc.ve_sum, stc.nonpos
-        student = self.likelihood.lik_id == B.LIK_STUDENT_T
-        if student:  # sum_n d ve_n / d scale, summed over the ranks with the residual's slot (Gaussian only: free here)
+        lik_par = mapped_parameter(self.likelihood)  # StudentT's scale, Gamma's shape, Ordinal's sigma
+        if lik_par is not None:  # sum_n d ve_n / d parameter, summed over the ranks with the residual's slot (Gaussian only: free here)
             res = stc.dparam
         extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1)])
         acc2, acc1, ve_sum, nonpos, rows, tail = D_.reduce_stats(st, P, M, True, self._reduce(), eng, extra=extra)
@@ -997,8 +999,8 @@ class t_SVGP(base_SVGP):
         if gaussian:
             s2 = self.likelihood.lik_param
             grads["likelihood_variance"] = scale * (-0.5 * rows * P / s2 + 0.5 * res / (s2 * s2))
-        if student:
-            grads["likelihood_scale"] = scale * res
+        if lik_par is not None:
+            grads[lik_par[0]] = scale * res
         elbo = ve_sum * scale - kl
         return elbo, grads
 

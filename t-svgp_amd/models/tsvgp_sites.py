@@ -46,7 +46,7 @@ from .tsvgp_white import t_SVGP_white
 
 class t_SVGP_sites(base_SVGP):
     """Class for the t-SVGP model with sites (reference src/models/tsvgp_sites.py:20-191).  Likelihoods: Gaussian and Bernoulli,
-    the arms of the fused site step (``tsvgp_diag_site_step_*``); ``StudentT`` and ``Poisson``, whose map is a kernel of its own
+    the arms of the fused site step (``tsvgp_diag_site_step_*``); ``StudentT``, ``Poisson``, ``Gamma``, ``Exponential`` and ``Ordinal``, whose map is a kernel of its own
     behind the moments of ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here."""
 
     # the M x M algebra and the route logic are t_SVGP_white's, on the projected (l, L) in place of its state
@@ -67,7 +67,7 @@ class t_SVGP_sites(base_SVGP):
                  lambda_1=None, lambda_2=None, num_latent=1, compute_dtype=None, device=None, projection="auto",
                  skip_unused_variance=False):
         x_data, y_data = data
-        if getattr(likelihood, "lik_id", None) in B.SCALAR_MAP_LIKS:
+        if getattr(likelihood, "lik_id", None) in B.COLUMN_MAP_LIKS:
             raise NotImplementedError(f"t_SVGP_sites does not take the {type(likelihood).__name__} likelihood: its likelihood map is "
                                       "fused into tsvgp_diag_site_step_*, which has Gaussian and Bernoulli arms only; use t_SVGP or "
                                       "t_SVGP_white")

@@ -48,7 +48,7 @@ from ..sites import DiagSites
 
 class t_VGP:
     """Class for the t-VGP model (reference src/models/tvgp.py:18-193).  Likelihoods: Gaussian and Bernoulli, the arms of the fused
-    row sweep (``tsvgp_vgp_rows_f64``); ``StudentT`` and ``Poisson``, whose map is a kernel of its own behind the moments of
+    row sweep (``tsvgp_vgp_rows_f64``); ``StudentT``, ``Poisson``, ``Gamma``, ``Exponential`` and ``Ordinal``, whose map is a kernel of its own behind the moments of
     ``t_SVGP`` / ``t_SVGP_white``, raise NotImplementedError here.  Like ``sample_functions``, the input gradients of the prediction
     (``predict_f_vjp``, ``predict_f`` under torch autograd) belong to the sparse models only: ``predict_f`` here returns no graph."""
 
@@ -61,7 +61,7 @@ class t_VGP:
         if getattr(likelihood, "lik_id", None) in B.COUPLED_LIKS or getattr(likelihood, "latent_dim", 1) != 1:
             raise ValueError("t_VGP is defined for a likelihood over one latent GP (tvgp.py:85: sW sW^T * K), got "
                              f"{type(likelihood).__name__}")
-        if getattr(likelihood, "lik_id", None) in B.SCALAR_MAP_LIKS:
+        if getattr(likelihood, "lik_id", None) in B.COLUMN_MAP_LIKS:
             raise NotImplementedError(f"t_VGP does not take the {type(likelihood).__name__} likelihood: its likelihood map is fused "
                                       "into tsvgp_vgp_rows_f64, which has Gaussian and Bernoulli arms only; use t_SVGP or t_SVGP_white")
         self.device = torch.device(device) if device is not None else default_device()

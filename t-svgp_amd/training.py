@@ -1,6 +1,6 @@
 """E/M training loop around the HIP E-step: mirror of the t-SVGP branch of the reference's driver
 (reference experiments/uci_regression.py:90-183): ``n_e_steps`` natural-gradient E-steps, then ``n_m_steps`` Adam steps on
-the kernel variance / lengthscales, the Gaussian noise variance (or the StudentT scale) and the inducing inputs (``model.trainable_variables``
+the kernel variance / lengthscales, the Gaussian noise variance (or the StudentT scale, the Gamma shape, the Ordinal sigma) and the inducing inputs (``model.trainable_variables``
 there; the sites are not trainable, src/sites.py:56-63).
 
 GPflow optimises UNCONSTRAINED variables: positive parameters live behind a softplus transform [ext]
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import _backend as B
+from .likelihoods import mapped_parameter
 
 
 def _softplus_inv(x: torch.Tensor) -> torch.Tensor:
@@ -60,8 +60,9 @@ def trainable_parameters(model) -> dict:
         out["Z"] = (model.inducing_variable.Z, None)
     if hasattr(model.likelihood, "variance"):
         out["likelihood_variance"] = (model.likelihood.variance, VARIANCE_LOWER_BOUND)
-    if getattr(model.likelihood, "lik_id", None) == B.LIK_STUDENT_T:
-        out["likelihood_scale"] = (model.likelihood.scale, 0.0)  # gpflow.likelihoods.StudentT: scale behind positive() [ext]
+    mapped = mapped_parameter(model.likelihood)
+    if mapped is not None:  # StudentT's scale, Gamma's shape, Ordinal's sigma: each behind gpflow's positive() [ext]
+        out[mapped[0]] = (mapped[1], 0.0)
     return out
 
 
