@@ -317,6 +317,33 @@ int tsvgp_lik_map_ordinal_f32(const float *mean, const float *var, const float *
                               double *ve_partial, double *dparam_partial, int32_t *nonpos_partial, int64_t N, int64_t Np,
                               void *stream);
 
+/* (4b'''') The linear model of coregionalization (gpflow.kernels.LinearCoregionalization, gpflow.conditionals.util.mix_latent_gp,
+ *     GPflow 2.2.1 [ext]): P outputs f = W g mixed from L independent latent GPs, 1 <= L, P <= TSVGP_MAX_BATCH.  W [P x L] fp64
+ *     row-major in DEVICE memory for either array type (read at execution: a replayed graph sees the current values), staged
+ *     into LDS once per workgroup.  One thread per row, one workgroup per 128 rows, fp64 arithmetic for either array type, no
+ *     atomics and a summation order fixed by the shape: two calls agree bit for bit.  N > 0, Np a multiple of 128 with
+ *     0 <= Np - N < 128.
+ *     tsvgp_lmc_mix_*: mean_g, var_g [N x L] -> Fmu, Fvar [N x P],
+ *        Fmu[n, p] = sum_l W[p, l] mean_g[n, l],   Fvar[n, p] = sum_l W[p, l]^2 var_g[n, l];
+ *     nonpos_partial [Np / 128] or NULL: per 128 rows, the rows with any var_g <= 0 (or NaN) or a non-finite mean_g.
+ *     tsvgp_lmc_unmix_*: the chain rule of the variational expectations through the mix, g0_f, g1_f [Np x P] (d ve / d Fmu,
+ *     d ve / d Fvar, never cropped) -> g0_g, g1_g [Np x L] (rows >= N written as zeros),
+ *        g0_g[n, l] = sum_p W[p, l] g0_f[n, p],   g1_g[n, l] = sum_p W[p, l]^2 g1_f[n, p]
+ *     with g1_g cropped at -1e-8 (reference src/models/tsvgp.py:262-263) unless flags = TSVGP_LIK_NOCROP (no other bit); a NaN
+ *     stays NaN.  dW_partial [Np / 128 x P x L] or NULL (given: mean_g, var_g [N x L] are required, otherwise they are not
+ *     read): the sums over each 128 rows of  g0_f[n, p] mean_g[n, l] + 2 W[p, l] g1_f[n, p] var_g[n, l] = d ve_n / d W[p, l]; the
+ *     caller adds the blocks. */
+int tsvgp_lmc_mix_f64(const double *mean_g, const double *var_g, const double *W, double *Fmu, double *Fvar,
+                      int32_t *nonpos_partial, int64_t N, int64_t Np, int L, int P, void *stream);
+int tsvgp_lmc_mix_f32(const float *mean_g, const float *var_g, const double *W, float *Fmu, float *Fvar, int32_t *nonpos_partial,
+                      int64_t N, int64_t Np, int L, int P, void *stream);
+int tsvgp_lmc_unmix_f64(const double *g0_f, const double *g1_f, const double *W, int flags, double *g0_g, double *g1_g,
+                        const double *mean_g, const double *var_g, double *dW_partial, int64_t N, int64_t Np, int L, int P,
+                        void *stream);
+int tsvgp_lmc_unmix_f32(const float *g0_f, const float *g1_f, const double *W, int flags, float *g0_g, float *g1_g,
+                        const float *mean_g, const float *var_g, double *dW_partial, int64_t N, int64_t Np, int L, int P,
+                        void *stream);
+
 /* (4c) The per-datum site step of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-148) fused with the likelihood map of
  *     (4): mean, var, Y [N x P] -> g0, g1 as tsvgp_lik_map_* (never cropped: TSVGP_LIK_NOCROP semantics whatever lik says), then
  *     IN PLACE on the fp64 site state lambda_1, lambda_2 [Np x P]:

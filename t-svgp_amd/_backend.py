@@ -159,6 +159,12 @@ _PROTOTYPES = {
                                           c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "tsvgp_lik_map_ordinal_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "tsvgp_lmc_mix_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_lmc_mix_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_lmc_unmix_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_int64, c_int, c_int, c_void_p]),
+    "tsvgp_lmc_unmix_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_int64, c_int, c_int, c_void_p]),
     "tsvgp_diag_site_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tsvgp_diag_site_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,

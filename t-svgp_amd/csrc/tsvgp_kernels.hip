@@ -1875,6 +1875,175 @@ __global__ __launch_bounds__(TILE) void lik_map_ordinal_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// lmc_mix_kernel / lmc_unmix_kernel: the linear model of coregionalization (gpflow.kernels.LinearCoregionalization and
+// gpflow.conditionals.util.mix_latent_gp [ext], GPflow 2.2.1): P outputs f = W g of L independent latent GPs, W [P x L] fp64
+// row-major in device memory for either array type.  Per row n
+//     mix:    Fmu[n, p] = sum_l W[p, l] mean_g[n, l],        Fvar[n, p] = sum_l W[p, l]^2 var_g[n, l]
+//     unmix:  g0_g[n, l] = sum_p W[p, l] g0_f[n, p],          g1_g[n, l] = sum_p W[p, l]^2 g1_f[n, p]
+// (the chain rule of the variational expectations through the mix; g1_g cropped at -1e-8 unless TSVGP_LIK_NOCROP, a NaN stays
+// NaN), and with dW_partial the per-128-row sums of  d ve / d W[p, l] = g0_f[n, p] mean_g[n, l] + 2 W[p, l] g1_f[n, p] var_g[n, l].
+// One thread per row, one workgroup per 128 rows; W and its elementwise square are staged into LDS once per workgroup (at most
+// 2 x 32 x 32 doubles) and read as broadcasts; the sums run over l (p) in index order in registers -- B is the compile-time
+// bound of the accumulator array (8 or 32).  The block sums of dW take the 128 rows in four chunks of 32 staged into LDS, one
+// thread per (p, l) pair (up to 8 pairs per thread; with fewer than 128 pairs, 128 / (P L) threads per pair, each on every
+// G-th row, their sums added in order through LDS) adding the rows of a chunk in order: no atomics, no shuffles, an order fixed
+// by the shape.  fp64 arithmetic for either array type; O(N (L + P)) loads and stores, HBM bound.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T, int B>
+__global__ __launch_bounds__(TILE) void lmc_mix_kernel(const T* __restrict__ mean_g, const T* __restrict__ var_g,
+                                                       const double* __restrict__ W, T* __restrict__ Fmu, T* __restrict__ Fvar,
+                                                       int32_t* __restrict__ nonpos_partial, int64_t N, int L, int P) {
+    __shared__ double Ws[TSVGP_MAX_BATCH * TSVGP_MAX_BATCH], W2s[TSVGP_MAX_BATCH * TSVGP_MAX_BATCH];
+    __shared__ int redi[TILE / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n = (int64_t)blockIdx.x * TILE + t;
+    for (int i = t; i < P * L; i += TILE) {
+        const double x = W[i];
+        Ws[i] = x;
+        W2s[i] = x * x;
+    }
+    __syncthreads();
+    int bad = 0;
+    if (n < N) {
+        double am[B], av[B];
+#pragma unroll
+        for (int p = 0; p < B; ++p) am[p] = av[p] = 0.0;
+        for (int l = 0; l < L; ++l) {
+            const double m = (double)mean_g[n * L + l], v = (double)var_g[n * L + l];
+            if (!(v > 0.0) || !isfinite(m)) bad = 1;
+#pragma unroll
+            for (int p = 0; p < B; ++p)
+                if (p < P) {
+                    am[p] = fma(Ws[p * L + l], m, am[p]);
+                    av[p] = fma(W2s[p * L + l], v, av[p]);
+                }
+        }
+#pragma unroll
+        for (int p = 0; p < B; ++p)
+            if (p < P) {
+                Fmu[n * P + p] = (T)am[p];
+                Fvar[n * P + p] = (T)av[p];
+            }
+    }
+    if (nonpos_partial) {  // (uniform over the grid)
+        int c = bad;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+        if (lane == 0) redi[w] = c;
+        __syncthreads();
+        if (t == 0) nonpos_partial[blockIdx.x] = redi[0] + redi[1];
+    }
+}
+
+#define LMC_CHUNK 32
+template <typename T, int B>
+__global__ __launch_bounds__(TILE) void lmc_unmix_kernel(const T* __restrict__ g0_f, const T* __restrict__ g1_f,
+                                                         const double* __restrict__ W, int flags, T* __restrict__ g0_g,
+                                                         T* __restrict__ g1_g, const T* __restrict__ mean_g,
+                                                         const T* __restrict__ var_g, double* __restrict__ dW_partial, int64_t N,
+                                                         int L, int P) {
+    __shared__ double Ws[TSVGP_MAX_BATCH * TSVGP_MAX_BATCH], W2s[TSVGP_MAX_BATCH * TSVGP_MAX_BATCH];
+    __shared__ double c0[LMC_CHUNK * TSVGP_MAX_BATCH], c1[LMC_CHUNK * TSVGP_MAX_BATCH];  // g0_f, g1_f of a chunk [32 x P]
+    __shared__ double cm[LMC_CHUNK * TSVGP_MAX_BATCH], cv[LMC_CHUNK * TSVGP_MAX_BATCH];  // mean_g, var_g of a chunk [32 x L]
+    const int t = threadIdx.x;
+    const int64_t n0 = (int64_t)blockIdx.x * TILE, n = n0 + t;
+    for (int i = t; i < P * L; i += TILE) {
+        const double x = W[i];
+        Ws[i] = x;
+        W2s[i] = x * x;
+    }
+    __syncthreads();
+    {
+        double a0[B], a1[B];
+#pragma unroll
+        for (int l = 0; l < B; ++l) a0[l] = a1[l] = 0.0;
+        if (n < N) {
+            for (int p = 0; p < P; ++p) {
+                const double d0 = (double)g0_f[n * P + p], d1 = (double)g1_f[n * P + p];
+#pragma unroll
+                for (int l = 0; l < B; ++l)
+                    if (l < L) {
+                        a0[l] = fma(Ws[p * L + l], d0, a0[l]);
+                        a1[l] = fma(W2s[p * L + l], d1, a1[l]);
+                    }
+            }
+            if (!(flags & TSVGP_LIK_NOCROP)) {
+#pragma unroll
+                for (int l = 0; l < B; ++l)
+                    if (a1[l] > -1e-8) a1[l] = -1e-8;  // reference tsvgp.py:262-263; a NaN stays NaN
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < B; ++l)
+            if (l < L) {  // rows >= N of the padded outputs: zeros
+                g0_g[n * L + l] = (T)a0[l];
+                g1_g[n * L + l] = (T)a1[l];
+            }
+    }
+    if (!dW_partial) return;  // (uniform over the grid)
+    // P L <= 1024 pairs: thread t owns the pairs t, t + 128, ...; with fewer than 128 pairs the threads form G = 128 / (P L) row
+    // groups instead, group g of a pair adding the rows g, g + G, ... of every chunk, and the groups are added in order at the end
+    const int npair = P * L;
+    const int G = npair >= TILE ? 1 : TILE / npair;
+    const int grp = G > 1 ? t / npair : 0, t0 = G > 1 ? t - grp * npair : t;
+    const bool active = grp < G;  // (G > 1: the last 128 - G P L threads only help to load)
+    double s0[8], s1[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s0[k] = s1[k] = 0.0;
+    for (int c = 0; c < TILE / LMC_CHUNK; ++c) {
+        const int64_t r0 = n0 + (int64_t)c * LMC_CHUNK;
+        __syncthreads();  // the previous chunk has been read
+        for (int i = t; i < LMC_CHUNK * P; i += TILE) {  // rows of g0_f, g1_f [Np x P]: all exist, those >= N count as zero
+            const bool live = r0 + i / P < N;
+            c0[i] = live ? (double)g0_f[r0 * P + i] : 0.0;
+            c1[i] = live ? (double)g1_f[r0 * P + i] : 0.0;
+        }
+        for (int i = t; i < LMC_CHUNK * L; i += TILE) {  // mean_g, var_g [N x L]: rows >= N are not there
+            const bool live = r0 + i / L < N;
+            cm[i] = live ? (double)mean_g[r0 * L + i] : 0.0;
+            cv[i] = live ? (double)var_g[r0 * L + i] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int idx = t0 + k * TILE;
+            if (active && idx < npair) {
+                const int p = idx / L, l = idx - p * L;
+                double b0 = s0[k], b1 = s1[k];
+                for (int r = grp; r < LMC_CHUNK; r += G) {
+                    b0 = fma(c0[r * P + p], cm[r * L + l], b0);
+                    b1 = fma(c1[r * P + p], cv[r * L + l], b1);
+                }
+                s0[k] = b0;
+                s1[k] = b1;
+            }
+        }
+    }
+    if (G > 1) {  // (uniform over the block) one pair per thread: the groups' sums through LDS, added in group order
+        __syncthreads();  // the last chunk has been read: c0, c1 are free
+        if (active) {
+            c0[grp * npair + t0] = s0[0];
+            c1[grp * npair + t0] = s1[0];
+        }
+        __syncthreads();
+        if (t < npair) {
+            double b0 = 0.0, b1 = 0.0;
+            for (int g = 0; g < G; ++g) {
+                b0 += c0[g * npair + t];
+                b1 += c1[g * npair + t];
+            }
+            dW_partial[(int64_t)blockIdx.x * npair + t] = b0 + 2.0 * Ws[t] * b1;
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int idx = t + k * TILE;
+        if (idx < npair) dW_partial[(int64_t)blockIdx.x * npair + idx] = s0[k] + 2.0 * Ws[idx] * s1[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // diag_site_step_kernel: the per-datum site update of t_SVGP_sites (reference src/models/tsvgp_sites.py:113-145) fused with
 // the likelihood-gradient map of lik_map_kernel (same device functions, same two-threads-per-row quadrature split, g1 never
 // cropped).  Per row and latent, in place on the fp64 site state [Np x P]:
@@ -5210,6 +5379,41 @@ int lik_map_ordinal(const T* mean, const T* var, const T* Y, int64_t in_stride, 
     return launch_status();
 }
 
+static bool lmc_shape_ok(int64_t N, int64_t Np, int L, int P) {
+    if (N <= 0 || Np < N || Np - N >= TILE || (Np % TILE) || Np / TILE > 0x7fffffff) return false;
+    return L >= 1 && L <= TSVGP_MAX_BATCH && P >= 1 && P <= TSVGP_MAX_BATCH;
+}
+
+template <typename T>
+int lmc_mix(const T* mean_g, const T* var_g, const double* W, T* Fmu, T* Fvar, int32_t* nonpos_partial, int64_t N, int64_t Np, int L,
+            int P, void* stream) {
+    if (!mean_g || !var_g || !W || !Fmu || !Fvar || !lmc_shape_ok(N, Np, L, P)) return TSVGP_EINVAL;
+    const dim3 grid((unsigned)(Np / TILE)), block(TILE);
+    if (P <= 8)
+        hipLaunchKernelGGL((lmc_mix_kernel<T, 8>), grid, block, 0, (hipStream_t)stream, mean_g, var_g, W, Fmu, Fvar, nonpos_partial, N,
+                           L, P);
+    else
+        hipLaunchKernelGGL((lmc_mix_kernel<T, TSVGP_MAX_BATCH>), grid, block, 0, (hipStream_t)stream, mean_g, var_g, W, Fmu, Fvar,
+                           nonpos_partial, N, L, P);
+    return launch_status();
+}
+
+template <typename T>
+int lmc_unmix(const T* g0_f, const T* g1_f, const double* W, int flags, T* g0_g, T* g1_g, const T* mean_g, const T* var_g,
+              double* dW_partial, int64_t N, int64_t Np, int L, int P, void* stream) {
+    if (!g0_f || !g1_f || !W || !g0_g || !g1_g || !lmc_shape_ok(N, Np, L, P)) return TSVGP_EINVAL;
+    if (flags & ~TSVGP_LIK_NOCROP) return TSVGP_EINVAL;
+    if (dW_partial && (!mean_g || !var_g)) return TSVGP_EINVAL;
+    const dim3 grid((unsigned)(Np / TILE)), block(TILE);
+    if (L <= 8)
+        hipLaunchKernelGGL((lmc_unmix_kernel<T, 8>), grid, block, 0, (hipStream_t)stream, g0_f, g1_f, W, flags, g0_g, g1_g, mean_g,
+                           var_g, dW_partial, N, L, P);
+    else
+        hipLaunchKernelGGL((lmc_unmix_kernel<T, TSVGP_MAX_BATCH>), grid, block, 0, (hipStream_t)stream, g0_f, g1_f, W, flags, g0_g,
+                           g1_g, mean_g, var_g, dW_partial, N, L, P);
+    return launch_status();
+}
+
 template <typename T>
 int lik_map_softmax(const T* mean, const T* var, const T* Y, int flags, int C, int S, const int64_t* rng_state, int64_t row_offset,
                     const T* epsilon, T* g0, T* g1, double* ve_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
@@ -6378,6 +6582,24 @@ int tsvgp_lik_map_ordinal_f32(const float* mean, const float* var, const float* 
                               double* dparam_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, void* stream) {
     return lik_map_ordinal<float>(mean, var, Y, in_stride, flags, edges, n_edges, sigma, g0, g1, out_stride, ve_partial,
                                   dparam_partial, nonpos_partial, N, Np, stream);
+}
+int tsvgp_lmc_mix_f64(const double* mean_g, const double* var_g, const double* W, double* Fmu, double* Fvar, int32_t* nonpos_partial,
+                      int64_t N, int64_t Np, int L, int P, void* stream) {
+    return lmc_mix<double>(mean_g, var_g, W, Fmu, Fvar, nonpos_partial, N, Np, L, P, stream);
+}
+int tsvgp_lmc_mix_f32(const float* mean_g, const float* var_g, const double* W, float* Fmu, float* Fvar, int32_t* nonpos_partial,
+                      int64_t N, int64_t Np, int L, int P, void* stream) {
+    return lmc_mix<float>(mean_g, var_g, W, Fmu, Fvar, nonpos_partial, N, Np, L, P, stream);
+}
+int tsvgp_lmc_unmix_f64(const double* g0_f, const double* g1_f, const double* W, int flags, double* g0_g, double* g1_g,
+                        const double* mean_g, const double* var_g, double* dW_partial, int64_t N, int64_t Np, int L, int P,
+                        void* stream) {
+    return lmc_unmix<double>(g0_f, g1_f, W, flags, g0_g, g1_g, mean_g, var_g, dW_partial, N, Np, L, P, stream);
+}
+int tsvgp_lmc_unmix_f32(const float* g0_f, const float* g1_f, const double* W, int flags, float* g0_g, float* g1_g,
+                        const float* mean_g, const float* var_g, double* dW_partial, int64_t N, int64_t Np, int L, int P,
+                        void* stream) {
+    return lmc_unmix<float>(g0_f, g1_f, W, flags, g0_g, g1_g, mean_g, var_g, dW_partial, N, Np, L, P, stream);
 }
 int tsvgp_lik_map_scalar_f32(const float* mean, const float* var, const float* Y, int64_t in_stride, int lik, double param0,
                              double param1, float* g0, float* g1, int64_t out_stride, double* ve_partial, double* dparam_partial,

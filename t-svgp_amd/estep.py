@@ -21,7 +21,11 @@ on them, then the site sums of the route -- ``run`` with P = latent_dim on one k
 two-sweep form on the one-pass-per-latent path (``_run_separate_coupled``).  The scalar likelihoods that have no arm in the moments
 kernels (``LIK_STUDENT_T``, ``LIK_POISSON``, ``LIK_GAMMA``, ``LIK_ORDINAL``; Y [N x P], one column per latent) take the same passes.  Every map from
 (mean, var, Y) to (g0, g1, ve, nonpos) that runs as a launch of its own, the Gaussian / Bernoulli one of the stored-tile and
-two-product passes included, goes through ``EStepEngine.lik_map``.  The two other N-sized launches of a pass have one entry each
+two-product passes included, goes through ``EStepEngine.lik_map``.
+Under ``LinearCoregionalization`` (P outputs mixed from the L latents of separate kernels by W [P, L], Y [N, P]) any such likelihood
+takes the mapped passes with ``_mixed_map`` for the map: ``lmc_mix`` (latent moments -> mixed), ``lik_map`` on the outputs,
+``lmc_unmix`` (the gradients back onto the latents), and the site sums over the L latents.
+The two other N-sized launches of a pass have one entry each
 as well, for the shared operand [Np, Mp] and the per-latent one [P, Np, Mp] alike: ``EStepEngine.moments`` (``_moments_then_map`` is
 the mapped pass's pair of it and ``lik_map``) and ``EStepEngine._site_sums``.
 """
@@ -37,7 +41,7 @@ import torch
 
 from . import _backend as B
 from .distributed import world_size
-from .kernels import SeparateIndependent
+from .kernels import LinearCoregionalization, SeparateIndependent
 from .side_branch import SideBranch, SideStream
 
 MAX_INPUT_DIM = 32  # the fill kernel pads D to a compile-time size (1, 2, 4, 8, 16, 32)
@@ -60,6 +64,12 @@ class EStepStats:
     tile: Optional[torch.Tensor] = None  # [Np, Mp] the stored triangular product t_n = Tm k_n (run(keep_tile=True))
     dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d (likelihood parameter) over the rows (LIK_STUDENT_T: scale,
     # LIK_GAMMA: shape, LIK_ORDINAL: sigma)
+    # LinearCoregionalization (mean, var, g0, g1, acc2, acc1 above are the L latents'): the P mixed outputs' counterparts
+    fmu: Optional[torch.Tensor] = None  # [N, P] mixed mean
+    fvar: Optional[torch.Tensor] = None  # [N, P] mixed variance
+    g0_f: Optional[torch.Tensor] = None  # [N, P] d ve / d fmu
+    g1_f: Optional[torch.Tensor] = None  # [N, P] d ve / d fvar, never cropped
+    dW: Optional[torch.Tensor] = None  # [P, L] sum of d ve / d W over the rows (a pass with LIK_NOCROP)
 
 
 @dataclass
@@ -71,6 +81,12 @@ class LikMapResult:
     ve_partial: torch.Tensor  # fp64 sums of ve per 128 rows: [Np / 128], or [P, Np / 128] from the per-column scalar map
     nonpos_partial: torch.Tensor  # int32 counts of rows with var <= 0, the same shape
     dparam: Optional[torch.Tensor] = None  # scalar: sum of d ve / d parameter over the rows (StudentT, Gamma, Ordinal)
+    # ``_mixed_map`` (g0, g1 above are then the L latents'): the mixed moments and the map's own gradients [Np, P], the sum of d ve / d W
+    fmu: Optional[torch.Tensor] = None
+    fvar: Optional[torch.Tensor] = None
+    g0_f: Optional[torch.Tensor] = None
+    g1_f: Optional[torch.Tensor] = None
+    dW: Optional[torch.Tensor] = None
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -639,6 +655,78 @@ class EStepEngine:
                 raise ValueError(f"lik_map: no likelihood map for lik_id {lik_id}")
         return res
 
+    def lmc_mix(self, mean_g, var_g, W, N, Np, *, Fmu=None, Fvar=None, count=True):
+        """``tsvgp_lmc_mix_*``: latent moments (mean_g, var_g) [N, L], contiguous and of one dtype (it picks the kernel), and W
+        [P, L] fp64 on the device -> (Fmu, Fvar [N, P], nonpos_partial [Np / 128] int32 or None without ``count``).  Outputs the
+        caller does not hand in are cached buffers ("lmc_fmu", "lmc_fvar", "lmc_nonpos_partial")."""
+        T, L, P = mean_g.dtype, mean_g.shape[1], W.shape[0]
+        if tuple(mean_g.shape) != (N, L) or tuple(var_g.shape) != (N, L) or tuple(W.shape) != (P, L) or W.dtype != torch.float64:
+            raise ValueError(f"lmc_mix: mean_g, var_g [N, L] and W [P, L] fp64, got {tuple(mean_g.shape)}, {tuple(var_g.shape)}, "
+                             f"{tuple(W.shape)} {W.dtype}")
+        if not (mean_g.is_contiguous() and var_g.is_contiguous() and W.is_contiguous()) or var_g.dtype != T:
+            raise ValueError("lmc_mix reads contiguous arrays of one dtype")
+        Fmu = self._get("lmc_fmu", (N, P), T) if Fmu is None else Fmu
+        Fvar = self._get("lmc_fvar", (N, P), T) if Fvar is None else Fvar
+        bad = self._get("lmc_nonpos_partial", (Np // B.TILE,), torch.int32) if count else None
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_lmc_mix", lambda: self._fn("tsvgp_lmc_mix", T)(
+                mean_g.data_ptr(), var_g.data_ptr(), W.data_ptr(), Fmu.data_ptr(), Fvar.data_ptr(), _ptr(bad), N, Np, L, P,
+                self._stream()))
+        return Fmu, Fvar, bad
+
+    def lmc_unmix(self, g0_f, g1_f, W, N, Np, *, nocrop=False, mean_g=None, var_g=None, g0_g=None, g1_g=None):
+        """``tsvgp_lmc_unmix_*``: the map's gradients (g0_f, g1_f) [Np, P] and W [P, L] -> (g0_g, g1_g [Np, L] with zero padding
+        rows, g1_g cropped at -1e-8 unless ``nocrop``; dW [P, L] fp64 or None).  With the latent moments (mean_g, var_g) [N, L]
+        given, dW = sum_n d ve_n / d W: the per-block sums of the launch, added over the blocks here.  Outputs the caller does not
+        hand in are the cached "coupled_g0" / "coupled_g1" the site sums of a mapped pass read."""
+        T, P, L = g0_f.dtype, W.shape[0], W.shape[1]
+        if tuple(g0_f.shape) != (Np, P) or tuple(g1_f.shape) != (Np, P) or W.dtype != torch.float64 or g1_f.dtype != T:
+            raise ValueError(f"lmc_unmix: g0_f, g1_f [Np, P] = [{Np}, {P}] of one dtype and W fp64, got {tuple(g0_f.shape)}, "
+                             f"{tuple(g1_f.shape)}")
+        want_dW = mean_g is not None
+        if want_dW and (var_g is None or tuple(mean_g.shape) != (N, L) or tuple(var_g.shape) != (N, L) or mean_g.dtype != T
+                        or var_g.dtype != T or not (mean_g.is_contiguous() and var_g.is_contiguous())):
+            raise ValueError(f"lmc_unmix: dW needs mean_g and var_g [N, L] = [{N}, {L}], contiguous, in the gradients' dtype")
+        if not (g0_f.is_contiguous() and g1_f.is_contiguous() and W.is_contiguous()):
+            raise ValueError("lmc_unmix reads contiguous arrays")
+        g0_g = self._get("coupled_g0", (Np, L), T) if g0_g is None else g0_g
+        g1_g = self._get("coupled_g1", (Np, L), T) if g1_g is None else g1_g
+        part = self._get("lmc_dW_partial", (Np // B.TILE, P, L), torch.float64) if want_dW else None
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_lmc_unmix", lambda: self._fn("tsvgp_lmc_unmix", T)(
+                g0_f.data_ptr(), g1_f.data_ptr(), W.data_ptr(), B.LIK_NOCROP if nocrop else 0, g0_g.data_ptr(), g1_g.data_ptr(),
+                _ptr(mean_g if want_dW else None), _ptr(var_g if want_dW else None), _ptr(part), N, Np, L, P, self._stream()))
+        return g0_g, g1_g, (part.sum(dim=0) if want_dW else None)
+
+    def _mixed_map(self, mean_g, var_g, Y, W, lik_id, lik_param, N, Np) -> LikMapResult:
+        """The map of a pass under ``LinearCoregionalization``: ``lmc_mix`` of the L latents' moments, ``lik_map`` of a
+        one-latent-per-column likelihood on the P mixed outputs (never cropped: the crop of tsvgp.py:262-263 is the latents'),
+        ``lmc_unmix`` back.  The result's g0, g1 [Np, L] are what the site sums read; its nonpos_partial counts the rows the map
+        rejected and those with a bad latent moment (a row may be in both: the sum is only compared with zero).  A pass with
+        LIK_NOCROP -- the M-step's -- also returns dW."""
+        lik = lik_id & 0xFF
+        if lik in B.COUPLED_LIKS:
+            raise ValueError("LinearCoregionalization takes a likelihood with one latent per output column, not a coupled one")
+        nocrop = bool(lik_id & B.LIK_NOCROP)
+        P, T = W.shape[0], mean_g.dtype
+        Fmu, Fvar, bad = self.lmc_mix(mean_g, var_g, W, N, Np)
+        f = self.lik_map(Fmu, Fvar, Y, lik | B.LIK_NOCROP, lik_param, N, Np, g0=self._get("lmc_g0f", (Np, P), T),
+                         g1=self._get("lmc_g1f", (Np, P), T))
+        g0, g1, dW = self.lmc_unmix(f.g0, f.g1, W, N, Np, nocrop=nocrop, mean_g=mean_g if nocrop else None,
+                                    var_g=var_g if nocrop else None)
+        return LikMapResult(g0, g1, f.ve_partial, torch.cat([f.nonpos_partial.reshape(-1), bad]), dparam=f.dparam, fmu=Fmu,
+                            fvar=Fvar, g0_f=f.g0, g1_f=f.g1, dW=dW)
+
+    def _mixed_stats(self, stats, lm, N, want_moments, want_grads):
+        """The mixed outputs' entries of ``EStepStats`` from what ``_mixed_map`` left in cached buffers: fp64 copies."""
+        if lm is None or lm.fmu is None:
+            return
+        stats.dW = lm.dW
+        if want_moments:
+            stats.fmu, stats.fvar = lm.fmu.to(torch.float64, copy=True), lm.fvar.to(torch.float64, copy=True)
+        if want_grads:
+            stats.g0_f, stats.g1_f = lm.g0_f[:N].to(torch.float64, copy=True), lm.g1_f[:N].to(torch.float64, copy=True)
+
     @staticmethod
     def _fused_param(lik_id, lik_param) -> float:
         """The parameter of a likelihood fused into the moments kernel.  A pass with no likelihood (predictions) ignores
@@ -669,22 +757,31 @@ class EStepEngine:
                 self._stream()))
         return ve_partial, nonpos_partial
 
-    def _moments_then_map(self, A, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only=False):
+    def _moments_then_map(self, A, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only=False, mix=None):
         """The pass of a likelihood whose map runs behind the moments (``B.MAPPED_LIKS``): the moments of every latent with no
-        likelihood into the cached "coupled_mean" / "coupled_var" [N, P] (they stay on this stream), then ``lik_map`` on them.
+        likelihood into the cached "coupled_mean" / "coupled_var" [N, P] (they stay on this stream), then ``lik_map`` on them --
+        or, with ``mix`` (W [outputs, P] of a ``LinearCoregionalization``), ``_mixed_map``.
         Returns (mean, var, LikMapResult)."""
         if mean_only:
             raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
         P = gam.shape[1]
         mean, var = self._get("coupled_mean", (N, P), self.dtype), self._get("coupled_var", (N, P), self.dtype)
         self.moments(A, Tm, gam, kdiag, N, moment_mode, mean=mean, var=var)
+        if mix is not None:
+            return mean, var, self._mixed_map(mean, var, Y, mix, lik_id, lik_param, N, Np)
         return mean, var, self.lik_map(mean, var, Y, lik_id, lik_param, N, Np)
 
     @staticmethod
-    def _check_y(Y, N, P, lik_id, lik_param=None):
+    def _check_y(Y, N, P, lik_id, lik_param=None, outputs=None):
         """Y [N, P]; a coupled likelihood (LIK_HETERO: two latents, LIK_SOFTMAX, LIK_MULTICLASS: C) maps its latents onto ONE target column:
-        Y [N, 1], P = latent_dim."""
+        Y [N, 1], P = latent_dim.  ``outputs`` (the rows of W under ``LinearCoregionalization``): Y [N, outputs], no coupled likelihood."""
         lik = lik_id & 0xFF
+        if outputs is not None:
+            if lik in B.COUPLED_LIKS:
+                raise ValueError("LinearCoregionalization takes a likelihood with one latent per output column, not a coupled one")
+            if Y is None or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != outputs:
+                raise ValueError(f"Y must be [N, P] = [{N}, {outputs}] (P: the rows of W), got {None if Y is None else tuple(Y.shape)}")
+            return
         if lik in B.COUPLED_LIKS:
             name = {B.LIK_HETERO: "heteroskedastic", B.LIK_SOFTMAX: "Softmax", B.LIK_MULTICLASS: "MultiClass"}[lik]
             C = 2 if lik == B.LIK_HETERO else getattr(lik_param, "latent_dim", None)  # (hetero passes lik_param = 0.0)
@@ -915,7 +1012,7 @@ class EStepEngine:
         return KfuP
 
     def _run_batched(self, X, Y, Z, kernel, whitened, *, moment_Tm, moment_mode, gamma, lik_id, lik_param, whiten_T,
-                     sites, want_moments, want_grads, mean_only, prefill=None) -> EStepStats:
+                     sites, want_moments, want_grads, mean_only, prefill=None, mix=None) -> EStepStats:
         """One pass for P latents with one kernel each as batched launches: fill [P, Np, Mp] -> in-place whitening of the
         latents that ask for it -> moments -> site sums (4 launches; BASELINE configs[4])."""
         T, dev = self.dtype, self.device
@@ -924,7 +1021,8 @@ class EStepEngine:
         N, M, P = X.shape[0], Z.shape[0], moment_Tm.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         need_g = lik_id != B.LIK_NONE
-        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS  # the map runs behind the moments: coupled latents or a scalar map
+        # the map runs behind the moments: coupled latents, a scalar map, or any likelihood on mixed outputs
+        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS or (need_g and mix is not None)
         if need_g:
             Y = Y.to(device=dev, dtype=T).contiguous()
         self._b_tag = None
@@ -960,7 +1058,7 @@ class EStepEngine:
         kdiag = [k.variance.item() for k in kernel.kernels]
         lm = None
         if mapped:
-            mean, var, lm = self._moments_then_map(KfuP, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only)
+            mean, var, lm = self._moments_then_map(KfuP, Tm, gam, kdiag, Y, lik_id, lik_param, N, Np, moment_mode, mean_only, mix)
             g0, g1, ve_partial, nonpos_partial = lm.g0, lm.g1, lm.ve_partial, lm.nonpos_partial  # what the common tail reads
         else:
             g0 = self._get("g0", (Np, P), T) if need_g else None
@@ -976,6 +1074,7 @@ class EStepEngine:
             stats.var = None if var is None else var.to(torch.float64, copy=mapped)
         if want_grads and need_g:
             stats.g0, stats.g1 = g0[:N].to(torch.float64), g1[:N].to(torch.float64)
+        self._mixed_stats(stats, lm, N, want_moments, want_grads)
         if sites:
             stats.acc2, stats.acc1 = self._site_sums(KfuP, g0, g1, P, M)
         self.last_batched = True
@@ -991,9 +1090,15 @@ class EStepEngine:
         if len(kernel.kernels) != P:
             raise ValueError(f"{len(kernel.kernels)} kernels for {P} latent GPs")
         lik_id = kw.get("lik_id", B.LIK_NONE)
-        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS  # the map runs behind the moments: coupled latents or a scalar map
+        # P outputs mixed from these latents (LinearCoregionalization): W [outputs, P] on the device when there is a likelihood
+        # to apply to the mixed moments; a pass without one returns the latents' moments as under SeparateIndependent
+        mix = kernel.device_W(self.device) if (isinstance(kernel, LinearCoregionalization) and lik_id != B.LIK_NONE) else None
+        if mix is not None:
+            kw["mean_only"] = False  # the mixed map takes (Fmu, Fvar) whatever the likelihood reads of them
+        # the map runs behind the moments: coupled latents, a scalar map, or any likelihood on mixed outputs
+        mapped = (lik_id & 0xFF) in B.MAPPED_LIKS or mix is not None
         if mapped or Y is not None:
-            self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"))
+            self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"), outputs=None if mix is None else mix.shape[0])
         if X.shape[0] > 0:
             if prefill is not None and prefill.name == "KfuP":  # the batched fill is already under way (start_fill)
                 whitened = [p for p in range(P) if self._per_latent(whiten_T, p) is not None]
@@ -1006,15 +1111,15 @@ class EStepEngine:
                                          gamma=gamma, lik_id=kw.get("lik_id", B.LIK_NONE), lik_param=kw.get("lik_param", 0.0),
                                          whiten_T=whiten_T, sites=kw.get("sites", False),
                                          want_moments=kw.get("want_moments", False), want_grads=want_grads,
-                                         mean_only=kw.get("mean_only", False), prefill=prefill)
+                                         mean_only=kw.get("mean_only", False), prefill=prefill, mix=mix)
         self.last_batched = False
         if mapped and X.shape[0] > 0:  # (an empty shard contributes zeros through the loop below)
             return self._run_separate_coupled(X, Y, Z, kernel, moment_Tm=moment_Tm, gamma=gamma, whiten_T=whiten_T,
-                                              project_T=project_T, want_grads=want_grads, **kw)
+                                              project_T=project_T, want_grads=want_grads, mix=mix, **kw)
         parts = []
         for p, kp in enumerate(kernel.kernels):
             # (per-latent routes: None = this latent works on K_fu directly)
-            st = self.run(X, None if Y is None else Y[:, p:p + 1], Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1],
+            st = self.run(X, None if (Y is None or mix is not None) else Y[:, p:p + 1], Z, kp, moment_Tm=moment_Tm[p:p + 1], gamma=gamma[:, p:p + 1],
                           whiten_T=per_latent(whiten_T, p), project_T=per_latent(project_T, p), want_grads=want_grads, **kw)
             if want_grads and st.g0 is not None:
                 st.g0, st.g1 = st.g0.clone(), st.g1.clone()  # views of a buffer the next latent overwrites
@@ -1030,7 +1135,7 @@ class EStepEngine:
         return out
 
     def _run_separate_coupled(self, X, Y, Z, kernel, *, moment_Tm, gamma, whiten_T, project_T, want_grads, lik_id, sites=False,
-                              want_moments=False, mean_only=False, **kw) -> EStepStats:
+                              want_moments=False, mean_only=False, mix=None, **kw) -> EStepStats:
         """The one-pass-per-latent path under a likelihood whose map runs behind the moments (``B.MAPPED_LIKS``): a coupled map
         needs the moments of ALL latents before any site sum, and this path has one K(X, Z) buffer.  Sweep 1: fill (and whitening)
         + moments with no likelihood, per latent; the map over [N, P] (``lik_map``); sweep 2 (``sites`` only): fill (and whitening / projection)
@@ -1052,13 +1157,17 @@ class EStepEngine:
             mean[:, p] = st.mean[:, 0]
             var[:, p] = st.var[:, 0]
         Yc = Y.to(device=dev, dtype=T).contiguous()
-        lm = self.lik_map(mean, var, Yc, lik_id, lik_param, N, Np)
+        if mix is not None:  # P outputs mixed from the latents: mix, map, un-mix
+            lm = self._mixed_map(mean, var, Yc, mix, lik_id, lik_param, N, Np)
+        else:
+            lm = self.lik_map(mean, var, Yc, lik_id, lik_param, N, Np)
         g0, g1 = lm.g0, lm.g1
         out = EStepStats(n_rows=N, ve_sum=lm.ve_partial.sum(), nonpos=lm.nonpos_partial.sum().to(torch.float64), dparam=lm.dparam)
         if want_moments:
             out.mean, out.var = mean.to(torch.float64, copy=True), var.to(torch.float64, copy=True)
         if want_grads:
             out.g0, out.g1 = g0[:N].to(torch.float64, copy=True), g1[:N].to(torch.float64, copy=True)
+        self._mixed_stats(out, lm, N, want_moments, want_grads)
         if sites:
             acc2, acc1 = [], []
             for p, kp in enumerate(kernel.kernels):

@@ -104,6 +104,51 @@ class SeparateIndependent:
         return torch.stack([k.K_diag(X) for k in self.kernels], dim=1)  # [N, P]
 
 
+class LinearCoregionalization(SeparateIndependent):
+    """``gpflow.kernels.LinearCoregionalization(kernels, W)`` [ext]: P outputs f = W g mixed from L independent latent GPs g_l,
+    one kernel each, W [P, L].  The sites, K_uu [L, M, M] and every N M^2-sized launch belong to the L latents exactly as under
+    ``SeparateIndependent``; the mixing runs per row between the moments and the likelihood map (``tsvgp_lmc_mix_*``) and the
+    chain rule back between the map and the site sums (``tsvgp_lmc_unmix_*``).  The likelihood sees Y [N, P]."""
+
+    MAX_DIM = 32  # TSVGP_MAX_BATCH: the two kernels stage W [P, L] into LDS
+
+    def __init__(self, kernels, W, name=None):
+        super().__init__(kernels, name=name or "linear_coregionalization")
+        self.W = W if isinstance(W, Parameter) else Parameter(W)
+        self._check_w(self.W.value)
+
+    def _check_w(self, W: torch.Tensor):
+        L = len(self.kernels)
+        if W.dim() != 2 or W.shape[1] != L:
+            raise ValueError(f"W must be [P, L] = [P, {L}] (one column per latent kernel), got {tuple(W.shape)}")
+        if not (1 <= W.shape[0] <= self.MAX_DIM and L <= self.MAX_DIM):
+            raise ValueError(f"LinearCoregionalization takes at most {self.MAX_DIM} outputs and {self.MAX_DIM} latent GPs, got "
+                             f"P = {W.shape[0]}, L = {L}")
+        if not bool(torch.isfinite(W).all()):
+            raise ValueError("W must be finite")
+
+    @property
+    def num_outputs(self) -> int:
+        return int(self.W.value.shape[0])
+
+    def device_W(self, device) -> torch.Tensor:
+        """W [P, L] fp64, contiguous, on ``device``: what the two kernels read.  Cached per parameter stamp (checked again when
+        the value changed)."""
+        key = (self.W.stamp(), str(device))
+        hit = self.__dict__.get("_w_cache")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        self._check_w(self.W.value)
+        out = self.W.value.detach().to(device=device, dtype=torch.float64).clone(memory_format=torch.contiguous_format)
+        self.__dict__["_w_cache"] = (key, out)
+        return out
+
+    def K_diag(self, X) -> torch.Tensor:
+        """The mixed prior variances [N, P]: sum_l W[p, l]^2 k_l(x, x)."""
+        W = self.W.value.to(torch.float64)
+        return super().K_diag(X).to(torch.float64) @ (W * W).t()
+
+
 def latent_kernels(kernel, P: int):
     """The list of per-latent kernels behind ``kernel``: P references to one shared kernel, or the separate ones."""
     if isinstance(kernel, SeparateIndependent):

@@ -41,7 +41,7 @@ from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import EStepStats, per_latent
 from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
-from ..kernels import SeparateIndependent, latent_kernels
+from ..kernels import LinearCoregionalization, SeparateIndependent, latent_kernels
 from ..likelihoods import mapped_parameter
 from ..sites import DenseSites
 from ..util import (
@@ -149,6 +149,16 @@ class base_SVGP(abc.ABC):
         """Returns the mean and cholesky factor of the covariance matrix of q(u)"""
         raise NotImplementedError
 
+    # -- P outputs mixed from the latents -------------------------------------------------------------------------
+    def _lmc(self):
+        """The kernel when it is a ``LinearCoregionalization`` (P outputs f = W g of the L latent GPs), else None."""
+        return self.kernel if isinstance(self.kernel, LinearCoregionalization) else None
+
+    def _refuse_lmc(self, what: str):
+        if self._lmc() is not None:
+            raise NotImplementedError(f"{what} is not implemented for LinearCoregionalization: the mixed outputs have marginal "
+                                      "predictions (predict_f, full_output_cov, predict_y, predict_log_density) only")
+
     # -- joint predictions -------------------------------------------------------------------------------------
     _BOTH_COV = "full_cov and full_output_cov together (the [N, P, N, P] covariance) are not implemented"
 
@@ -188,6 +198,7 @@ class base_SVGP(abc.ABC):
         generator (the hook ``Softmax`` offers) and leaves the counter alone.  Both covariance flags together are not defined."""
         if full_cov and full_output_cov:
             raise NotImplementedError(self._BOTH_COV)
+        self._refuse_lmc("predict_f_samples")
         eng = self._sample_engine() if full_cov else self._get_engine()  # (the marginal form needs the generator alone)
         S = 1 if num_samples is None else int(num_samples)
         P = int(self.num_latent_gps)
@@ -231,6 +242,7 @@ class base_SVGP(abc.ABC):
         ``draw=None`` uses, and then advances, a counter of this model that starts at 0 -- its own, not ``predict_f_samples``'."""
         from ..pathwise import sample_functions
 
+        self._refuse_lmc("sample_functions")
         eng = self._sample_engine()
         P = int(self.num_latent_gps)
         if not (1 <= P <= B.MAX_BATCH):
@@ -272,6 +284,7 @@ class base_SVGP(abc.ABC):
         the route ``predict_f`` takes, one K(Xnew, Z) fill per kernel, one GEMM U = K Q_p and one ``tsvgp_moments_vjp_*`` launch
         per latent (``EStepEngine.predict_vjp``); input dimension D <= 32.  ``predict_f`` itself takes part in torch autograd
         with respect to a Xnew that requires grad, and ``predict_y`` / ``predict_log_density`` with it."""
+        self._refuse_lmc("predict_f_vjp")
         X = Xnew if isinstance(Xnew, torch.Tensor) else torch.as_tensor(np.asarray(Xnew))
         X = X.detach().to(device=self.device, dtype=torch.float64)
         P = int(self.num_latent_gps)
@@ -317,6 +330,8 @@ class base_SVGP(abc.ABC):
                 if par.trainable and id(par) not in seen:
                     seen.add(id(par))
                     out.append(par)
+        if self._lmc() is not None and self.kernel.W.trainable:
+            out.append(self.kernel.W)
         out += [par for par in vars(self.likelihood).values() if hasattr(par, "trainable") and par.trainable]
         if self.inducing_variable.Z.trainable:
             out.append(self.inducing_variable.Z)
@@ -336,6 +351,17 @@ class t_SVGP(base_SVGP):
                          num_latent_gps=num_latent_gps, num_data=num_data, compute_dtype=compute_dtype, device=device)
         self.num_inducing = self.inducing_variable.num_inducing
         self._init_variational_parameters(self.num_inducing, lambda_1, lambda_2_sqrt)
+        if self._lmc() is not None:
+            # P outputs mixed from L latents: the sites are the latents' (lambda_1 [M, L], lambda_2_sqrt [L, M, M])
+            L_ = len(self.kernel.kernels)
+            if self.num_latent_gps != L_:
+                raise ValueError(f"LinearCoregionalization has {L_} latent kernels (the columns of W): num_latent_gps must be {L_}, "
+                                 f"got {self.num_latent_gps}")
+            if self._coupled():
+                raise NotImplementedError(f"the {self._lik_name()} likelihood couples its latents and is not implemented for "
+                                          "LinearCoregionalization: use a likelihood with one latent per output column")
+            if latent_split:
+                raise NotImplementedError("latent_split is not implemented for LinearCoregionalization")
         if self._coupled() and self.num_latent_gps != self.likelihood.latent_dim:
             raise ValueError(f"the {self._lik_name()} likelihood needs num_latent_gps = {self.likelihood.latent_dim} "
                              f"(its latent_dim), got {self.num_latent_gps}")
@@ -751,6 +777,8 @@ class t_SVGP(base_SVGP):
         more than one rank Xnew is local: there is no collective."""
         if full_cov and full_output_cov:
             raise NotImplementedError(self._BOTH_COV)
+        if self._lmc() is not None:
+            return self._predict_f_mixed(Xnew, full_cov, full_output_cov)
         if full_cov:
             return self._joint(Xnew)
         Xg = None if full_output_cov else self._grad_rows(Xnew)
@@ -758,6 +786,26 @@ class t_SVGP(base_SVGP):
             return _PredictF.apply(Xg, self)
         mean, var = self._predict_marginal(self._as_device(Xnew))
         return mean, (torch.diag_embed(var) if full_output_cov else var)
+
+    def _predict_f_mixed(self, Xnew, full_cov, full_output_cov):
+        """``predict_f`` under ``LinearCoregionalization``, as GPflow's ``mix_latent_gp`` [ext]: the latents' marginals through
+        ``tsvgp_lmc_mix_f64`` -- (Fmu, Fvar) [N, P], or Fvar = W diag(var_g[n]) W^T [N, P, P] with ``full_output_cov``."""
+        if full_cov:
+            self._refuse_lmc("predict_f(full_cov=True)")
+        if self._grad_rows(Xnew) is not None:
+            self._refuse_lmc("autograd through predict_f")
+        mean_g, var_g = self._predict_marginal(self._as_device(Xnew))
+        N = mean_g.shape[0]
+        eng = self._get_engine()
+        W = self.kernel.device_W(self.device)
+        P = W.shape[0]
+        Fmu = torch.empty((N, P), dtype=torch.float64, device=self.device)
+        Fvar = torch.empty((N, P), dtype=torch.float64, device=self.device)
+        if N > 0:  # (the latents' variances were checked by the pass that made them)
+            eng.lmc_mix(mean_g.contiguous(), var_g.contiguous(), W, N, B.round_up(N), Fmu=Fmu, Fvar=Fvar, count=False)
+        if full_output_cov:
+            return Fmu, torch.einsum("pl,nl,ql->npq", W, var_g, W)
+        return Fmu, Fvar
 
     def _predict_marginal(self, Xd, want_operands=False):
         ops = self._site_operands()
@@ -785,6 +833,7 @@ class t_SVGP(base_SVGP):
         """Same moments straight from the sites: var = knn - |D k|^2 (tsvgp.py:215-232, util.py:91-185)."""
         if full_cov and full_output_cov:
             raise NotImplementedError(self._BOTH_COV)
+        self._refuse_lmc("new_predict_f")
         if isinstance(self.kernel, SeparateIndependent):
             # "todo : make broadcastable" (tsvgp.py:214): the reference form only covers one shared kernel
             raise NotImplementedError("new_predict_f is not broadcastable over separate kernels in the reference")
@@ -851,7 +900,9 @@ class t_SVGP(base_SVGP):
         "likelihood_shape" (Gamma) or "likelihood_sigma" (Ordinal): the sum of d ve / d parameter comes out of the likelihood map's
         own pass}), gradients of the ELBO
         with respect to the constrained parameter values; with one kernel per latent (``SeparateIndependent``) the kernel
-        entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales".  With more than one rank ``data`` is this
+        entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales".  With ``LinearCoregionalization`` also "W" [P, L]:
+        with the sites fixed W enters through the mix alone, d ELBO / d W[p, l] = scale sum_n (g0_f[n, p] mean_g[n, l] +
+        2 W[p, l] g1_f[n, p] var_g[n, l]), the block sums of the un-mix launch.  With more than one rank ``data`` is this
         rank's shard."""
         sep = isinstance(self.kernel, SeparateIndependent)
         X, Y = self._as_device(data[0]), self._as_device(data[1])
@@ -874,14 +925,18 @@ class t_SVGP(base_SVGP):
         # The TRUE d ve / d var here: the crop of tsvgp.py:262-263 belongs to the site update, not to the ELBO (with the
         # 1e-3 jitter of the probit link log p is not log-concave in the far tails, so some g1 are positive)
         parts = []
-        mapped = self._mapped()
+        lmc = self._lmc() is not None
+        # (mixed outputs: the same pass, whose map is mix -> likelihood -> un-mix; its g0, g1 are the LATENTS' true gradients, and
+        # it returns dW and, for the Gaussian noise gradient, the mixed moments)
+        mapped = self._mapped() or lmc
         if mapped:
             # A likelihood that couples the latents cannot ride on a per-kernel pass (and the scalar maps behind the moments do not
             # ride on the stored-tile form of one): one pass over all latents maps the
             # moments of all of them to the true g0, g1 (and the variational expectations); the per-kernel passes below then take
             # their columns as given (``site_grads``) for the site sums and the kernel-gradient contraction.
             stc = eng.run(X, Y, ops["Z"], self.kernel, moment_Tm=Dm, moment_mode=ops["moment_mode"], gamma=beta,
-                          lik_id=self.likelihood.lik_id | B.LIK_NOCROP, lik_param=self.likelihood.lik_param, want_grads=True)
+                          lik_id=self.likelihood.lik_id | B.LIK_NOCROP, lik_param=self.likelihood.lik_param, want_grads=True,
+                          want_moments=lmc and gaussian)
             Np = B.round_up(X.shape[0])
             gc0 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
             gc1 = torch.zeros((Np, P), dtype=eng.dtype, device=self.device)
@@ -920,7 +975,7 @@ class t_SVGP(base_SVGP):
                 dls[ki] += l
                 dZ += z
             sum_g1[ki] = g1.sum(dtype=torch.float64)
-            if gaussian:  # d ve / d s2 = -1/(2 s2) + ((y - m)^2 + v) / (2 s2^2), summed
+            if gaussian and not lmc:  # d ve / d s2 = -1/(2 s2) + ((y - m)^2 + v) / (2 s2^2), summed
                 res = res + torch.sum((Y[:, sl].to(st.mean.dtype) - st.mean) ** 2 + st.var)
         if sep:
             st = EStepStats(n_rows=parts[0].n_rows, ve_sum=sum(s_.ve_sum for s_ in parts),
@@ -931,14 +986,23 @@ class t_SVGP(base_SVGP):
         lik_par = mapped_parameter(self.likelihood)  # StudentT's scale, Gamma's shape, Ordinal's sigma
         if lik_par is not None:  # sum_n d ve_n / d parameter, summed over the ranks with the residual's slot (Gaussian only: free here)
             res = stc.dparam
-        extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1)])
+        n_out = P
+        dW = torch.zeros(0, dtype=torch.float64, device=self.device)
+        if lmc:
+            n_out = self.kernel.num_outputs
+            if gaussian and stc.fmu is not None:  # the noise gradient's residual on the MIXED moments, over all P outputs
+                res = torch.sum((Y.to(stc.fmu.dtype) - stc.fmu) ** 2 + stc.fvar)
+            # sum_n d ve_n / d W from the un-mix launch (an empty shard of several: zeros), summed over the ranks with the tail
+            dW = (stc.dW if stc.dW is not None else torch.zeros((n_out, P), dtype=torch.float64, device=self.device)).reshape(-1)
+        extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1), dW])
         acc2, acc1, ve_sum, nonpos, rows, tail = D_.reduce_stats(st, P, M, True, self._reduce(), eng, extra=extra)
         o = 0
         dvar, o = tail[o:o + nk], o + nk
         dls, o = tail[o:o + nk * Dn].reshape(nk, Dn), o + nk * Dn
         dZ, o = tail[o:o + M * Dn].reshape(M, Dn), o + M * Dn
         sum_g1, o = tail[o:o + nk], o + nk
-        res = tail[o]
+        res, o = tail[o], o + 1
+        dW = tail[o:o + dW.numel()]
         self._check_step(ops, nonpos)
         scale = (float(self.num_data) / rows) if self.num_data is not None else 1.0
 
@@ -998,9 +1062,11 @@ class t_SVGP(base_SVGP):
             grads[pre + "lengthscales"] = g_ls[ki] + (n_ls.sum() if len(ls_shape) == 0 else n_ls.reshape(ls_shape))
         if gaussian:
             s2 = self.likelihood.lik_param
-            grads["likelihood_variance"] = scale * (-0.5 * rows * P / s2 + 0.5 * res / (s2 * s2))
+            grads["likelihood_variance"] = scale * (-0.5 * rows * n_out / s2 + 0.5 * res / (s2 * s2))
         if lik_par is not None:
             grads[lik_par[0]] = scale * res
+        if lmc:  # W enters the ELBO through the mix alone (the sites are fixed and the KL is the latents')
+            grads["W"] = scale * dW.reshape(n_out, P)
         elbo = ve_sum * scale - kl
         return elbo, grads
 
@@ -1122,6 +1188,8 @@ class t_SVGP(base_SVGP):
         dozen GEMMs per latent -- ~20 ms of a 34 ms 8-way shard step at P = 8, M = 1024 -- so with several ranks every latent
         gets ONE owner (p mod world).  ``latent_split``: None = whenever that applies, False = never."""
         if self.latent_split is False or not isinstance(self.kernel, SeparateIndependent) or not self._reduce():
+            return False
+        if self._lmc() is not None:  # the mix needs every latent's moments on every rank: the replicated step
             return False
         if D_.world_size() < 2 and not D_.FORCE_COLLECTIVES:
             return False
@@ -1260,7 +1328,8 @@ class t_SVGP(base_SVGP):
         if self.device.type != "cuda":
             return False
         eng = self._get_engine()
-        if self.cache_whitened or eng.profile is not None or isinstance(self.kernel, SeparateIndependent):
+        lmc = self._lmc()
+        if self.cache_whitened or eng.profile is not None or (isinstance(self.kernel, SeparateIndependent) and lmc is None):
             return False
         # With several ranks the step is TWO graphs around the all-reduce of the packed accumulators: everything in
         # front of it (prelude, fill, moments, site sums, packing) and everything behind it (unpacking, epilogue, state
@@ -1273,6 +1342,11 @@ class t_SVGP(base_SVGP):
         if hasattr(self.likelihood, "graph_key"):  # Monte Carlo: sample count and row offset are baked in; (seed, draw) are not
             lik_v += self.likelihood.graph_key()
         draw0 = getattr(self.likelihood, "draw", None)
+        if lmc is not None:
+            # the mix and un-mix launches read W through the pointer of ``device_W``, a tensor made anew for every value W is
+            # given: its stamp is part of the key, and the copy is made here, in front of any capture
+            lik_v += (lmc.W.stamp(),)
+            lmc.device_W(self.device)
         key = (X.data_ptr(), Y.data_ptr(), tuple(X.shape), tuple(Y.shape), X.dtype, Y.dtype, self._kernel_versions(),
                lik_v, self.inducing_variable.Z.stamp(), float(lr), float(jitter), tuple(routes), self.num_data)
         entry = self._graphs.get(key)
@@ -1319,6 +1393,8 @@ class t_SVGP(base_SVGP):
                                      backup=(bl1, bL), buf=buf)
                     if hasattr(self.likelihood, "rng_state"):  # the map's nodes hold this tensor's address
                         entry["lik_state"] = self.likelihood.rng_state(self.device)
+                    if lmc is not None:  # ... and the mix's nodes this one
+                        entry["lmc_W"] = lmc.device_W(self.device)
                     self._graphs[key] = entry
             except RuntimeError as exc:
                 # What torch / HIP raise when an operation is not permitted under stream capture: never try this key again

@@ -42,7 +42,7 @@ import torch
 from .. import _backend as B
 from .. import distributed as D_
 from ..base import default_jitter, to_tensor
-from ..kernels import SeparateIndependent
+from ..kernels import LinearCoregionalization, SeparateIndependent
 from ..sites import DenseSites
 from ..util import cholesky_deferred, cond2_estimate, info_sum, rev_cholesky
 from .tsvgp import _PredictF, base_SVGP
@@ -76,6 +76,8 @@ class t_SVGP_white(base_SVGP):
         self._cond_cache = None
         self._direct_failed = False
         self._two_product = False  # set once Lambda_2 + 1e-9 I failed to factor: the reference's two-product variance from then on
+        if isinstance(kernel, LinearCoregionalization):
+            raise NotImplementedError("t_SVGP_white does not take LinearCoregionalization: mixed outputs are on t_SVGP only")
         if isinstance(kernel, SeparateIndependent):
             raise NotImplementedError("t_SVGP_white takes one shared kernel (util.py:52-56 asserts Kuu [M, M])")
         self.num_inducing = self.inducing_variable.num_inducing

@@ -42,7 +42,7 @@ import torch
 from .. import _backend as B
 from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import MAX_INPUT_DIM
-from ..kernels import SeparateIndependent
+from ..kernels import LinearCoregionalization, SeparateIndependent
 from ..sites import DiagSites
 
 
@@ -56,6 +56,8 @@ class t_VGP:
         x_data, y_data = data
         if mean_function is not None:
             raise ValueError("t_VGP: only the default Zero mean function is implemented")
+        if isinstance(kernel, LinearCoregionalization):
+            raise NotImplementedError("t_VGP does not take LinearCoregionalization: mixed outputs are on t_SVGP only")
         if isinstance(kernel, SeparateIndependent):
             raise ValueError("t_VGP takes one kernel: it is defined for one latent GP")
         if getattr(likelihood, "lik_id", None) in B.COUPLED_LIKS or getattr(likelihood, "latent_dim", 1) != 1:

@@ -54,6 +54,8 @@ def trainable_parameters(model) -> dict:
         for p, k in enumerate(kern.kernels):
             out[f"kernels.{p}.variance"] = (k.variance, 0.0)
             out[f"kernels.{p}.lengthscales"] = (k.lengthscales, 0.0)
+        if hasattr(kern, "W"):  # LinearCoregionalization: the mixing matrix, unconstrained
+            out["W"] = (kern.W, None)
     else:
         out = {"variance": (kern.variance, 0.0), "lengthscales": (kern.lengthscales, 0.0)}
     if getattr(model, "inducing_variable", None) is not None:  # t_VGP has none
