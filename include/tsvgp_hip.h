@@ -419,7 +419,8 @@ int tsvgp_moments_batched_f32(const float *A, int64_t strideA, const float *Tm, 
  *     B [Np x Mp]; g0,g1 contiguous [Np x P] with rows >= N equal to 0.  B, g0, g1 and work on 16-byte boundaries (operand
  *     rows and the 16 P weights of a chunk travel as 16-byte LDS-DMA pieces; TSVGP_EINVAL otherwise).
  *     The N range is cut into `nsplit` slices; partial tiles go to `work` and are summed in a fixed order (bitwise
- *     reproducible; no atomics).  work must hold tsvgp_site_accum_work_bytes_*(Mp, P, nsplit) bytes.  Any nsplit >= 1 is
+ *     reproducible; no atomics); on a diagonal tile the row-block operands are the column-block fragments already in registers
+ *     (one LDS read per fragment and k-step).  work must hold tsvgp_site_accum_work_bytes_*(Mp, P, nsplit) bytes.  Any nsplit >= 1 is
  *     valid (a slice is a whole number of chunks -- 16 rows in fp64, 32 in fp32 with P <= 8 -- so a count above Np / chunk
  *     leaves workgroups with empty slices: correct, wasted); the launch runs in rounds of tsvgp_site_accum_slots_*() equal workgroups (per latent: n_off * nsplit off-diagonal
  *     + nt * ceil(20 nsplit / 32) diagonal ones, 22 / 32 in fp32), so a count that fills whole rounds is the fast one
@@ -436,6 +437,23 @@ int tsvgp_site_accum_batched_f64(const double *B, int64_t strideB, const double 
                                  double *acc1, void *work, int64_t Np, int Mp, int P, int nsplit, void *stream);
 int tsvgp_site_accum_batched_f32(const float *B, int64_t strideB, const float *g0, const float *g1, double *acc2,
                                  double *acc1, void *work, int64_t Np, int Mp, int P, int nsplit, void *stream);
+/* (5c) The constant-weight form of (5) and (5b): g1[n, p] = g1_const[p] on every row n < N (a homoskedastic Gaussian
+ *     likelihood: -1 / (2 s2)).  g1_const: P doubles in DEVICE memory (8-byte boundary), in both precisions.  The kernels sum
+ *     B[n,i] * B[n,j] unweighted -- no weight is moved, read back or multiplied into the operand -- and the reduction multiplies
+ *     each summed element of acc2 by g1_const[p] once, in fp64, before it writes it and its mirror image:
+ *        acc2[p][i][j] = g1_const[p] * sum_n B[n,i] * B[n,j]
+ *     so the rows >= N of B must be zero (they are: the producers zero-fill the padding) and no weight array marks them.
+ *     acc1, g0, work, nsplit, the slices and the fixed summation order are those of (5): acc1 is bit-identical to (5)'s, acc2
+ *     equals (5)'s with g1 = g1_const on every row up to the rounding of the products (bit for bit when they are exact).
+ *     1 <= P <= 8 (the hand-laid kernels; TSVGP_EINVAL above: callers with more latents use the general form). */
+int tsvgp_site_accum_cw_f64(const double *B, const double *g0, const double *g1_const, double *acc2, double *acc1, void *work,
+                            int64_t Np, int Mp, int P, int nsplit, void *stream);
+int tsvgp_site_accum_cw_f32(const float *B, const float *g0, const double *g1_const, double *acc2, double *acc1, void *work,
+                            int64_t Np, int Mp, int P, int nsplit, void *stream);
+int tsvgp_site_accum_cw_batched_f64(const double *B, int64_t strideB, const double *g0, const double *g1_const, double *acc2,
+                                    double *acc1, void *work, int64_t Np, int Mp, int P, int nsplit, void *stream);
+int tsvgp_site_accum_cw_batched_f32(const float *B, int64_t strideB, const float *g0, const double *g1_const, double *acc2,
+                                    double *acc1, void *work, int64_t Np, int Mp, int P, int nsplit, void *stream);
 
 /* (6) Batched lower Cholesky of the M x M site matrices, in place:  A[b] = L[b] L[b]^T, L written to the lower triangle
  *     of the 128x128 diagonal blocks and below (the strictly upper part of the diagonal blocks is zeroed; blocks above

@@ -14,6 +14,8 @@
 //                       map in one sweep of the operand.  HBM bound.
 //   syrk_kernel         weighted Gram  sum_n g1[n] a_n a_n^T  over an N-slice per workgroup (lower tiles only) + the
 //                       first-order sum on diagonal tiles.  MFMA bound.  Partial tiles -> syrk_reduce_kernel (fixed order).
+//                       (P <= 8: syrk1_kernel / syrk1f_kernel, and their constant-weight forms syrk1_kernel_cw /
+//                       syrk1f_kernel_cw for g1 = one number per latent, scaled once in syrk_reduce_kernel.)
 //   potrf_diag_kernel, chol_tile_kernel, trtri_level_kernel   blocked Cholesky of the M x M site matrices and the
 //                       inverse factor (latency bound; sub-blocked diagonal block, wave-tile products without LDS).
 //   kgrad_kernel        kernel-parameter gradient contraction of the M-step.  HBM bound.
@@ -2539,7 +2541,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // syrk_kernel costs 0.71 of an off-diagonal one (23/32), not 9/16.  The split of the diagonal tiles follows the two kernels
 // of round 3, which serve P <= 8:
 #define TSVGP_SYRK_DIAG_DEN 32
-#define TSVGP_SYRK1_DIAG_NUM 20   // syrk1_kernel (fp64): 19/32 .. 23/32 measured within 1 % of each other; 20/32 best
+#define TSVGP_SYRK1_DIAG_NUM 20   // syrk1_kernel (fp64): 19/32 .. 23/32 measured within 1 % of each other; 20/32 best (measured
+                                  // before the diagonal tiles took their A side from the T-side registers; not re-measured since)
 #define TSVGP_SYRK1F_DIAG_NUM 22  // syrk1f_kernel (fp32)
 // (esize: sizeof of the N-sized arrays' type: syrk1_kernel's ratio for fp64, syrk1f_kernel's for fp32)
 __host__ __device__ inline int syrk_ns_diag(int ns_off, int esize) {
@@ -2701,11 +2704,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void syrk_kernel(SyrkArgs<T> a) {
 //     k-step 2: MFMAs on set X | reads of k-step 3 -> set Y
 //     s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier
 //     k-step 3: MFMAs on set Y | LDS-DMA of chunk c + 2 into this chunk's buffer, its weights, reads of (c + 1, 0) -> set X
+// Diagonal tiles read each fragment once: both operand sides come from the one image, the A fragment of row block w is the LDS
+// word of the T fragment of column block w, so the A side is taken (general form: multiplied) from the T-side registers.
+// Constant-weight form (CW, syrk1_kernel_cw): no g1 piece, no g1 slots, no multiplies; see syrk1_main.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int S1_IMG = KC * LDS_KS;   // doubles per image (16 k-rows of 144)
 constexpr int S1_BUF = 2 * S1_IMG;    // doubles per chunk buffer (image I + image J)
 
-template <bool DIAG, int W>
+template <bool DIAG, int W, bool CW>
 __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* lds, double* wl, int p, int it, int jt, int sidx, int slab,
                                            int per_p, int w) {
     typedef v4d acc_t;
@@ -2723,7 +2729,11 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
     // block 7 - W (9 of the 16 pairs); MB = T-side fragments needed per k-step
     constexpr int MB = DIAG ? 8 - W : 8;
     constexpr int NM = DIAG ? 9 : 16;
-    constexpr int NR = 2 + MB;
+    // fragment reads per k-step.  Diagonal tile: both sides come from the one image and the A fragment of row block w is the very
+    // LDS word of the T fragment of column block w (offa0 == offb + 16 w, offa1 == offb + 16 (7 - w), both inside 0 .. 7 - W
+    // because W <= 3): the A side is taken from the T-side registers, nothing is read twice
+    constexpr int NR = DIAG ? MB : 2 + MB;
+    constexpr int F0 = (DIAG && CW) ? 2 : 0;  // first entry of a fragment set in use (constant-weight diagonal: no A-side copies)
 
     const int lr = lane & 15, lk = lane >> 4;
     const int offa0 = lk * LDS_KS + w * 16 + lr;
@@ -2766,7 +2776,7 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
     const uint64_t g1_u = uni64(a.g1), g0_u = uni64(a.g0);
     const uint64_t wchunk = (uint64_t)KC * P * sizeof(double);
     auto dma_weights = [&](const int64_t c, const int buf) TSVGP_AI {  // wl: [buffer][g1 | g0][128 doubles]
-        if (w == 0 || (DIAG && w == 1)) {
+        if ((!CW && w == 0) || (DIAG && w == 1)) {  // constant-weight form: g1 is not read (a.g1 is null)
             const unsigned la = wl_u + (unsigned)((buf * 256 + (w == 1 ? 128 : 0)) * sizeof(double));
             const uint64_t g = (w == 1 ? g0_u : g1_u) + (uint64_t)c * wchunk;
             const unsigned vo_ = dvo;
@@ -2785,7 +2795,8 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
         if constexpr (I < 4) w1r[I] = wl[buf * 256 + woff + I * 4 * P];
         else w0r[I - 4] = wl[buf * 256 + 128 + woff + (I - 4) * 4 * P];
     };
-    constexpr int NW = DIAG ? 8 : 4;
+    constexpr int NW = (CW ? 0 : 4) + (DIAG ? 4 : 0);  // weight slots per chunk; the constant-weight form has g0's only
+    constexpr int W0 = CW ? 4 : 0;
 
     acc_t acc[2][8];
 #pragma unroll
@@ -2803,11 +2814,28 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
     };
     auto rds = [&](Frag1<double>& f, auto slot_tag, auto ks_tag, const int boff) TSVGP_AI {  // T-side fragments first, A-side last
         constexpr int S = decltype(slot_tag)::value;
-        if constexpr (S < MB) rd1(f, TSVGP_IC(2 + S), ks_tag, boff);
+        if constexpr (DIAG) {
+            // column blocks 7 - W and W first: they are the A side of every MFMA of the k-step (and 7 - W the T side of its last
+            // one only); then the others in the order the MFMAs take them
+            constexpr int blk = S == 0 ? 7 - W : S == 1 ? W : (S - 2 < W ? S - 2 : S - 1);
+            rd1(f, TSVGP_IC(2 + blk), ks_tag, boff);
+        } else if constexpr (S < MB) rd1(f, TSVGP_IC(2 + S), ks_tag, boff);
         else rd1(f, TSVGP_IC(S - MB), ks_tag, boff);
     };
+    // the A fragments of a k-step times the lane's weight of its k-row; a diagonal tile makes them from the T-side registers of
+    // column blocks W and 7 - W.  Nothing in the constant-weight form: the scale is applied once, in syrk_reduce_kernel
+    auto weigh = [&](auto& f, auto ks_tag) TSVGP_AI {
+        constexpr int KW = decltype(ks_tag)::value;
+        if constexpr (!CW && DIAG) {
+            f.v[0] = f.v[2 + W] * w1r[KW];
+            f.v[1] = f.v[2 + 7 - W] * w1r[KW];
+        } else if constexpr (!CW) {
+            f.v[0] *= w1r[KW];
+            f.v[1] *= w1r[KW];
+        }
+    };
     auto keep_set = [&](const Frag1<double>& f) TSVGP_AI {
-        cfor<0, NR>([&](auto e) TSVGP_AI {
+        cfor<F0, 2 + MB>([&](auto e) TSVGP_AI {
             const double x = f.v[decltype(e)::value];
             asm volatile("" ::"v"(x));
         });
@@ -2823,7 +2851,8 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
             // n <= W: both row blocks (pairs 2 n, 2 n + 1); W < n <= 7 - W: row block 1 only
             constexpr int n = (I < 2 * (W + 1)) ? (I >> 1) : (I - (W + 1));
             constexpr int sblk = (I < 2 * (W + 1)) ? (I & 1) : 1;
-            acc[sblk][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.v[sblk], f.v[2 + n], acc[sblk][n], 0, 0, 0);
+            constexpr int ea = CW ? 2 + (sblk ? 7 - W : W) : sblk;  // constant weight: the T fragment of the row block itself
+            acc[sblk][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.v[ea], f.v[2 + n], acc[sblk][n], 0, 0, 0);
         }
     };
     v2d f1[4];  // first-order sum: the lane's column pair in its four k-rows
@@ -2850,8 +2879,7 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
                     f1[I - NR] = *reinterpret_cast<const v2d*>(lds + off1 + B0 + (I - NR) * 4 * LDS_KS);
                 TSVGP_SB();
             });
-            nxt.v[0] *= w1r[KS_ + 1];
-            nxt.v[1] *= w1r[KS_ + 1];
+            weigh(nxt, TSVGP_IC(KS_ + 1));
             if constexpr (DIAG && KS_ == 1) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -2874,13 +2902,12 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
                 constexpr int I = decltype(i)::value;
                 if constexpr (I < NM) mf(fy, i);
                 if constexpr (I < NDMA) dma_piece(TSVGP_IC(DIAG ? 2 * I : I), BUF);
-                else if constexpr (I < NDMA + NW) read_weight(TSVGP_IC(I - NDMA), BUF ^ 1);
+                else if constexpr (I < NDMA + NW) read_weight(TSVGP_IC(W0 + I - NDMA), BUF ^ 1);
                 else if constexpr (I < S3) rds(fx, TSVGP_IC(I - NDMA - NW), TSVGP_IC(0), B1);
                 TSVGP_SB();
             });
             dma_weights(c_fetch, BUF);
-            fx.v[0] *= w1r[0];
-            fx.v[1] *= w1r[0];
+            weigh(fx, TSVGP_IC(0));
             TSVGP_SB();
         } else {
             cfor<0, NM>([&](auto i) TSVGP_AI { mf(fy, i); });
@@ -2900,10 +2927,9 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        cfor<0, NW>([&](auto i) TSVGP_AI { read_weight(i, 0); });
+        cfor<0, NW>([&](auto i) TSVGP_AI { read_weight(TSVGP_IC(W0 + decltype(i)::value), 0); });
         cfor<0, NR>([&](auto i) TSVGP_AI { rds(fx, i, TSVGP_IC(0), 0); });
-        fx.v[0] *= w1r[0];
-        fx.v[1] *= w1r[0];
+        weigh(fx, TSVGP_IC(0));
         // chunk i of the slice sits in buffer i & 1 and fetches chunk i + 2 (clamped to the last one: a harmless re-fetch
         // into a dead buffer) while a chunk follows it
         int i = 0;
@@ -2954,10 +2980,11 @@ __device__ __forceinline__ void syrk1_body(const SyrkArgs<double>& a, double* ld
     }
 }
 
-__global__ __launch_bounds__(NTHREADS, 1) void syrk1_kernel(SyrkArgs<double> a) {
-    __shared__ __attribute__((aligned(1024))) double lds[2 * S1_BUF];
-    __shared__ __attribute__((aligned(1024))) double wl[2 * 256];  // per chunk buffer: 128 doubles of g1, 128 of g0
-
+// CW: the constant-weight form (syrk1_kernel_cw): g1[n, p] = c[p] on every row, so the kernel sums b_n b_n^T unweighted -- no
+// g1 piece, no g1 slots read back, no multiply of the A fragments -- and syrk_reduce_kernel applies c[p] once per element.
+// The first-order sum (g0) is the same code in both forms.
+template <bool CW>
+__device__ __forceinline__ void syrk1_main(const SyrkArgs<double>& a, double* lds, double* wl) {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nt = a.nt, n_off = nt * (nt - 1) / 2;
     const int per_p = n_off * a.ns_off + nt * a.ns_diag;
@@ -2979,16 +3006,28 @@ __global__ __launch_bounds__(NTHREADS, 1) void syrk1_kernel(SyrkArgs<double> a) 
     const int tri = it * (it + 1) / 2 + jt;
     const int slab = (tri - it) * a.ns_off + it * a.ns_diag + sidx;
     if (it != jt) {
-        syrk1_body<false, 0>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1_body<false, 0, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 0) {
-        syrk1_body<true, 0>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1_body<true, 0, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 1) {
-        syrk1_body<true, 1>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1_body<true, 1, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 2) {
-        syrk1_body<true, 2>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1_body<true, 2, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else {
-        syrk1_body<true, 3>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1_body<true, 3, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     }
+}
+
+__global__ __launch_bounds__(NTHREADS, 1) void syrk1_kernel(SyrkArgs<double> a) {
+    __shared__ __attribute__((aligned(1024))) double lds[2 * S1_BUF];
+    __shared__ __attribute__((aligned(1024))) double wl[2 * 256];  // per chunk buffer: 128 doubles of g1, 128 of g0
+    syrk1_main<false>(a, lds, wl);
+}
+
+__global__ __launch_bounds__(NTHREADS, 1) void syrk1_kernel_cw(SyrkArgs<double> a) {
+    __shared__ __attribute__((aligned(1024))) double lds[2 * S1_BUF];
+    __shared__ __attribute__((aligned(1024))) double wl[2 * 256];  // (the g1 halves stay unused: one LDS layout for both forms)
+    syrk1_main<true>(a, lds, wl);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3011,7 +3050,7 @@ constexpr int S1F_IMG = S1F_KC * TILE;  // floats per image (16 KB)
 constexpr int S1F_BUF = 2 * S1F_IMG;    // floats per chunk buffer (image I + image J)
 constexpr int S1F_WL = 512;             // floats of weights per chunk buffer: 256 of g1, 256 of g0
 
-template <bool DIAG, int W>
+template <bool DIAG, int W, bool CW>
 __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds, float* wl, int p, int it, int jt, int sidx,
                                             int slab, int per_p, int w) {
     typedef v4f acc_t;
@@ -3028,7 +3067,9 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
 
     constexpr int MB = DIAG ? 8 - W : 8;  // as syrk1_body
     constexpr int NM = DIAG ? 9 : 16;
-    constexpr int NR = 2 + MB;
+    constexpr int NR = DIAG ? MB : 2 + MB;    // as syrk1_body: on a diagonal tile the A side is the T fragments of blocks W, 7 - W
+    constexpr int F0 = (DIAG && CW) ? 2 : 0;  // (the swizzle moves block n of an odd k-row for both sides alike: offa0 is the
+                                              // address of T fragment w, offa1 of T fragment 7 - w)
     constexpr int NKS = S1F_KC / 4;  // k-steps per chunk
 
     // fragment of k-row k = 4 ks + lk, column 16 n + lr: float k * 128 + 16 (n ^ (k & 1)) + lr, and k & 1 = lk & 1
@@ -3072,7 +3113,7 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
     const uint64_t g1_u = uni64(a.g1), g0_u = uni64(a.g0);
     const uint64_t wchunk = (uint64_t)S1F_KC * P * sizeof(float);
     auto dma_weights = [&](const int64_t c, const int buf) TSVGP_AI {  // wl: [buffer][g1 | g0][256 floats]
-        if (w == 0 || (DIAG && w == 1)) {
+        if ((!CW && w == 0) || (DIAG && w == 1)) {  // constant-weight form: g1 is not read (a.g1 is null)
             const unsigned la = wl_u + (unsigned)((buf * S1F_WL + (w == 1 ? 256 : 0)) * sizeof(float));
             const uint64_t g = (w == 1 ? g0_u : g1_u) + (uint64_t)c * wchunk;
             const unsigned vo_ = dvw;
@@ -3092,7 +3133,8 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
         else w0r[I - NKS] = wl[buf * S1F_WL + 256 + woff + (I - NKS) * 4 * P];
     };
     // weight slot J of a half (HALF 0: k-steps 0..3, read in front of the chunk; HALF 1: k-steps 4..7, read at its start)
-    constexpr int NWH = DIAG ? 8 : 4;
+    constexpr int NWH = (CW ? 0 : 4) + (DIAG ? 4 : 0);  // the constant-weight form has g0's slots only
+    constexpr int WH0 = CW ? 4 : 0;
     auto read_weight_half = [&](auto j_tag, auto half_tag, const int buf) TSVGP_AI {
         constexpr int J = decltype(j_tag)::value, H = decltype(half_tag)::value;
         if constexpr (J < 4) read_weight(TSVGP_IC(4 * H + J), buf);
@@ -3115,11 +3157,28 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
     };
     auto rds = [&](Frag& f, auto slot_tag, auto ks_tag, const int boff) TSVGP_AI {  // T-side fragments first, A-side last
         constexpr int S = decltype(slot_tag)::value;
-        if constexpr (S < MB) rd1(f, TSVGP_IC(2 + S), ks_tag, boff);
+        if constexpr (DIAG) {
+            // column blocks 7 - W and W first: they are the A side of every MFMA of the k-step (and 7 - W the T side of its last
+            // one only); then the others in the order the MFMAs take them
+            constexpr int blk = S == 0 ? 7 - W : S == 1 ? W : (S - 2 < W ? S - 2 : S - 1);
+            rd1(f, TSVGP_IC(2 + blk), ks_tag, boff);
+        } else if constexpr (S < MB) rd1(f, TSVGP_IC(2 + S), ks_tag, boff);
         else rd1(f, TSVGP_IC(S - MB), ks_tag, boff);
     };
+    // the A fragments of a k-step times the lane's weight of its k-row; a diagonal tile makes them from the T-side registers of
+    // column blocks W and 7 - W.  Nothing in the constant-weight form: the scale is applied once, in syrk_reduce_kernel
+    auto weigh = [&](auto& f, auto ks_tag) TSVGP_AI {
+        constexpr int KW = decltype(ks_tag)::value;
+        if constexpr (!CW && DIAG) {
+            f.v[0] = f.v[2 + W] * w1r[KW];
+            f.v[1] = f.v[2 + 7 - W] * w1r[KW];
+        } else if constexpr (!CW) {
+            f.v[0] *= w1r[KW];
+            f.v[1] *= w1r[KW];
+        }
+    };
     auto keep_set = [&](const Frag& f) TSVGP_AI {
-        cfor<0, NR>([&](auto e) TSVGP_AI {
+        cfor<F0, 2 + MB>([&](auto e) TSVGP_AI {
             const float x = f.v[decltype(e)::value];
             asm volatile("" ::"v"(x));
         });
@@ -3132,7 +3191,8 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
         } else {
             constexpr int n = (I < 2 * (W + 1)) ? (I >> 1) : (I - (W + 1));
             constexpr int sblk = (I < 2 * (W + 1)) ? (I & 1) : 1;
-            acc[sblk][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.v[sblk], f.v[2 + n], acc[sblk][n], 0, 0, 0);
+            constexpr int ea = CW ? 2 + (sblk ? 7 - W : W) : sblk;  // constant weight: the T fragment of the row block itself
+            acc[sblk][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.v[ea], f.v[2 + n], acc[sblk][n], 0, 0, 0);
         }
     };
     v2f f1[NKS];  // first-order sum: the lane's column pair in its eight k-rows
@@ -3157,13 +3217,12 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
                 constexpr int I = decltype(i)::value;
                 if constexpr (I < NM) mf(cur, i);
                 if constexpr (I < NR) rds(nxt, i, TSVGP_IC(KS_ + 1), B0);
-                else if constexpr (I < NR + XW) read_weight_half(TSVGP_IC(I - NR), TSVGP_IC(1), BUF);
+                else if constexpr (I < NR + XW) read_weight_half(TSVGP_IC(WH0 + I - NR), TSVGP_IC(1), BUF);
                 else if constexpr (I < S)
                     f1[2 * KS_ + I - NR - XW] = *reinterpret_cast<const v2f*>(lds + off1 + B0 + (2 * KS_ + I - NR - XW) * 4 * TILE);
                 TSVGP_SB();
             });
-            nxt.v[0] *= w1r[KS_ + 1];
-            nxt.v[1] *= w1r[KS_ + 1];
+            weigh(nxt, TSVGP_IC(KS_ + 1));
             if constexpr (DIAG && (KS_ == 4 || KS_ == 5)) {
 #pragma unroll
                 for (int q = 4 * (KS_ - 4); q < 4 * (KS_ - 4) + 4; ++q) {
@@ -3185,13 +3244,12 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
                 constexpr int I = decltype(i)::value;
                 if constexpr (I < NM) mf(fy, i);
                 if constexpr (I < NDMA) dma_piece(TSVGP_IC(DIAG ? 2 * I : I), BUF);
-                else if constexpr (I < NDMA + NWH) read_weight_half(TSVGP_IC(I - NDMA), TSVGP_IC(0), BUF ^ 1);
+                else if constexpr (I < NDMA + NWH) read_weight_half(TSVGP_IC(WH0 + I - NDMA), TSVGP_IC(0), BUF ^ 1);
                 else if constexpr (I < S3) rds(fx, TSVGP_IC(I - NDMA - NWH), TSVGP_IC(0), B1);
                 TSVGP_SB();
             });
             dma_weights(c_fetch, BUF);
-            fx.v[0] *= w1r[0];
-            fx.v[1] *= w1r[0];
+            weigh(fx, TSVGP_IC(0));
             TSVGP_SB();
         } else {
             cfor<0, NM>([&](auto i) TSVGP_AI { mf(fy, i); });
@@ -3210,10 +3268,9 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        cfor<0, NWH>([&](auto i) TSVGP_AI { read_weight_half(i, TSVGP_IC(0), 0); });
+        cfor<0, NWH>([&](auto i) TSVGP_AI { read_weight_half(TSVGP_IC(WH0 + decltype(i)::value), TSVGP_IC(0), 0); });
         cfor<0, NR>([&](auto i) TSVGP_AI { rds(fx, i, TSVGP_IC(0), 0); });
-        fx.v[0] *= w1r[0];
-        fx.v[1] *= w1r[0];
+        weigh(fx, TSVGP_IC(0));
         int i = 0;
         const int64_t c_last = c_hi - 1;
         auto fetch_of = [&](int idx) TSVGP_AI { const int64_t c = c_lo + idx + 2; return c < c_last ? c : c_last; };
@@ -3258,11 +3315,8 @@ __device__ __forceinline__ void syrk1f_body(const SyrkArgs<float>& a, float* lds
     }
 }
 
-#define TSVGP_S1F_WAVES 2  // waves per SIMD the register allocation may assume at most (1: one workgroup per CU)
-__global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, TSVGP_S1F_WAVES))) void syrk1f_kernel(SyrkArgs<float> a) {
-    __shared__ __attribute__((aligned(1024))) float lds[2 * S1F_BUF];
-    __shared__ __attribute__((aligned(1024))) float wl[2 * S1F_WL];
-
+template <bool CW>  // as syrk1_main
+__device__ __forceinline__ void syrk1f_main(const SyrkArgs<float>& a, float* lds, float* wl) {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nt = a.nt, n_off = nt * (nt - 1) / 2;
     const int per_p = n_off * a.ns_off + nt * a.ns_diag;
@@ -3284,19 +3338,35 @@ __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 
     const int tri = it * (it + 1) / 2 + jt;
     const int slab = (tri - it) * a.ns_off + it * a.ns_diag + sidx;
     if (it != jt) {
-        syrk1f_body<false, 0>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1f_body<false, 0, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 0) {
-        syrk1f_body<true, 0>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1f_body<true, 0, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 1) {
-        syrk1f_body<true, 1>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1f_body<true, 1, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else if (w == 2) {
-        syrk1f_body<true, 2>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1f_body<true, 2, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     } else {
-        syrk1f_body<true, 3>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
+        syrk1f_body<true, 3, CW>(a, lds, wl, p, it, jt, sidx, slab, per_p, w);
     }
 }
 
-// Sums the partial tiles over the splits in a fixed order and writes the full symmetric matrix (fp64).
+#define TSVGP_S1F_WAVES 2  // waves per SIMD the register allocation may assume at most (1: one workgroup per CU)
+__global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, TSVGP_S1F_WAVES))) void syrk1f_kernel(SyrkArgs<float> a) {
+    __shared__ __attribute__((aligned(1024))) float lds[2 * S1F_BUF];
+    __shared__ __attribute__((aligned(1024))) float wl[2 * S1F_WL];
+    syrk1f_main<false>(a, lds, wl);
+}
+
+__global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, TSVGP_S1F_WAVES))) void syrk1f_kernel_cw(SyrkArgs<float> a) {
+    __shared__ __attribute__((aligned(1024))) float lds[2 * S1F_BUF];
+    __shared__ __attribute__((aligned(1024))) float wl[2 * S1F_WL];
+    syrk1f_main<true>(a, lds, wl);
+}
+
+// Sums the partial tiles over the splits in a fixed order and writes the full symmetric matrix (fp64).  scale: null (the general
+// form: the weights went into the products) or the P constants c[p] of the constant-weight form, which multiply each summed
+// element once, in front of the two writes (the "+ 0.0" of the fma keeps an empty sum at +0.0 under a negative c, as the
+// weighted products leave it).
 // One block per 16-row strip of a 128 x 128 tile: the sums go out row by row (1 KB runs) and, through an LDS image of the
 // strip, mirrored as 128 rows of 16 (128-byte runs).  (Up to round 5 a block took two rows and every thread wrote its mirrored
 // element on its own: a column of 8-byte stores 8 KB apart, 67 us for M = 1024 where the 41 MB it moves are ~10 us.)
@@ -3305,6 +3375,7 @@ template <typename T>
 __global__ __launch_bounds__(NTHREADS) void syrk_reduce_kernel(const T* __restrict__ part2,
                                                                const T* __restrict__ part1,
                                                                double* __restrict__ acc2, double* __restrict__ acc1,
+                                                               const double* __restrict__ scale,
                                                                int Mp, int P, int nt, int ns_off, int ns_diag) {
     // grid.x = ntri * (128 / SR_ROWS) + blocks for acc1, grid.y = P
     __shared__ double img[SR_ROWS][TILE + 1];
@@ -3330,6 +3401,11 @@ __global__ __launch_bounds__(NTHREADS) void syrk_reduce_kernel(const T* __restri
         for (int sp = 0; sp < ns; ++sp) {
 #pragma unroll
             for (int q = 0; q < RPT; ++q) acc[q] += (double)src[(size_t)sp * (TILE * TILE) + q * (NTHREADS / 128) * TILE];
+        }
+        if (scale) {
+            const double c = scale[p];
+#pragma unroll
+            for (int q = 0; q < RPT; ++q) acc[q] = __builtin_fma(acc[q], c, 0.0);
         }
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
@@ -5541,14 +5617,18 @@ int64_t site_accum_work_bytes(int Mp, int P, int nsplit) {
 }
 
 template <typename T>
-int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, double* acc2, double* acc1, void* work, int64_t Np,
-               int Mp, int P, int nsplit, void* stream) {
-    if (!B || !g0 || !g1 || !acc2 || !acc1 || !work || Np <= 0 || (Np % TILE) || Mp <= 0 || (Mp % TILE) || P <= 0 ||
+int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, const double* g1_const, double* acc2, double* acc1,
+               void* work, int64_t Np, int Mp, int P, int nsplit, void* stream) {
+    // exactly one of g1 (the general form) and g1_const (the constant-weight form: P <= 8, the hand-laid kernels) is given
+    const bool cw = g1_const != nullptr;
+    if (cw ? (g1 != nullptr || P > 8) : !g1) return TSVGP_EINVAL;
+    if (!B || !g0 || !acc2 || !acc1 || !work || Np <= 0 || (Np % TILE) || Mp <= 0 || (Mp % TILE) || P <= 0 ||
         nsplit <= 0 || strideB < 0 || (strideB != 0 && strideB < Np * (int64_t)Mp))
         return TSVGP_EINVAL;
     // the operand rows and the weights of a chunk travel by 16-byte LDS-DMA pieces: B, g0, g1 (contiguous [Np x P]) on
     // 16-byte boundaries, as every allocator hands them out; a sliced view that is not gets an error, not a fault
-    if (((uintptr_t)B | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)work) & 15 || ((strideB * (int64_t)sizeof(T)) & 15))
+    if (((uintptr_t)B | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)work) & 15 || ((strideB * (int64_t)sizeof(T)) & 15) ||
+        ((uintptr_t)g1_const & 7))
         return TSVGP_EINVAL;
     const int nt = Mp / TILE, ntri = nt * (nt + 1) / 2, n_off = ntri - nt;
     const int64_t total_chunks = Np / KC;
@@ -5573,8 +5653,14 @@ int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, double* ac
     if (sizeof(T) == 8 && P <= 8) {  // (the weights of a chunk travel as one 1-KiB LDS-DMA piece: 16 P doubles)
       if constexpr (sizeof(T) == 8) {
         static DynLdsOptIn optin_s1;  // 72 KB of static LDS: above the 64 KB a kernel gets without asking
-        if (optin_s1.ensure(reinterpret_cast<const void*>(&syrk1_kernel), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
-        hipLaunchKernelGGL(syrk1_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        static DynLdsOptIn optin_s1c;
+        if (cw) {
+            if (optin_s1c.ensure(reinterpret_cast<const void*>(&syrk1_kernel_cw), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
+            hipLaunchKernelGGL(syrk1_kernel_cw, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        } else {
+            if (optin_s1.ensure(reinterpret_cast<const void*>(&syrk1_kernel), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
+            hipLaunchKernelGGL(syrk1_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        }
       }
     } else if (sizeof(T) == 4 && P <= 8) {
       if constexpr (sizeof(T) == 4) {
@@ -5582,15 +5668,21 @@ int site_accum(const T* B, int64_t strideB, const T* g0, const T* g1, double* ac
         a.chunks_off = (total32 + a.ns_off - 1) / a.ns_off;
         a.chunks_diag = (total32 + a.ns_diag - 1) / a.ns_diag;
         static DynLdsOptIn optin_s1f;  // 68 KB of static LDS
-        if (optin_s1f.ensure(reinterpret_cast<const void*>(&syrk1f_kernel), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
-        hipLaunchKernelGGL(syrk1f_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        static DynLdsOptIn optin_s1fc;
+        if (cw) {
+            if (optin_s1fc.ensure(reinterpret_cast<const void*>(&syrk1f_kernel_cw), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
+            hipLaunchKernelGGL(syrk1f_kernel_cw, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        } else {
+            if (optin_s1f.ensure(reinterpret_cast<const void*>(&syrk1f_kernel), 0) != TSVGP_OK) return TSVGP_ELAUNCH;
+            hipLaunchKernelGGL(syrk1f_kernel, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+        }
       }
     } else
         hipLaunchKernelGGL(syrk_kernel<T>, dim3((unsigned)nwg), dim3(NTHREADS), 0, (hipStream_t)stream, a);
     if (launch_status() != TSVGP_OK) return TSVGP_ELAUNCH;
     const int extra = (Mp + NTHREADS - 1) / NTHREADS;
     hipLaunchKernelGGL(syrk_reduce_kernel<T>, dim3((unsigned)(ntri * (TILE / SR_ROWS) + extra), (unsigned)P), dim3(NTHREADS), 0,
-                       (hipStream_t)stream, a.part2, a.part1, acc2, acc1, Mp, P, nt, a.ns_off, a.ns_diag);
+                       (hipStream_t)stream, a.part2, a.part1, acc2, acc1, g1_const, Mp, P, nt, a.ns_off, a.ns_diag);
     return launch_status();
 }
 
@@ -6668,19 +6760,39 @@ int64_t tsvgp_site_accum_work_bytes_f32(int Mp, int P, int nsplit) {
 }
 int tsvgp_site_accum_f64(const double* B, const double* g0, const double* g1, double* acc2, double* acc1, void* work,
                          int64_t Np, int Mp, int P, int nsplit, void* stream) {
-    return site_accum<double>(B, 0, g0, g1, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+    return site_accum<double>(B, 0, g0, g1, nullptr, acc2, acc1, work, Np, Mp, P, nsplit, stream);
 }
 int tsvgp_site_accum_batched_f64(const double* B, int64_t strideB, const double* g0, const double* g1, double* acc2,
                                  double* acc1, void* work, int64_t Np, int Mp, int P, int nsplit, void* stream) {
-    return site_accum<double>(B, strideB, g0, g1, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+    return site_accum<double>(B, strideB, g0, g1, nullptr, acc2, acc1, work, Np, Mp, P, nsplit, stream);
 }
 int tsvgp_site_accum_batched_f32(const float* B, int64_t strideB, const float* g0, const float* g1, double* acc2,
                                  double* acc1, void* work, int64_t Np, int Mp, int P, int nsplit, void* stream) {
-    return site_accum<float>(B, strideB, g0, g1, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+    return site_accum<float>(B, strideB, g0, g1, nullptr, acc2, acc1, work, Np, Mp, P, nsplit, stream);
 }
 int tsvgp_site_accum_f32(const float* B, const float* g0, const float* g1, double* acc2, double* acc1, void* work,
                          int64_t Np, int Mp, int P, int nsplit, void* stream) {
-    return site_accum<float>(B, 0, g0, g1, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+    return site_accum<float>(B, 0, g0, g1, nullptr, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+}
+int tsvgp_site_accum_cw_f64(const double* B, const double* g0, const double* g1_const, double* acc2, double* acc1, void* work,
+                            int64_t Np, int Mp, int P, int nsplit, void* stream) {
+    if (!g1_const) return TSVGP_EINVAL;
+    return site_accum<double>(B, 0, g0, nullptr, g1_const, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+}
+int tsvgp_site_accum_cw_f32(const float* B, const float* g0, const double* g1_const, double* acc2, double* acc1, void* work,
+                            int64_t Np, int Mp, int P, int nsplit, void* stream) {
+    if (!g1_const) return TSVGP_EINVAL;
+    return site_accum<float>(B, 0, g0, nullptr, g1_const, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+}
+int tsvgp_site_accum_cw_batched_f64(const double* B, int64_t strideB, const double* g0, const double* g1_const, double* acc2,
+                                    double* acc1, void* work, int64_t Np, int Mp, int P, int nsplit, void* stream) {
+    if (!g1_const) return TSVGP_EINVAL;
+    return site_accum<double>(B, strideB, g0, nullptr, g1_const, acc2, acc1, work, Np, Mp, P, nsplit, stream);
+}
+int tsvgp_site_accum_cw_batched_f32(const float* B, int64_t strideB, const float* g0, const double* g1_const, double* acc2,
+                                    double* acc1, void* work, int64_t Np, int Mp, int P, int nsplit, void* stream) {
+    if (!g1_const) return TSVGP_EINVAL;
+    return site_accum<float>(B, strideB, g0, nullptr, g1_const, acc2, acc1, work, Np, Mp, P, nsplit, stream);
 }
 
 int tsvgp_potrf_f64(double* A, int M, int lda, int batch, int64_t stride, int* info, double* work, int flags,

@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -135,6 +136,18 @@ def site_sum_slices(Mp: int, P: int, Np, slots: int, f64: bool, oversubscribe=No
     return best
 
 
+def gaussian_g1_const(lik_id, lik_param, dtype=torch.float64):
+    """The value every live row of g1 takes under a homoskedastic Gaussian likelihood, as the moments kernel writes it --
+    -1 / (2 s2), cropped at -1e-8 unless LIK_NOCROP, rounded to the compute ``dtype`` -- or None when ``lik_id`` is another
+    likelihood or ``lik_param`` is no finite positive scalar: what a model hands ``EStepEngine.run(g1_const=...)``."""
+    if (lik_id & 0xFF) != B.LIK_GAUSSIAN or not isinstance(lik_param, (int, float)) or not (0.0 < lik_param < math.inf):
+        return None
+    c = -0.5 / float(lik_param)
+    if not (lik_id & B.LIK_NOCROP):
+        c = min(c, -1e-8)
+    return float(torch.tensor(c, dtype=torch.float64).to(dtype))
+
+
 class EStepEngine:
     """Launches the C-ABI kernels (include/tsvgp_hip.h) on torch-allocated device memory."""
 
@@ -157,6 +170,9 @@ class EStepEngine:
         self.last_trmm_batch = 1  # latents per whitening launch of that pass
         self.profile = None  # set to a dict to record (start, stop) HIP events per kernel launch on the launch stream
         self.profile_only = None  # a set of kernel names: bracket only these launches
+        self.constant_weight_sites = True  # ``run`` takes ``g1_const`` (the models ask before they pass it)
+        self.site_sum_calls = {"general": 0, "constant_weight": 0}  # launches of ``_site_sums`` by form
+        self._g1c = None  # (value, P, device tensor) of the last constant-weight launch
         # A/B switch: round 4's diagonal-block kernel instead of round 5's (TSVGP_POTRF_DIAG_V1)
         self.potrf_flags = B.POTRF_DIAG_V1 if os.environ.get("TSVGP_POTRF_DIAG_V1") == "1" else 0
 
@@ -1012,7 +1028,7 @@ class EStepEngine:
         return KfuP
 
     def _run_batched(self, X, Y, Z, kernel, whitened, *, moment_Tm, moment_mode, gamma, lik_id, lik_param, whiten_T,
-                     sites, want_moments, want_grads, mean_only, prefill=None, mix=None) -> EStepStats:
+                     sites, want_moments, want_grads, mean_only, prefill=None, mix=None, g1_const=None) -> EStepStats:
         """One pass for P latents with one kernel each as batched launches: fill [P, Np, Mp] -> in-place whitening of the
         latents that ask for it -> moments -> site sums (4 launches; BASELINE configs[4])."""
         T, dev = self.dtype, self.device
@@ -1076,7 +1092,7 @@ class EStepEngine:
             stats.g0, stats.g1 = g0[:N].to(torch.float64), g1[:N].to(torch.float64)
         self._mixed_stats(stats, lm, N, want_moments, want_grads)
         if sites:
-            stats.acc2, stats.acc1 = self._site_sums(KfuP, g0, g1, P, M)
+            stats.acc2, stats.acc1 = self._site_sums(KfuP, g0, g1, P, M, g1_const=None if mapped else g1_const)
         self.last_batched = True
         return stats
 
@@ -1097,6 +1113,9 @@ class EStepEngine:
             kw["mean_only"] = False  # the mixed map takes (Fmu, Fvar) whatever the likelihood reads of them
         # the map runs behind the moments: coupled latents, a scalar map, or any likelihood on mixed outputs
         mapped = (lik_id & 0xFF) in B.MAPPED_LIKS or mix is not None
+        g1_const = kw.pop("g1_const", None)
+        if not mapped:  # (behind a map the gradients are per row: the general form)
+            kw["g1_const"] = g1_const
         if mapped or Y is not None:
             self._check_y(Y, X.shape[0], P, lik_id, kw.get("lik_param"), outputs=None if mix is None else mix.shape[0])
         if X.shape[0] > 0:
@@ -1111,7 +1130,8 @@ class EStepEngine:
                                          gamma=gamma, lik_id=kw.get("lik_id", B.LIK_NONE), lik_param=kw.get("lik_param", 0.0),
                                          whiten_T=whiten_T, sites=kw.get("sites", False),
                                          want_moments=kw.get("want_moments", False), want_grads=want_grads,
-                                         mean_only=kw.get("mean_only", False), prefill=prefill, mix=mix)
+                                         mean_only=kw.get("mean_only", False), prefill=prefill, mix=mix,
+                                         g1_const=kw.get("g1_const"))
         self.last_batched = False
         if mapped and X.shape[0] > 0:  # (an empty shard contributes zeros through the loop below)
             return self._run_separate_coupled(X, Y, Z, kernel, moment_Tm=moment_Tm, gamma=gamma, whiten_T=whiten_T,
@@ -1226,8 +1246,12 @@ class EStepEngine:
     def run(self, X, Y, Z, kernel, *, moment_Tm, moment_mode, gamma, lik_id=B.LIK_NONE, lik_param=0.0,
             whiten_T=None, whiten_mode=B.TRI_UPPER, project_T=None, sites=False, want_moments=False, want_grads=False,
             b_tag=None, mean_only=False, prefill=None, moments_on_kfu=False, project_mode=B.TRI_LOWER,
-            keep_tile=False, site_grads=None) -> EStepStats:
+            keep_tile=False, site_grads=None, g1_const=None) -> EStepStats:
         """One pass over the shard's rows.
+
+        g1_const (``estep.gaussian_g1_const``; LIK_GAUSSIAN only): the number g1 holds on every row, which lets the site sums run in
+        their constant-weight form (``_site_sums``).  Ignored where the gradients come out of a map behind the moments (mixed
+        outputs un-mix g1 per row).
 
         keep_tile (one latent, no whitening): the triangular product of the moments, t_n = Tm k_n, is STORED (``tsvgp_trmm``
         into the buffer "Tt", returned as ``stats.tile``) and the moments are assembled from it -- mean by a matrix-vector
@@ -1266,9 +1290,11 @@ class EStepEngine:
                                       lik_id=lik_id, lik_param=lik_param, whiten_T=whiten_T, whiten_mode=whiten_mode,
                                       project_T=project_T, sites=sites, want_moments=want_moments, want_grads=want_grads,
                                       mean_only=mean_only, moments_on_kfu=moments_on_kfu, project_mode=project_mode,
-                                      prefill=prefill)
+                                      prefill=prefill, g1_const=g1_const)
         if site_grads is not None and lik_id != B.LIK_NONE:
             raise ValueError("site_grads replaces the likelihood: lik_id must be LIK_NONE")
+        if g1_const is not None and (lik_id & 0xFF) != B.LIK_GAUSSIAN:
+            raise ValueError("g1_const: only a homoskedastic Gaussian likelihood has one g1 for every row")
         if mean_only and (lik_id & 0xFF) not in (B.LIK_NONE, B.LIK_GAUSSIAN):
             raise ValueError("mean_only needs a likelihood whose gradients do not depend on the predictive variance")
         T, dev = self.dtype, self.device
@@ -1385,14 +1411,19 @@ class EStepEngine:
             self.trmm(A, self._pad_square(project_T, Mp, "pad_proj"), Aproj, project_mode)
             A = Aproj
         if sites:
-            stats.acc2, stats.acc1 = self._site_sums(A, g0, g1, P, M)
+            stats.acc2, stats.acc1 = self._site_sums(A, g0, g1, P, M, g1_const=None if mapped else g1_const)
         return stats
 
-    def _site_sums(self, A, g0, g1, P, M):
+    def _site_sums(self, A, g0, g1, P, M, g1_const=None):
         """(sum_n g1 a a^T [P, M, M], sum_n g0 a [P, M]) over the rows of one operand A [Np, Mp] shared by the P latents
         (``tsvgp_site_accum_*``) or of one operand per latent, A [P, Np, Mp] (``tsvgp_site_accum_batched_*``); g0, g1 [Np, P] with
-        zero padding rows.  The only launch of either."""
+        zero padding rows.  The only launch of either.
+
+        g1_const (a float, P <= 8): the constant-weight form (``tsvgp_site_accum_cw_*``) -- g1 is that number on every live row,
+        so the kernels sum a a^T unweighted and the reduction scales the sums once; ``g1`` is not read.  Above eight latents the
+        general form runs on ``g1`` whatever ``g1_const`` says.  ``site_sum_calls`` counts the launches of either form."""
         dev = self.device
+        cw = g1_const is not None and P <= 8
         Np, Mp = A.shape[-2:]
         nsplit = self.nsplit_override or self.choose_nsplit(Mp, P, Np)
         nsplit = max(1, min(nsplit, Np // site_sum_chunk_rows(self.dtype == torch.float64, P)))
@@ -1400,12 +1431,20 @@ class EStepEngine:
         work = self._get("work", (nbytes,), torch.uint8)
         acc2 = torch.empty((P, Mp, Mp), dtype=torch.float64, device=dev)
         acc1 = torch.empty((P, Mp), dtype=torch.float64, device=dev)
+        name = "tsvgp_site_accum_cw" if cw else "tsvgp_site_accum"
         if A.dim() == 3:
-            fn, operand = self._fn("tsvgp_site_accum_batched"), (A.data_ptr(), Np * Mp)
+            fn, operand = self._fn(name + "_batched"), (A.data_ptr(), Np * Mp)
         else:
-            fn, operand = self._fn("tsvgp_site_accum"), (A.data_ptr(),)
+            fn, operand = self._fn(name), (A.data_ptr(),)
+        if cw:  # the P scalars on the device, kept while the value stays (it moves with the likelihood's variance: an M-step)
+            if self._g1c is None or self._g1c[:2] != (float(g1_const), P):
+                self._g1c = (float(g1_const), P, torch.full((P,), float(g1_const), dtype=torch.float64, device=dev))
+            weights = self._g1c[2]
+        else:
+            weights = g1
+        self.site_sum_calls["constant_weight" if cw else "general"] += 1
         with torch.cuda.device(dev):
-            self._launch("tsvgp_site_accum", lambda: fn(*operand, g0.data_ptr(), g1.data_ptr(), acc2.data_ptr(), acc1.data_ptr(),
+            self._launch("tsvgp_site_accum", lambda: fn(*operand, g0.data_ptr(), weights.data_ptr(), acc2.data_ptr(), acc1.data_ptr(),
                                                         work.data_ptr(), Np, Mp, P, nsplit, self._stream()))
         return acc2[:, :M, :M], acc1[:, :M]
 

@@ -38,7 +38,7 @@ import torch
 from .. import _backend as B
 from .. import distributed as D_
 from ..base import default_device, default_float, default_jitter, to_tensor
-from ..estep import EStepStats, per_latent
+from ..estep import EStepStats, gaussian_g1_const, per_latent
 from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
 from ..kernels import LinearCoregionalization, SeparateIndependent, latent_kernels
@@ -148,6 +148,15 @@ class base_SVGP(abc.ABC):
     def get_mean_chol_cov_inducing_posterior(self):
         """Returns the mean and cholesky factor of the covariance matrix of q(u)"""
         raise NotImplementedError
+
+    def _site_form(self, lik_id) -> dict:
+        """What hands the likelihood to the engine's site sums: ``g1_const`` for a homoskedastic Gaussian likelihood on the latents
+        themselves -- one g1 for every row, the constant-weight form (``gaussian_g1_const``) -- and nothing for every other
+        likelihood, for mixed outputs (g1 is un-mixed per row) and for an engine without that form."""
+        if not getattr(self._get_engine(), "constant_weight_sites", False) or self._lmc() is not None:
+            return {}
+        c = gaussian_g1_const(lik_id, self.likelihood.lik_param, self.compute_dtype)
+        return {} if c is None else {"g1_const": c}
 
     # -- P outputs mixed from the latents -------------------------------------------------------------------------
     def _lmc(self):
@@ -1155,7 +1164,7 @@ class t_SVGP(base_SVGP):
                      lik_id=self.likelihood.lik_id, lik_param=self.likelihood.lik_param,
                      whiten_T=ops["whiten_T"], whiten_mode=ops["whiten_mode"], project_T=ops["project_T"],
                      moments_on_kfu=ops["moments_on_kfu"], project_mode=ops["project_mode"],
-                     sites=True, b_tag=warm_key,
+                     sites=True, b_tag=warm_key, **self._site_form(self.likelihood.lik_id),
                      mean_only=self.skip_unused_variance and self.likelihood.lik_id == B.LIK_GAUSSIAN)
         return st, ops
 
@@ -1245,7 +1254,7 @@ class t_SVGP(base_SVGP):
         # 3. the N-pass: every latent over this rank's rows
         st = eng.run(X, Y, self._Z(), self.kernel, moment_Tm=Tm_full, prefill=pre, moment_mode=B.TRI_UPPER, gamma=gamma_full,
                      lik_id=self.likelihood.lik_id, lik_param=self.likelihood.lik_param, whiten_T=whiten_full,
-                     whiten_mode=B.TRI_UPPER, project_T=None, sites=True,
+                     whiten_mode=B.TRI_UPPER, project_T=None, sites=True, **self._site_form(self.likelihood.lik_id),
                      mean_only=self.skip_unused_variance and self.likelihood.lik_id == B.LIK_GAUSSIAN)
         # 4. reduce-scatter by latent (slots in owner order) + the three scalars
         blk = tri + M

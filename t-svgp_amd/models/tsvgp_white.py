@@ -191,7 +191,7 @@ class t_SVGP_white(base_SVGP):
         return self._get_engine().run(X, Y, ops["Z"], self.kernel, moment_Tm=ops["moment_Tm"], moment_mode=ops["moment_mode"],
                                       gamma=ops["gamma"], lik_id=lik_id, lik_param=self.likelihood.lik_param,
                                       whiten_T=ops["whiten_T"], whiten_mode=B.TRI_UPPER, sites=sites,
-                                      want_moments=want_moments)
+                                      want_moments=want_moments, **(self._site_form(lik_id) if sites else {}))
 
     def _check(self, ops, nonpos):
         zero = torch.zeros(1, dtype=torch.float64, device=self.device)

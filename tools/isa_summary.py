@@ -14,6 +14,7 @@ KERNELS = [("panel1_kernelIdLi1", "panel1_kernel<double, MOMENTS>  (tsvgp_moment
            ("panel1_kernelIfLi1", "panel1_kernel<float, MOMENTS>   (tsvgp_moments_f32)"),
            ("panel1_kernelIdLi0", "panel1_kernel<double, STORE>    (tsvgp_trmm_f64, upper form)"),
            ("syrk1_kernel", "syrk1_kernel  (tsvgp_site_accum_f64)"), ("syrk1f_kernel", "syrk1f_kernel (tsvgp_site_accum_f32)")]
+# (the tags are substrings: the constant-weight kernels syrk1_kernel_cw / syrk1f_kernel_cw are listed with the general ones)
 COLS = ("v_mfma", "scratch_", "v_accvgpr", "ds_read", "global_load_lds", "s_waitcnt", "s_barrier", "other")
 print("columns per basic block:", ", ".join(COLS), "  (blocks without MFMA, scratch or accvgpr instructions are left out)\n")
 first_dump = True
