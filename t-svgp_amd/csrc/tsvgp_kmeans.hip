@@ -1,7 +1,7 @@
 // tsvgp_kmeans.hip -- Lloyd's k-means for inducing points (tsvgp_kmeans_assign_f64, tsvgp_kmeans_update_f64; include/tsvgp_hip.h
 // (12)) and its k-means++ seeding (tsvgp_kmeanspp_f64; (13)) for CDNA4 (gfx950 / MI355X): 64-wide wavefronts, fp64 vector arithmetic, LDS broadcast reads.  A translation unit of its
-// own: it shares nothing with the E-step kernels of tsvgp_kernels.hip but the C-ABI header, and their object code does not depend
-// on it.
+// own: of what it shares with the E-step kernels of tsvgp_kernels.hip it uses the C-ABI header and launch_status alone (the rest of
+// tsvgp_device.h, which it includes for that one line, compiles to nothing here), and their object code does not depend on it.
 //
 // Kernel inventory
 //   kmeans_assign_kernel<DT>   nearest scaled centre per row: lanes along rows, centres broadcast from LDS; fp64 VALU bound, no
@@ -16,10 +16,9 @@
 #include <stdint.h>
 
 #include "tsvgp_hip.h"
+#include "tsvgp_device.h"
 
 namespace {
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? TSVGP_OK : TSVGP_ELAUNCH; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Lloyd's k-means for inducing points (tsvgp_kmeans_assign_f64, tsvgp_kmeans_update_f64): the two N-sized steps of an iteration.

@@ -1,4 +1,4 @@
-"""NumPy restatements of the Bernoulli (probit) Gauss-Hermite map of ``csrc/tsvgp_kernels.hip`` and the input grid the
+"""NumPy restatements of the Bernoulli (probit) Gauss-Hermite map of ``csrc/tsvgp_device.h`` and the input grid the
 Gaussian / Bernoulli map tests share (tests/test_bernoulli_ref_cpu.py, tests/test_gpu_gauss_bern_map.py).
 
 ``bern_sums_f32``  the kernel's ``bern_sums_f`` in ``np.float32`` arithmetic: the node and weight tables of GH_XF / GH_WF, the

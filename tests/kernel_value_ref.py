@@ -1,5 +1,5 @@
 """Entrywise reference, restatement, error bound and input grid for the kernel-matrix values ``variance * k_kind(s)`` that
-``kernel_profile<KIND>`` of ``csrc/tsvgp_kernels.hip`` forms at five sites (the fill, ``gram_to_kernel``, the epilogue of ``cov``,
+``kernel_profile<KIND>`` of ``csrc/tsvgp_device.h`` forms at five sites (the fill, ``gram_to_kernel``, the epilogue of ``cov``,
 ``vgp_system``, ``greedy_step``).  Shared by tests/test_kernel_value_ref_cpu.py and tests/test_gpu_kernel_values.py.
 
 ``reference``   K = variance * k_kind(s), s = sum_d ((x_d - z_d) inv_ls_d)^2 in ``np.longdouble`` from the inputs AS THE KERNEL

@@ -1,4 +1,4 @@
-"""Kernel-matrix values entry by entry at every site that evaluates ``kernel_profile`` (csrc/tsvgp_kernels.hip): the fill in all
+"""Kernel-matrix values entry by entry at every site that evaluates ``kernel_profile`` (csrc/tsvgp_device.h): the fill in all
 its row, column and store paths, ``tsvgp_gram_to_kernel_*``, the epilogue of ``tsvgp_cov_*``, ``tsvgp_vgp_system_f64`` and
 ``tsvgp_greedy_select_f64``, against the longdouble reference of tests/kernel_value_ref.py under its derived relative bound
 (flat constant doubled, ``GPU_FACTOR``) on its radial grid (a from 0 to the edge of the type's normal range, exact r = 0, both

@@ -232,9 +232,11 @@ def check_rules(text):
     return bad
 
 
-def _blocks_of(text, name):
+def _blocks_of(text, name, whole=False):
+    """[(label, [instruction text, ...]), ...] of one kernel up to its first s_endpgm; whole: up to the end of the function."""
     m = re.search(r"^" + re.escape(name) + r":", text, re.M)
-    body = text[m.end():text.find("s_endpgm", m.end())].split("\n")
+    end = re.compile(r"^\.Lfunc_end\d+:", re.M).search(text, m.end()).start() if whole else text.find("s_endpgm", m.end())
+    body = text[m.end():end].split("\n")
     blocks, cur = [], ("entry", [])
     for ln in body:
         t = ln.split(";")[0].strip()
@@ -248,12 +250,21 @@ def _blocks_of(text, name):
     return blocks
 
 
+def kernel_metadata(text):
+    """{kernel symbol: {field: value text}} from the amdhsa.kernels metadata of the assembly (the scalar fields of each entry)."""
+    out = {}
+    start = text.find("\namdhsa.kernels:")
+    if start < 0:
+        return out
+    for entry in re.split(r"^  - ", text[start:text.find("\namdhsa.target:", start)], flags=re.M)[1:]:
+        fields = dict(re.findall(r"^(?:    )?\.(\w+):[ \t]+(\S+)[ \t]*$", entry, re.M))
+        out[fields["name"]] = fields
+    return out
+
+
 def vgpr_counts(text):
     """{kernel symbol: VGPRs} from the metadata of the assembly (.vgpr_count)."""
-    out = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\s*\n(?:.*\n)*?\s*\.vgpr_count:\s+(\d+)", text):
-        out[m.group(1)] = int(m.group(2))
-    return out
+    return {name: int(f["vgpr_count"]) for name, f in kernel_metadata(text).items()}
 
 
 def main():
