@@ -48,6 +48,25 @@ class HeteroskedasticTFPConditional:
                        (d1 * z[None, None, :]).sum(axis=(1, 2)) / (2.0 * sd[:, 1])], axis=1)
         return g0, g1
 
+    def separated(self, Fmu, Fvar, Y):
+        """(g0, g1 [N, 2], ve [N]) from the separated form of the same grid sum: with S0 = sum_i w_i (y - f0_i)^2 = W0 r^2 + Q2 v0
+        (r = y - m0; the odd sums vanish node pair by node pair), S1 = sum_j w_j exp(-2 f1_j), T1 = sum_j w_j z_j exp(-2 f1_j),
+            ve = -1/2 log 2 pi W0^2 - W0^2 m1 - 1/2 S0 S1,   d/dm0 = W0 r S1,   d/dv0 = -1/2 Q2 S1,
+            d/dm1 = S0 S1 - W0^2,   d/dv1 = S0 T1 / (2 s1).
+        The literal grid above adds summands of size |r| S1 that cancel to d/dm0 = 0 at r = 0 and to d/dv0 = O(sd0) at any r: its
+        rounding error is u |r| S1 / sd0 there.  Against mpmath (tests/test_likmap_range_cpu.py's fixture) it returns d/dm0 = 1.2e25
+        where the sum is 0 (r = 0, v1 = 100) and d/dv0 to 1.7e-8 relative at |r| = 1e7, sd0 = 2.7e-3.  This form has no such sum;
+        it is the one the range tests compare the HIP map with."""
+        z, w = O.gh_points_and_weights(self.n_gh)
+        Fmu, Fvar = np.asarray(Fmu, np.float64), np.asarray(Fvar, np.float64)
+        m0, m1, v0, s1 = Fmu[:, 0], Fmu[:, 1], Fvar[:, 0], np.sqrt(Fvar[:, 1])
+        r = np.asarray(Y, np.float64).reshape(-1) - m0
+        e = w * np.exp(-2.0 * (m1[:, None] + s1[:, None] * z))
+        W0, Q2, S1, T1 = w.sum(), np.sum(w * z * z), e.sum(axis=1), (e * z).sum(axis=1)
+        S0 = W0 * r * r + Q2 * v0
+        ve = -0.5 * LOG_2PI * W0 * W0 - W0 * W0 * m1 - 0.5 * S0 * S1
+        return np.stack([W0 * r * S1, S0 * S1 - W0 * W0], axis=1), np.stack([-0.5 * Q2 * S1, S0 * T1 / (2.0 * s1)], axis=1), ve
+
     def predict_mean_and_var(self, Fmu, Fvar):
         f0, f1, W, _, _ = self._grid(Fmu, Fvar)
         ey = np.sum(W * f0 * np.ones_like(f1), axis=(1, 2))
