@@ -130,6 +130,25 @@ int tsvgp_kernel_fill_batched_f32(int kind, const float *X, const float *Z, cons
                                   const float *variance_host, float *K, int64_t strideK, int64_t N, int M, int D,
                                   int64_t ldk, int P, void *stream);
 
+/* (1s) The fill of a SUM of C stationary kernels (gpflow.kernels.Sum / k1 + k2 [ext]) on shared inputs, in ONE launch and one
+ *     write of K:
+ *        K[n, m] = sum_c variance[c] * k_{kind[c]}(r_c),   r_c^2 = sum_d ((x_nd - z_md) * inv_ls[c*D + d])^2,
+ *     the components added in index order, profiles and difference-form distance exactly as (1b) (same device functions).  A
+ *     component that acts on some input columns only has zeros in its row of inv_ls.  inv_ls [C x D] is a device array;
+ *     kinds_host [C] and variance_host [C] are HOST arrays (they travel as kernel arguments, as variance_host of (1c)).
+ *     1 <= C <= TSVGP_MAX_COMPONENTS, every kind one of TSVGP_KERNEL_* (the reserved 1 is refused).  Everything else as (1):
+ *     padding rows and columns up to the 128-multiples are written as exact zeros, D <= 32, ldk even and K on a boundary of
+ *     two elements (fp32 stores four columns per thread where K is on a 16-byte boundary and ldk a multiple of 4, else two:
+ *     the same values either way), non-temporal stores from 512 MB up; TSVGP_EINVAL before any launch otherwise.  With
+ *     C * Dpad <= 32 (Dpad = D padded to 1, 2, 4, 8, 16, 32) a thread keeps the scaled Z columns of all components in registers;
+ *     beyond it reloads them per component and chunk of 8 rows (csrc/tsvgp_sumfill.hip). */
+#define TSVGP_MAX_COMPONENTS 4
+int tsvgp_kernel_fill_sum_f64(const int *kinds_host, const double *X, const double *Z, const double *inv_ls,
+                              const double *variance_host, double *K, int64_t N, int M, int D, int64_t ldk, int C,
+                              void *stream);
+int tsvgp_kernel_fill_sum_f32(const int *kinds_host, const float *X, const float *Z, const float *inv_ls,
+                              const float *variance_host, float *K, int64_t N, int M, int D, int64_t ldk, int C, void *stream);
+
 /* (1d) Input dimensions beyond 32 (the reference's MNIST notebook has D = 784): the scaled squared distance is then a
  *     GEMM, r2[n,m] = xx[n] + zz[m] - 2 G[n,m] with G = (X/l)(Z/l)^T (GPflow's square_distance form [ext]), which the caller
  *     takes from the BLAS library into K [rows_pad x ldk]; this call turns it into K = variance * k(r2) in place and

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(CSRC, "libtsvgp_hip.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "tsvgp_hip.h")
 # one translation unit per kernel family that has been split off (the E-step's first: by far the longest compile)
 SOURCES = [os.path.join(CSRC, name) for name in ("tsvgp_kernels.hip", "tsvgp_chol.hip", "tsvgp_likmap.hip", "tsvgp_predict.hip",
-                                                 "tsvgp_select.hip", "tsvgp_kmeans.hip")]
+                                                 "tsvgp_select.hip", "tsvgp_kmeans.hip", "tsvgp_sumfill.hip")]
 HEADERS = [HEADER_PATH, os.path.join(CSRC, "tsvgp_chol.h"), os.path.join(CSRC, "tsvgp_device.h")]
 # per-source compiler switches: the small-matrix kernels keep their MFMA accumulators in VGPRs (the AGPR form the compiler
 # picks for a one-wave-per-SIMD kernel ran the panel kernel's dependent MFMA chains ~1.5x slower in a stamped lab build of that
@@ -27,6 +27,7 @@ SOURCE_FLAGS = {"tsvgp_chol.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 TILE = 128
 MAX_BATCH = 32  # TSVGP_MAX_BATCH: latents per launch of the *_batched entry points
+MAX_COMPONENTS = 4  # TSVGP_MAX_COMPONENTS: components of a Sum kernel in one tsvgp_kernel_fill_sum_* launch
 LIK_NONE, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_HETERO = 3  # two coupled latents: tsvgp_lik_map_hetero_* only
 LIK_SOFTMAX = 4  # C coupled latents, Monte Carlo: tsvgp_lik_map_softmax_* only
@@ -114,6 +115,10 @@ _PROTOTYPES = {
                                               c_int64, c_int, c_void_p]),
     "tsvgp_kernel_fill_batched_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
                                               c_int64, c_int, c_void_p]),
+    "tsvgp_kernel_fill_sum_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int,
+                                          c_void_p]),
+    "tsvgp_kernel_fill_sum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int,
+                                          c_void_p]),
     "tsvgp_gram_to_kernel_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int, c_int64, c_void_p]),
     "tsvgp_gram_to_kernel_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_int64, c_void_p]),
     "tsvgp_cov_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int64, c_int64, c_int, c_int, c_int64,

@@ -42,7 +42,7 @@ import torch
 
 from . import _backend as B
 from .distributed import world_size
-from .kernels import LinearCoregionalization, SeparateIndependent
+from .kernels import LinearCoregionalization, SeparateIndependent, Sum
 from .side_branch import SideBranch, SideStream
 
 MAX_INPUT_DIM = 32  # the fill kernel pads D to a compile-time size (1, 2, 4, 8, 16, 32)
@@ -330,6 +330,36 @@ class EStepEngine:
                                     N, M, D, out.shape[1], self._stream()))
         return out
 
+    def sum_fill(self, X: torch.Tensor, Z: torch.Tensor, kernel: Sum, out: torch.Tensor):
+        """out[Np x Mp] <- sum_c K_c(X, Z) (padding zero) for a ``Sum`` kernel: one launch of ``tsvgp_kernel_fill_sum_*``."""
+        N, D = X.shape
+        M = Z.shape[0]
+        if D > MAX_INPUT_DIM:
+            raise NotImplementedError(f"a Sum kernel takes at most {MAX_INPUT_DIM} input columns (the fused fill's compile-time "
+                                      f"sizes; the GEMM form is per component), got D = {D}")
+        C = len(kernel.kernels)
+        inv_ls = kernel.inv_lengthscales(D, X.dtype, self.device)  # [C, D]
+        kinds = (ctypes.c_int * C)(*kernel.kinds)
+        var = ((ctypes.c_double if X.dtype == torch.float64 else ctypes.c_float) * C)(*kernel.variances())
+        fn = self._fn("tsvgp_kernel_fill_sum", X.dtype)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_se_fill" if N != M or X.data_ptr() != Z.data_ptr() else "tsvgp_se_fill(Kuu)",
+                         lambda: fn(kinds, X.data_ptr(), Z.data_ptr(), inv_ls.data_ptr(), var, out.data_ptr(), N, M, D,
+                                    out.stride(0), C, self._stream()))
+        return out
+
+    def fill(self, X: torch.Tensor, Z: torch.Tensor, kernel, out: torch.Tensor):
+        """out[Np x Mp] <- K(X, Z) (padding zero) of ONE latent GP's kernel: a stationary kernel through ``se_fill``, a ``Sum``
+        through ``sum_fill``.  X, Z and out share one dtype."""
+        if isinstance(kernel, Sum):
+            return self.sum_fill(X, Z, kernel, out)
+        return self.se_fill(X, Z, kernel.inv_lengthscales(X.shape[1], X.dtype, self.device), kernel.variance.item(), out, kernel.kind)
+
+    @staticmethod
+    def kdiag(kernel) -> float:
+        """The prior variance k(x, x) of ONE latent GP's kernel as a Python float: ``variance``, or its sum over a ``Sum``."""
+        return kernel.prior_variance() if isinstance(kernel, Sum) else kernel.variance.item()
+
     def kuu(self, Z: torch.Tensor, kernel) -> torch.Tensor:
         """K(Z, Z) in fp64, [M, M] (no jitter); [P, M, M] for separate per-latent kernels."""
         if isinstance(kernel, SeparateIndependent):
@@ -338,8 +368,7 @@ class EStepEngine:
         M, D = Z.shape
         Mp = B.round_up(M)
         out = torch.empty((Mp, Mp), dtype=torch.float64, device=self.device)
-        inv_ls = kernel.inv_lengthscales(D, torch.float64, self.device)
-        self.se_fill(Z, Z, inv_ls, kernel.variance.item(), out, kernel.kind)
+        self.fill(Z, Z, kernel, out)
         return out[:M, :M].contiguous()
 
     def tri_copy(self, src: torch.Tensor, M: int, scale: float = 1.0, flip: int = 0, out: torch.Tensor = None,
@@ -955,9 +984,11 @@ class EStepEngine:
         for p in range(P):
             kern = kernels[p if len(kernels) > 1 else 0]
             if p == 0 or len(kernels) > 1:
-                self.se_fill(X, Z, kern.inv_lengthscales(D, T, dev), kern.variance.item(), Kfu, kern.kind)
+                self.fill(X, Z, kern, Kfu)
             torch.mm(Kfu, self._pad_square(0.5 * (Q[p] + Q[p].T), Mp, "pad_Q"), out=Ubuf)
-            self.moments_vjp(X, Z, kern, Ubuf, cm[:, p], cv[:, p], beta[:, p], dX, accumulate=p > 0)
+            # (a Sum: dK is the sum of its components' dK_c on the same U -- one launch each, accumulating behind the first)
+            for c, comp in enumerate(kern.kernels if isinstance(kern, Sum) else [kern]):
+                self.moments_vjp(X, Z, comp, Ubuf, cm[:, p], cv[:, p], beta[:, p], dX, accumulate=p > 0 or c > 0)
         return dX
 
     def selftest_mfma(self, dtype=None):
@@ -1235,11 +1266,10 @@ class EStepEngine:
                 self._fill_batched(Xc, Zc, kernel, buf)
         else:
             inv_ls = kernel.inv_lengthscales(D, T, dev)
-            variance = kernel.variance.item()
             buf = self._get("Kfu", (Np, Mp), T)
             with self.fork(reads=(Xc, Zc, inv_ls), writes=(buf,), name="Kfu", buf=buf,
                            key=(X.data_ptr(), tuple(X.shape), Z.data_ptr(), tuple(Z.shape), id(kernel))) as branch:
-                self.se_fill(Xc, Zc, inv_ls, variance, buf, kernel.kind)
+                self.fill(Xc, Zc, kernel, buf)
         return branch
 
     # ------------------------------------------------------------------ one N-pass
@@ -1324,8 +1354,7 @@ class EStepEngine:
             self._check_y(Y, N, P, lik_id, lik_param)
             Y = Y.to(device=dev, dtype=T).contiguous()
         Np, Mp = B.round_up(N), B.round_up(M)
-        inv_ls = kernel.inv_lengthscales(D, T, dev)
-        variance = kernel.variance.item()
+        variance = self.kdiag(kernel)
 
         # The N x M operand of the moments / site kernels: the whitened B = Kfu U^-T, or Kfu itself ("direct" route).
         # A tagged operand left by the previous call is reused when the tag matches (warm E-steps).
@@ -1344,7 +1373,7 @@ class EStepEngine:
                 prefill.take("Kfu", Kfu)
             else:
                 self._side.wait_stale()
-                self.se_fill(X, Z, inv_ls, variance, Kfu, kernel.kind)
+                self.fill(X, Z, kernel, Kfu)
             A = Kfu
             if whiten_T is not None and not late_whiten:
                 Bw = self._get("B", (Np, Mp), T)
@@ -1463,7 +1492,7 @@ class EStepEngine:
         N, M = X.shape[0], Z.shape[0]
         Np, Mp = B.round_up(N), B.round_up(M)
         Bw = self._buf["B"]  # the whitened operand of the pass just run
-        kff = kernel.variance.item()
+        kff = self.kdiag(kernel)
         bn = torch.linalg.vector_norm(Bw[:N], dim=1).to(torch.float64)
         var = (2.0 * kff - bn * bn)[:, None] - st.var  # st.var = kff - |T2 b|^2
         stats = EStepStats(n_rows=N, ve_sum=torch.zeros((), dtype=torch.float64, device=dev), nonpos=(~(var > 0)).sum().to(torch.float64))
@@ -1545,9 +1574,8 @@ class EStepEngine:
         self._side.wait_stale()
         for p in range(P):
             kp = kernel.kernels[p] if separate else kernel
-            inv_ls, variance = kp.inv_lengthscales(D, T, dev), kp.variance.item()
             if p == 0 or separate:
-                self.se_fill(X, Z, inv_ls, variance, Kfu, kp.kind)
+                self.fill(X, Z, kp, Kfu)
             A = Kfu
             wt = self._per_latent(whiten_T, p)
             if wt is not None:
@@ -1557,10 +1585,12 @@ class EStepEngine:
             self.trmm(A, Tm, tile, moment_mode)
             mean[:, p] = torch.mv(A[:N], gam[:, p])  # gam: [Mp, P], rows >= M zero
             C = cov[p] if Cw is None else Cw
-            base = dict(X=X, inv_ls=inv_ls, variance=variance, kind=kp.kind)
-            if D > MAX_INPUT_DIM:
-                self.se_fill(X, X, inv_ls, variance, C, kp.kind)  # the GEMM form (its padding is zero: the call below sets it)
+            if D > MAX_INPUT_DIM or isinstance(kp, Sum):
+                # the GEMM form, or the fused fill of a Sum (the padding is zero: the call below sets it)
+                self.fill(X, X, kp, C)
                 base = dict(accumulate=True)
+            else:
+                base = dict(X=X, inv_ls=kp.inv_lengthscales(D, T, dev), variance=kp.variance.item(), kind=kp.kind)
             if two_product:
                 self.cov(A, C, N, sign=-1.0, **base)
                 self.cov(tile, C, N, sign=1.0, accumulate=True)

@@ -10,7 +10,7 @@ import torch
 from ._backend import KMEANSPP_MAX_TRIALS
 from .base import Parameter, to_tensor
 from .estep import MAX_INPUT_DIM, EStepEngine
-from .kernels import LinearCoregionalization, SeparateIndependent
+from .kernels import LinearCoregionalization, SeparateIndependent, refuse_sum
 
 
 class InducingPoints:
@@ -84,6 +84,7 @@ def select_inducing_points(X, kernel, num_inducing, *, threshold=0.0, device=Non
     Out of scope: fp32 arithmetic (the selection is fp64 whatever X is), more than 32 input columns, and a row-sharded X -- a
     global argmax would cost one collective per step; a sharded caller selects on one rank from its shard or from a subsample.
     ``SeparateIndependent`` is refused: one kernel defines one conditional variance, so pass the latent's kernel you mean."""
+    refuse_sum(kernel, "select_inducing_points")
     if isinstance(kernel, LinearCoregionalization):
         raise NotImplementedError("select_inducing_points does not take LinearCoregionalization: one kernel defines one conditional "
                                   "variance; pass the kernel of the latent you mean")

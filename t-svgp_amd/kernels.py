@@ -3,6 +3,9 @@
 ``SquaredExponential`` mirrors ``gpflow.kernels.SquaredExponential`` (the kernel every reference test, notebook and
 experiment on this path uses: reference tests/models/test_tsvgp.py:100, experiments/uci_regression.py:186-187).
 The N-sized evaluations K(X, Z) run in the HIP fill kernel (``tsvgp_se_fill_*``); nothing here loops over data.
+
+``Sum`` (``k1 + k2``) adds up to four stationary components, each with its own variance, lengthscales and ``active_dims``;
+its K(X, Z) is one launch of ``tsvgp_kernel_fill_sum_*`` ("Sum kernels").
 """
 from __future__ import annotations
 
@@ -16,14 +19,42 @@ class SquaredExponential:
 
     kind = 0  # TSVGP_KERNEL_SE: selects the profile inside the HIP fill kernel (include/tsvgp_hip.h)
 
-    def __init__(self, variance=1.0, lengthscales=1.0, name=None):
+    def __init__(self, variance=1.0, lengthscales=1.0, name=None, active_dims=None):
         self.variance = Parameter(variance)
         self.lengthscales = Parameter(lengthscales)
         self.name = name or type(self).__name__.lower()
+        # the input columns this kernel acts on (gpflow's ``active_dims`` as a list); None: all of them.  On the device an
+        # inactive column is a zero in inv_lengthscales(): no HIP kernel knows about it
+        self.active_dims = None if active_dims is None else tuple(int(d) for d in active_dims)
+        if self.active_dims is not None:
+            if not self.active_dims or min(self.active_dims) < 0 or len(set(self.active_dims)) != len(self.active_dims):
+                raise ValueError(f"active_dims must be a non-empty list of distinct column indices >= 0, got {active_dims}")
+            ls = self.lengthscales.value
+            if ls.dim() > 0 and ls.shape[0] != len(self.active_dims):
+                raise ValueError(f"lengthscales has {ls.shape[0]} entries but active_dims names {len(self.active_dims)} columns")
 
     @property
     def ard(self) -> bool:
         return self.lengthscales.value.dim() > 0
+
+    def __add__(self, other):
+        return Sum([self, other])
+
+    def stamp(self):
+        """Cache key of the kernel's hyperparameters (identity + ``Parameter.stamp`` of each): what a carried-over K(X, Z), a
+        cached factor or a captured graph that baked them in is keyed on."""
+        return (id(self), self.variance.stamp(), self.lengthscales.stamp())
+
+    def prior_variance(self) -> float:
+        """k(x, x) as a Python float (no device read): the E-step's scalar ``kdiag``."""
+        return self.variance.item()
+
+    def gather_lengthscale_grad(self, dls: torch.Tensor) -> torch.Tensor:
+        """The [D] lengthscale gradient of the HIP contraction in the shape of the parameter: the active columns (an ARD
+        parameter) or their sum (an isotropic one)."""
+        if self.active_dims is not None:
+            dls = dls[list(self.active_dims)]
+        return dls if self.ard else dls.sum()
 
     def inv_lengthscales(self, D: int, dtype=None, device=None) -> torch.Tensor:
         """[D] vector of 1/lengthscale (isotropic values are broadcast)."""
@@ -33,6 +64,8 @@ class SquaredExponential:
         # an in-place edit of .value bumps only the tensor's own counter.  The returned tensor is shared: read-only.
         par = self.lengthscales
         key = (id(par), par.version, par.value.data_ptr(), par.value._version, D, dtype, str(device))
+        if self.active_dims is not None:
+            return self._inv_lengthscales_active(key + (self.active_dims,), D, dtype, device)
         hit = self.__dict__.get("_inv_ls_cache")
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -43,6 +76,25 @@ class SquaredExponential:
             raise ValueError(f"lengthscales has {ls.shape[0]} entries but the inputs have {D} columns")
         out = to_tensor(1.0 / ls, dtype, device).contiguous()
         self.__dict__["_inv_ls_cache"] = (key, out)
+        return out
+
+    def _inv_lengthscales_active(self, key, D, dtype, device) -> torch.Tensor:
+        """``inv_lengthscales`` with ``active_dims``: zeros on the inactive columns -- (x_d - z_d) * 0 drops them from every
+        scaled distance.  One cached vector per (D, dtype, device): an fp32 engine asks for the fp64 vector (K_uu) and the fp32
+        one (K(X, Z)) in turn, and a step replayed from a captured graph must find both (the scatter below reads an index
+        tensor made on the host, which a stream capture does not permit)."""
+        slots = self.__dict__.setdefault("_inv_ls_slots", {})
+        slot = (D, dtype, str(device))
+        hit = slots.get(slot)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        if max(self.active_dims) >= D:
+            raise ValueError(f"active_dims {list(self.active_dims)} names a column beyond the inputs' {D}")
+        ls = self.lengthscales.value
+        inv = torch.zeros(D, dtype=ls.dtype, device=ls.device)
+        inv[list(self.active_dims)] = 1.0 / (ls.expand(len(self.active_dims)) if ls.dim() == 0 else ls)
+        out = to_tensor(inv, dtype, device).contiguous()
+        slots[slot] = self.__dict__["_inv_ls_cache"] = (key, out)
         return out
 
     def K_diag(self, X) -> torch.Tensor:
@@ -56,6 +108,8 @@ class SquaredExponential:
     def K_torch(self, Z: torch.Tensor, variance: torch.Tensor, lengthscales: torch.Tensor) -> torch.Tensor:
         """K(Z, Z) as a differentiable torch expression of (variance, lengthscales, Z), difference form like the HIP
         fill.  Only for the M x M part of the M-step gradient (``t_SVGP.elbo_and_grads``); N-sized work never comes here."""
+        if self.active_dims is not None:
+            Z = Z[:, list(self.active_dims)]
         Zs = Z / lengthscales
         diff = Zs[:, None, :] - Zs[None, :, :]
         return variance * self._profile(torch.sum(diff * diff, dim=-1))
@@ -85,6 +139,86 @@ class Matern52(SquaredExponential):
         return (1.0 + a + 5.0 / 3.0 * sc) * torch.exp(-a)
 
 
+class Sum:
+    """``gpflow.kernels.Sum`` [ext] of 1 to ``MAX_COMPONENTS`` stationary kernels (``SquaredExponential`` / ``Matern32`` /
+    ``Matern52``, each with its own variance, lengthscales and ``active_dims``): k(x, z) = sum_c k_c(x, z), one latent GP.
+    k(x, x) = sum_c variance_c stays a constant, so everything behind the fill takes it unchanged; K(X, Z) is ONE launch of
+    ``tsvgp_kernel_fill_sum_*``."""
+
+    MAX_COMPONENTS = 4  # TSVGP_MAX_COMPONENTS
+
+    def __init__(self, kernels, name=None):
+        flat = []
+        for k in kernels:
+            flat.extend(k.kernels if isinstance(k, Sum) else [k])
+        if not flat:
+            raise ValueError("Sum needs at least one component kernel")
+        for k in flat:
+            if isinstance(k, SeparateIndependent):
+                raise ValueError(f"a Sum component must be a single-output stationary kernel, got the multi-output {type(k).__name__}")
+            if not isinstance(k, SquaredExponential):
+                raise ValueError(f"a Sum component must be SquaredExponential, Matern32 or Matern52, got {type(k).__name__}")
+        if len(flat) > self.MAX_COMPONENTS:
+            raise ValueError(f"Sum takes at most {self.MAX_COMPONENTS} components (TSVGP_MAX_COMPONENTS), got {len(flat)}")
+        self.kernels = flat
+        self.name = name or "sum"
+
+    def __add__(self, other):
+        return Sum([self, other])
+
+    @property
+    def kinds(self):
+        return tuple(int(k.kind) for k in self.kernels)
+
+    def stamp(self):
+        """Covers every component's parameters (see ``SquaredExponential.stamp``)."""
+        return (id(self),) + tuple(k.stamp() for k in self.kernels)
+
+    def prior_variance(self) -> float:
+        """k(x, x) = sum_c variance_c as a Python float (no device read), the components added in index order."""
+        total = 0.0
+        for k in self.kernels:
+            total += k.variance.item()
+        return total
+
+    def variances(self):
+        return [k.variance.item() for k in self.kernels]
+
+    def inv_lengthscales(self, D: int, dtype=None, device=None) -> torch.Tensor:
+        """[C, D] (contiguous): one row of 1/lengthscale per component, zeros on its inactive columns.  Cached per stamp of the
+        components' lengthscales, one array per (D, dtype, device) as ``_inv_lengthscales_active``."""
+        key = tuple(k.lengthscales.stamp() + (k.lengthscales.value.data_ptr(), k.active_dims) for k in self.kernels)
+        slots = self.__dict__.setdefault("_inv_ls_slots", {})
+        slot = (D, dtype, str(device))
+        hit = slots.get(slot)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        out = torch.stack([k.inv_lengthscales(D, dtype, device) for k in self.kernels]).contiguous()
+        slots[slot] = (key, out)
+        return out
+
+    def K_diag(self, X) -> torch.Tensor:
+        out = self.kernels[0].K_diag(X)
+        for k in self.kernels[1:]:
+            out = out + k.K_diag(X)
+        return out
+
+    def K_torch(self, Z: torch.Tensor, variances, lengthscales) -> torch.Tensor:
+        """K(Z, Z) as a differentiable torch expression of (Z, the components' variances and lengthscales: one entry per
+        component each), the components added in index order."""
+        out = None
+        for k, v, ls in zip(self.kernels, variances, lengthscales):
+            Kc = k.K_torch(Z, v, ls)
+            out = Kc if out is None else out + Kc
+        return out
+
+
+def refuse_sum(kernel, where: str):
+    """``NotImplementedError`` for a ``Sum`` kernel where only a single stationary kernel is implemented."""
+    if isinstance(kernel, Sum):
+        raise NotImplementedError(f"{where} does not take a Sum kernel (a single SquaredExponential / Matern32 / Matern52 only)")
+
+
 class SeparateIndependent:
     """``gpflow.kernels.SeparateIndependent`` [ext]: P independent latent GPs, one kernel each, no mixing matrix
     (reference docs/notebooks/heteroskedastic.py:62-67).  Used with ``SharedIndependentInducingVariables``; the
@@ -94,6 +228,8 @@ class SeparateIndependent:
         self.kernels = list(kernels)
         if not self.kernels:
             raise ValueError("SeparateIndependent needs at least one kernel")
+        for k in self.kernels:
+            refuse_sum(k, type(self).__name__)
         self.name = name or "separate_independent"
 
     @property

@@ -41,7 +41,7 @@ from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import EStepStats, gaussian_g1_const, per_latent
 from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
-from ..kernels import LinearCoregionalization, SeparateIndependent, latent_kernels
+from ..kernels import LinearCoregionalization, SeparateIndependent, Sum, latent_kernels, refuse_sum
 from ..likelihoods import mapped_parameter
 from ..sites import DenseSites
 from ..util import (
@@ -252,6 +252,7 @@ class base_SVGP(abc.ABC):
         from ..pathwise import sample_functions
 
         self._refuse_lmc("sample_functions")
+        refuse_sum(self.kernel, "sample_functions")
         eng = self._sample_engine()
         P = int(self.num_latent_gps)
         if not (1 <= P <= B.MAX_BATCH):
@@ -502,8 +503,8 @@ class t_SVGP(base_SVGP):
     def _kernel_versions(self):
         # Parameter identity and the tensors' own edit counters ride along: a replaced Parameter restarts at version 0 and an
         # in-place edit of .value does not pass through assign()
-        return tuple((id(k), k.variance.stamp(), k.lengthscales.stamp())
-                     for k in latent_kernels(self.kernel, self.num_latent_gps))
+        # (a Sum's stamp covers every component's parameters)
+        return tuple(k.stamp() for k in latent_kernels(self.kernel, self.num_latent_gps))
 
     # Route gates on cond(K_uu + jitter I), per latent GP.  direct: K^-1 (sum g k k^T) K^-1 cancels two factors of K, so its
     # error grows faster than cond.  Measured against the CPU restatement of the reference at the benchmark's M = 1024, D = 8
@@ -909,7 +910,8 @@ class t_SVGP(base_SVGP):
         "likelihood_shape" (Gamma) or "likelihood_sigma" (Ordinal): the sum of d ve / d parameter comes out of the likelihood map's
         own pass}), gradients of the ELBO
         with respect to the constrained parameter values; with one kernel per latent (``SeparateIndependent``) the kernel
-        entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales".  With ``LinearCoregionalization`` also "W" [P, L]:
+        entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales"; with a ``Sum`` kernel, per component,
+        "components.<c>.variance" / "components.<c>.lengthscales" (one ``tsvgp_kernel_grad`` launch per component on the same U).  With ``LinearCoregionalization`` also "W" [P, L]:
         with the sites fixed W enters through the mix alone, d ELBO / d W[p, l] = scale sum_n (g0_f[n, p] mean_g[n, l] +
         2 W[p, l] g1_f[n, p] var_g[n, l]), the block sums of the un-mix launch.  With more than one rank ``data`` is this
         rank's shard."""
@@ -923,9 +925,13 @@ class t_SVGP(base_SVGP):
         gaussian = self.likelihood.lik_id == B.LIK_GAUSSIAN
         kernels = list(self.kernel.kernels) if sep else [self.kernel]
         nk = len(kernels)
+        # A Sum is ONE kernel for the N-pass (one fused fill) and C parameter sets for the gradient: the contraction is linear in
+        # dK and V does not depend on the kernel, so every component takes its own tsvgp_kernel_grad launch on the same U
+        comps = list(self.kernel.kernels) if isinstance(self.kernel, Sum) else None
+        ng = nk if comps is None else len(comps)  # parameter sets (variance, lengthscales)
         Q = Dm.transpose(-1, -2) @ Dm  # [P, M, M]
-        dvar = torch.zeros(nk, dtype=torch.float64, device=self.device)
-        dls = torch.zeros((nk, Dn), dtype=torch.float64, device=self.device)
+        dvar = torch.zeros(ng, dtype=torch.float64, device=self.device)
+        dls = torch.zeros((ng, Dn), dtype=torch.float64, device=self.device)
         dZ = torch.zeros((M, Dn), dtype=torch.float64, device=self.device)
         sum_g1 = torch.zeros(nk, dtype=torch.float64, device=self.device)
         res = torch.zeros((), dtype=torch.float64, device=self.device)
@@ -971,18 +977,20 @@ class t_SVGP(base_SVGP):
                 if tile_path:
                     # U[n, m] = sum_{i <= m} t[n, i] D[i, m]: the lower-form product with D^T
                     eng.trmm(st.tile, eng._pad_square(Dm[p_].transpose(-1, -2).contiguous(), Kfu.shape[1], "pad_Dt"), Ubuf, B.TRI_LOWER)
-                    v, l, z = eng.kernel_grad(X, ops["Z"], kern, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
-                    dvar[ki] += v
-                    dls[ki] += l
-                    dZ += z
+                    for gi, kc in enumerate([kern] if comps is None else comps, 0 if comps is not None else ki):
+                        v, l, z = eng.kernel_grad(X, ops["Z"], kc, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
+                        dvar[gi] += v
+                        dls[gi] += l
+                        dZ += z
                     continue
                 # U = K_fu Q_p: a plain dense GEMM, so it goes to the BLAS library (rocBLAS DGEMM holds 0.95 of the fp64 MFMA
                 # peak at this shape, tools/dgemm_ref.py: 28.1 ms at N = 1e6, M = 1024 against 33.8 for tsvgp_trmm's dense mode)
                 torch.mm(Kfu, eng._pad_square(0.5 * (Q[p_] + Q[p_].T), Kfu.shape[1], "pad_Q"), out=Ubuf)
-                v, l, z = eng.kernel_grad(X, ops["Z"], kern, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
-                dvar[ki] += v
-                dls[ki] += l
-                dZ += z
+                for gi, kc in enumerate([kern] if comps is None else comps, 0 if comps is not None else ki):
+                    v, l, z = eng.kernel_grad(X, ops["Z"], kc, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
+                    dvar[gi] += v
+                    dls[gi] += l
+                    dZ += z
             sum_g1[ki] = g1.sum(dtype=torch.float64)
             if gaussian and not lmc:  # d ve / d s2 = -1/(2 s2) + ((y - m)^2 + v) / (2 s2^2), summed
                 res = res + torch.sum((Y[:, sl].to(st.mean.dtype) - st.mean) ** 2 + st.var)
@@ -1006,8 +1014,8 @@ class t_SVGP(base_SVGP):
         extra = torch.cat([dvar, dls.reshape(-1), dZ.reshape(-1), sum_g1, res.reshape(1), dW])
         acc2, acc1, ve_sum, nonpos, rows, tail = D_.reduce_stats(st, P, M, True, self._reduce(), eng, extra=extra)
         o = 0
-        dvar, o = tail[o:o + nk], o + nk
-        dls, o = tail[o:o + nk * Dn].reshape(nk, Dn), o + nk * Dn
+        dvar, o = tail[o:o + ng], o + ng
+        dls, o = tail[o:o + ng * Dn].reshape(ng, Dn), o + ng * Dn
         dZ, o = tail[o:o + M * Dn].reshape(M, Dn), o + M * Dn
         sum_g1, o = tail[o:o + nk], o + nk
         res, o = tail[o], o + 1
@@ -1023,14 +1031,21 @@ class t_SVGP(base_SVGP):
         # only through the elementwise K(Z, Z; theta) (round 5; the factorisation and the triangular solve used to sit inside the
         # autograd graph: ~4.5 ms of rocSOLVER / rocBLAS launches per evaluation, forward and backward).  TSVGP_MSTEP_AUTOGRAD=1: that
         # form, kept as the cross-check of tests/test_gpu_mstep.py.
-        var_t = [k.variance.value.detach().to(self.device).clone().requires_grad_(True) for k in kernels]
-        ls_t = [k.lengthscales.value.detach().to(self.device).clone().requires_grad_(True) for k in kernels]
+        owners = kernels if comps is None else comps  # whose (variance, lengthscales) the gradient is taken for
+        var_t = [k.variance.value.detach().to(self.device).clone().requires_grad_(True) for k in owners]
+        ls_t = [k.lengthscales.value.detach().to(self.device).clone().requires_grad_(True) for k in owners]
+        if comps is None:
+            k_torch = lambda: torch.stack([k.K_torch(Z_t, v_, l_) for k, v_, l_ in zip(kernels, var_t, ls_t)])
+            k_nn = lambda: sum(v_ * s_ for v_, s_ in zip(var_t, sum_g1))  # sum_np g1 * k(x, x), k(x, x) = variance
+        else:
+            k_torch = lambda: self.kernel.K_torch(Z_t, var_t, ls_t)[None]
+            k_nn = lambda: sum(var_t) * sum_g1[0]  # k(x, x) = sum_c variance_c
         Z_t = self._Z().detach().clone().requires_grad_(True)
         l1, L = self.lambda_1.value.detach(), self.lambda_2_sqrt.value.detach()
         Id = ops["Id"]
         if os.environ.get("TSVGP_MSTEP_AUTOGRAD", "0") == "1":
             with torch.enable_grad():
-                K6 = torch.stack([k.K_torch(Z_t, v_, l_) for k, v_, l_ in zip(kernels, var_t, ls_t)]) + default_jitter() * Id
+                K6 = k_torch() + default_jitter() * Id
                 K6 = K6.expand(P, M, M)  # one shared kernel: the same matrix for every latent
                 W = Id + L.transpose(-1, -2) @ (K6 @ L)
                 cW = torch.linalg.cholesky(0.5 * (W + W.transpose(-1, -2)))
@@ -1040,7 +1055,7 @@ class t_SVGP(base_SVGP):
                 beta_t = l1 - torch.einsum("pmk,kp->mp", Qt, K6l)
                 kl = 0.5 * (torch.einsum("mp,pmk,kp->", beta_t, K6, beta_t) - torch.sum(Qt * K6)
                             + 2.0 * torch.sum(torch.log(torch.diagonal(cW, dim1=-2, dim2=-1))))
-                knn = sum(v_ * s_ for v_, s_ in zip(var_t, sum_g1))  # sum_np g1 * k(x, x), k(x, x) = variance
+                knn = k_nn()
                 surrogate = scale * (torch.sum(beta_t * acc1.transpose(-1, -2)) - torch.sum(Qt * acc2) + knn) - kl
                 g_all = torch.autograd.grad(surrogate, var_t + ls_t + [Z_t])
             kl = kl.detach()
@@ -1058,15 +1073,17 @@ class t_SVGP(base_SVGP):
                 G = G.sum(dim=0, keepdim=True)  # one kernel behind every latent
             kl = kl_from_dense_site(ops["K6"], l1, Dm, ops["U_W"], beta)
             with torch.enable_grad():
-                Kt = torch.stack([k.K_torch(Z_t, v_, l_) for k, v_, l_ in zip(kernels, var_t, ls_t)])
-                knn = sum(v_ * s_ for v_, s_ in zip(var_t, sum_g1))  # sum_np g1 * k(x, x), k(x, x) = variance
+                Kt = k_torch()
+                knn = k_nn()
                 g_all = torch.autograd.grad(torch.sum(G.detach() * Kt) + scale * knn, var_t + ls_t + [Z_t])
-        g_var, g_ls, g_Z = g_all[:nk], g_all[nk:2 * nk], g_all[-1]
+        g_var, g_ls, g_Z = g_all[:ng], g_all[ng:2 * ng], g_all[-1]
         grads = {"Z": g_Z + scale * dZ}
-        for ki, k in enumerate(kernels):
+        for ki, k in enumerate(owners):
             ls_shape = k.lengthscales.value.shape
             n_ls = scale * dls[ki]
-            pre = f"kernels.{ki}." if sep else ""
+            if k.active_dims is not None:  # the [D] contraction gathered to the parameter's columns (zeros elsewhere)
+                n_ls = n_ls[list(k.active_dims)]
+            pre = f"components.{ki}." if comps is not None else f"kernels.{ki}." if sep else ""
             grads[pre + "variance"] = g_var[ki] + scale * dvar[ki]
             grads[pre + "lengthscales"] = g_ls[ki] + (n_ls.sum() if len(ls_shape) == 0 else n_ls.reshape(ls_shape))
         if gaussian:

@@ -38,7 +38,7 @@ from .. import _backend as B
 from .. import distributed as D_
 from ..base import default_jitter, to_tensor
 from ..estep import EStepStats
-from ..kernels import LinearCoregionalization, SeparateIndependent
+from ..kernels import LinearCoregionalization, SeparateIndependent, refuse_sum
 from ..sites import DiagSites
 from .tsvgp import _PredictF, base_SVGP
 from .tsvgp_white import t_SVGP_white
@@ -80,6 +80,7 @@ class t_SVGP_sites(base_SVGP):
         self._cond_cache = None
         self._direct_failed = False
         self._two_product = False
+        refuse_sum(kernel, "t_SVGP_sites")
         if isinstance(kernel, LinearCoregionalization):
             raise NotImplementedError("t_SVGP_sites does not take LinearCoregionalization: mixed outputs are on t_SVGP only")
         if isinstance(kernel, SeparateIndependent):

@@ -42,7 +42,7 @@ import torch
 from .. import _backend as B
 from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import MAX_INPUT_DIM
-from ..kernels import LinearCoregionalization, SeparateIndependent
+from ..kernels import LinearCoregionalization, SeparateIndependent, refuse_sum
 from ..sites import DiagSites
 
 
@@ -56,6 +56,7 @@ class t_VGP:
         x_data, y_data = data
         if mean_function is not None:
             raise ValueError("t_VGP: only the default Zero mean function is implemented")
+        refuse_sum(kernel, "t_VGP")
         if isinstance(kernel, LinearCoregionalization):
             raise NotImplementedError("t_VGP does not take LinearCoregionalization: mixed outputs are on t_SVGP only")
         if isinstance(kernel, SeparateIndependent):

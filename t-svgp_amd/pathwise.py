@@ -35,7 +35,7 @@ import torch
 from . import _backend as B
 from .base import default_jitter
 from .estep import MAX_INPUT_DIM
-from .kernels import SeparateIndependent, latent_kernels
+from .kernels import SeparateIndependent, Sum, latent_kernels
 
 _CHI2_NORMALS = {B.KERNEL_MATERN32: 3, B.KERNEL_MATERN52: 5}  # 2 nu
 
@@ -136,7 +136,9 @@ class _Evaluate(torch.autograd.Function):
 
 def _private_copy(kernel):
     """A kernel of the same class with its own parameters: what the draw keeps of the model's kernel."""
-    return type(kernel)(variance=kernel.variance.item(), lengthscales=kernel.lengthscales.value.clone())
+    if isinstance(kernel, Sum):
+        return Sum([_private_copy(k) for k in kernel.kernels])
+    return type(kernel)(variance=kernel.variance.item(), lengthscales=kernel.lengthscales.value.clone(), active_dims=kernel.active_dims)
 
 
 def sample_functions(model, eng, num_samples, num_features, seed, draw) -> FunctionSamples:

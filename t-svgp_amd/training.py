@@ -15,6 +15,7 @@ import math
 
 import torch
 
+from .kernels import Sum
 from .likelihoods import mapped_parameter
 
 
@@ -49,7 +50,12 @@ def trainable_parameters(model) -> dict:
     reference's M-step trains; the names are those of ``t_SVGP.elbo_and_grads`` ("kernels.<p>.variance" ... with one
     kernel per latent)."""
     kern = model.kernel
-    if hasattr(kern, "kernels"):  # SeparateIndependent
+    if isinstance(kern, Sum):  # one latent GP, C parameter sets
+        out = {}
+        for c, k in enumerate(kern.kernels):
+            out[f"components.{c}.variance"] = (k.variance, 0.0)
+            out[f"components.{c}.lengthscales"] = (k.lengthscales, 0.0)
+    elif hasattr(kern, "kernels"):  # SeparateIndependent
         out = {}
         for p, k in enumerate(kern.kernels):
             out[f"kernels.{p}.variance"] = (k.variance, 0.0)
