@@ -18,8 +18,9 @@ LIB_PATH = os.path.join(CSRC, "libtsvgp_hip.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "tsvgp_hip.h")
 # one translation unit per kernel family that has been split off (the E-step's first: by far the longest compile)
 SOURCES = [os.path.join(CSRC, name) for name in ("tsvgp_kernels.hip", "tsvgp_chol.hip", "tsvgp_likmap.hip", "tsvgp_predict.hip",
-                                                 "tsvgp_select.hip", "tsvgp_kmeans.hip", "tsvgp_sumfill.hip")]
-HEADERS = [HEADER_PATH, os.path.join(CSRC, "tsvgp_chol.h"), os.path.join(CSRC, "tsvgp_device.h")]
+                                                 "tsvgp_grad.hip", "tsvgp_vgp.hip", "tsvgp_select.hip", "tsvgp_kmeans.hip",
+                                                 "tsvgp_sumfill.hip")]
+HEADERS = [HEADER_PATH] + [os.path.join(CSRC, name) for name in ("tsvgp_chol.h", "tsvgp_device.h", "tsvgp_mfma.h")]
 # per-source compiler switches: the small-matrix kernels keep their MFMA accumulators in VGPRs (the AGPR form the compiler
 # picks for a one-wave-per-SIMD kernel ran the panel kernel's dependent MFMA chains ~1.5x slower in a stamped lab build of that
 # kernel, since removed: code in git history, its other results in profiles/r05_potrf_diag_lab.txt)

@@ -1,6 +1,6 @@
 // tsvgp_chol.h -- internal interface between tsvgp_kernels.hip (the E-step's and the M x M chain's part of the C-ABI, the blocked
 // factorisation's driver) and tsvgp_chol.hip (the panel kernel of round 5).  Not part of the C-ABI: include/tsvgp_hip.h is.  What
-// the other translation units share with tsvgp_kernels.hip is in tsvgp_device.h.
+// the other translation units share with tsvgp_kernels.hip is in tsvgp_device.h and tsvgp_mfma.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,12 +1,14 @@
 // tsvgp_device.h -- what more than one translation unit of libtsvgp_hip.so uses, and nothing else: the tile constants and vector
-// types, the Gauss-Hermite tables with the Gaussian / Bernoulli map lik_eval (the moments epilogues, vgp_rows_kernel,
-// lik_map_kernel, diag_site_step_kernel), the kernel profiles k(s) and k'(s) with exp_nonpos, and launch_status.  Not part of the
-// C-ABI: include/tsvgp_hip.h is.  Everything sits in an anonymous namespace: every unit compiles its own copy and exports none of
-// it.  No __global__ function belongs here (each unit that includes the header would emit it again).
+// types, the Gauss-Hermite tables with the Gaussian / Bernoulli map lik_eval (the moments epilogues of tsvgp_kernels.hip,
+// vgp_rows_kernel of tsvgp_vgp.hip, lik_map_kernel and diag_site_step_kernel of tsvgp_likmap.hip), the kernel profiles k(s) and
+// k'(s) with exp_nonpos, and launch_status.  The MFMA wrappers and the tile product, which only the units with tile products
+// need, are in tsvgp_mfma.h.  Not part of the C-ABI: include/tsvgp_hip.h is.  Everything sits in an anonymous namespace: every unit
+// compiles its own copy and exports none of it.  No __global__ function belongs here (each unit that includes the header would
+// emit it again).
 //
 // The cached assembly of the `product_asm` fixture (tests/conftest.py) is keyed by the hash of tsvgp_kernels.hip and
-// include/tsvgp_hip.h ONLY: after an edit to this header alone (as to tsvgp_chol.h) remove tsvgp_kernels_*.s from the
-// temporary directory by hand, or the ISA lint and the register-budget test read the assembly of the previous build.
+// include/tsvgp_hip.h ONLY: after an edit to this header alone (as to tsvgp_mfma.h or tsvgp_chol.h) remove tsvgp_kernels_*.s from
+// the temporary directory by hand, or the ISA lint and the register-budget test read the assembly of the previous build.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +21,8 @@ namespace {
 
 constexpr int TILE = TSVGP_TILE;  // 128
 constexpr int NTHREADS = 256;
+constexpr int FILL_COLS = 512;  // columns per workgroup of se_fill_kernel and kgrad_kernel: two adjacent columns per thread
+constexpr int COV_XS = 33;  // X panel image: row stride in elements (D <= 32; odd: the 16 rows of a fragment column hit 16 banks)
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -200,7 +204,7 @@ __device__ __forceinline__ T kernel_profile(T s) {
     }
 }
 
-// k(s) and k'(s) together, in closed form (the comment block above kgrad_kernel, tsvgp_kernels.hip)
+// k(s) and k'(s) together, in closed form (the comment block above kgrad_kernel, tsvgp_grad.hip)
 template <int KIND, typename T>
 __device__ __forceinline__ void kernel_profile_grad(T s, T& f, T& df) {
     if constexpr (KIND == TSVGP_KERNEL_SE) {

@@ -18,9 +18,9 @@
 //                       syrk1f_kernel_cw for g1 = one number per latent, scaled once in syrk_reduce_kernel.)
 //   potrf_diag_kernel, chol_tile_kernel, trtri_level_kernel   blocked Cholesky of the M x M site matrices and the
 //                       inverse factor (latency bound; sub-blocked diagonal block, wave-tile products without LDS).
-//   kgrad_kernel        kernel-parameter gradient contraction of the M-step.  HBM bound.
-//   mvjp_kernel         input gradient of the marginal moments (predict_f under autograd): kgrad_kernel's pair term summed over
-//                       m per row, lanes along m.  One read of U = K_fu Q; VALU-issue bound as measured.
+//   gram_to_kernel_kernel   the fill for D > 32: turns the Gram block of a BLAS GEMM into K(X, Z) in place.
+//   zero_fill_kernel .. sym_pack_kernel   the small fused M x M helpers of the replicated prelude / epilogue.
+//   selftest_kernel     single-wave check of the MFMA operand and accumulator maps.
 //
 // Tiling shared by the N-sized MFMA kernels: 128x128 output tile per 256-thread workgroup; wave w owns row blocks
 // {w, 7 - w} x all eight 16-column blocks (acc[2][8]); k-chunks of 16 (32 floats in the panel kernels) staged
@@ -28,9 +28,11 @@
 // and staging hide under the other's MFMAs.  LDS images are padded so that every fragment read and every staging write
 // is bank-conflict free: [row][k] images use a row stride of 17 doubles / 34 floats, [k][row] images a k stride of 144.
 //
-// The likelihood maps that run as launches of their own (tsvgp_likmap.hip), greedy selection (tsvgp_select.hip) and the pathwise
-// draws (tsvgp_predict.hip) are translation units of their own, as tsvgp_chol.hip and tsvgp_kmeans.hip are: this file's object
-// code does not depend on them.  What they share with it is in tsvgp_device.h.
+// Everything the E-step does not launch is a translation unit of its own, as tsvgp_chol.hip and tsvgp_kmeans.hip are: the
+// likelihood maps that run as launches of their own (tsvgp_likmap.hip), greedy selection (tsvgp_select.hip), the posterior at new
+// inputs (tsvgp_predict.hip: pathwise draws, cov_kernel, mvjp_kernel), the M-step's gradient contractions (tsvgp_grad.hip) and
+// the exact model t_VGP (tsvgp_vgp.hip).  This file's object code does not depend on them.  What they share with it is in
+// tsvgp_device.h, and the MFMA wrappers with the tile product in tsvgp_mfma.h.
 
 #include <hip/hip_runtime.h>
 
@@ -43,149 +45,13 @@
 #include "tsvgp_hip.h"
 #include "tsvgp_chol.h"
 #include "tsvgp_device.h"
+#include "tsvgp_mfma.h"
 
 namespace {
 
-constexpr int KC = 16;            // k-chunk of the site-accumulation kernel ([k][row] images)
 #define TSVGP_CHOL_PRIO 3  // wave priority of the latency-bound factorisation kernels (s_setprio, 0..3)
-constexpr int LDS_KS = 144;       // [k][row] image: k stride (elements)
 constexpr int MODE_STORE = 0;
 constexpr int MODE_MOMENTS = 1;
-
-// ---------------------------------------------------------------------------------------------------------------
-// MFMA wrappers.  A operand: lane l holds A[i = l&15][k = l>>4]; B operand: lane l holds B[k = l>>4][j = l&15].
-// C/D: column = l&15 for both types; row = (l>>4) + 4*r for f64, (l>>4)*4 + r for f32 (r = register index 0..3).
-// ---------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<double> {
-    typedef v4d acc_t;
-    typedef v2d pair_t;
-    static __device__ __forceinline__ acc_t run(double a, double b, acc_t c) {
-        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
-template <>
-struct Mfma<float> {
-    typedef v4f acc_t;
-    typedef v2f pair_t;
-    static __device__ __forceinline__ acc_t run(float a, float b, acc_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) * 4 + r; }
-};
-
-// k-chunk of the panel kernels ([row][k] images): 16 doubles or 32 floats -- the same 128 bytes per row, the same 64
-// bytes staged per thread and operand, and the same MFMA time between two barriers for both types (an fp32 MFMA takes
-// half the cycles of an fp64 one; with 16-float chunks the barrier and the staging latency weigh twice as much).
-// Row stride in elements: 17 doubles / 34 floats (18 for 16-float chunks) make the fragment reads (banked modulo 32
-// dwords per group of 32 lanes) and the 8-byte staging writes conflict free.
-template <typename T>
-struct PanelK {
-    static constexpr int KC = sizeof(T) == 8 ? 16 : 32;
-    static constexpr int H = KC / 2;  // elements one thread stages per operand and chunk
-    static constexpr int RS = KC + (sizeof(T) == 8 ? 1 : 2);
-};
-
-// H consecutive elements of one row: global -> registers (16-byte loads) and registers -> LDS (8-byte stores: the rows
-// of the double image are only 8-byte aligned).
-template <typename T, int H>
-__device__ __forceinline__ void load_run(T (&r)[H], const T* __restrict__ p) {
-    if constexpr (sizeof(T) == 8) {
-#pragma unroll
-        for (int q = 0; q < H / 2; ++q) {
-            v2d v = *reinterpret_cast<const v2d*>(p + 2 * q);
-            r[2 * q] = v[0];
-            r[2 * q + 1] = v[1];
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < H / 4; ++q) {
-            v4f v = *reinterpret_cast<const v4f*>(p + 4 * q);
-            r[4 * q] = v[0];
-            r[4 * q + 1] = v[1];
-            r[4 * q + 2] = v[2];
-            r[4 * q + 3] = v[3];
-        }
-    }
-}
-template <typename T, int H>
-__device__ __forceinline__ void store_run(T* p, const T (&r)[H]) {
-    if constexpr (sizeof(T) == 8) {
-#pragma unroll
-        for (int q = 0; q < H; ++q) p[q] = r[q];
-    } else {
-#pragma unroll
-        for (int q = 0; q < H / 2; ++q) {
-            v2f v;
-            v[0] = r[2 * q];
-            v[1] = r[2 * q + 1];
-            *reinterpret_cast<v2f*>(p + 2 * q) = v;
-        }
-    }
-}
-
-// Wave w (0..3) of a workgroup owns the 16-row blocks {w, 7 - w} and ALL eight 16-column blocks of the 128x128 tile
-// (32 x 128 per wave, acc[2][8]).  Every wave therefore sees the same column structure -- the k-tile on the diagonal
-// of a triangular product skips the same (chunk, column block) pairs in all waves, with compile-time masks -- and the
-// row pairing {w, 7 - w} gives every wave 9 of its 16 accumulators on a diagonal tile of the symmetric product.
-__device__ __forceinline__ int row_block(int w, int slot) { return slot == 0 ? w : 7 - w; }
-
-// One k-chunk of MFMAs on [row][k] images: acc[s][n] += A(row block s) * B(column block n)^T.
-// MLO / MHI (compile time): bit n set = column block n takes part in the first / second half of the chunk's k-steps
-// (a 32-wide chunk spans two 16-wide k-blocks of a triangular operand; for 16-wide chunks both masks are equal).
-template <typename T, int MLO, int MHI>
-__device__ __forceinline__ void mma_chunk_rowk(typename Mfma<T>::acc_t (&acc)[2][8], const T* __restrict__ As,
-                                               const T* __restrict__ Bs, int w, int lane) {
-    constexpr int RS = PanelK<T>::RS, PKC = PanelK<T>::KC, NKS = PKC / 4;
-    const int lr = lane & 15, lk = lane >> 4;
-    const T* ap0 = As + (w * 16 + lr) * RS + lk;
-    const T* ap1 = As + ((7 - w) * 16 + lr) * RS + lk;
-    const T* bp = Bs + lr * RS + lk;
-#pragma unroll
-    for (int ks = 0; ks < PKC / 4; ++ks) {
-        const int NMASK = (ks < PKC / 8) ? MLO : MHI;
-        T a[2], b[8];
-        a[0] = ap0[ks * 4];
-        a[1] = ap1[ks * 4];
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-            if (NMASK & (1 << n)) b[n] = bp[n * 16 * RS + ks * 4];
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-            if (NMASK & (1 << n)) {
-                acc[0][n] = Mfma<T>::run(a[0], b[n], acc[0][n]);
-                acc[1][n] = Mfma<T>::run(a[1], b[n], acc[1][n]);
-            }
-    }
-}
-
-// One k-chunk (16) of MFMAs on [k][row] images.  DIAG: only accumulators with column block <= row block
-// (W = the wave index, compile time, selects the row blocks {W, 7 - W}).
-template <typename T, bool DIAG, int W>
-__device__ __forceinline__ void mma_chunk_krow(typename Mfma<T>::acc_t (&acc)[2][8], const T* __restrict__ As,
-                                               const T* __restrict__ Bs, int w, int lane) {
-    const int lr = lane & 15, lk = lane >> 4;
-    const T* ap0 = As + lk * LDS_KS + w * 16 + lr;
-    const T* ap1 = As + lk * LDS_KS + (7 - w) * 16 + lr;
-    const T* bp = Bs + lk * LDS_KS + lr;
-#pragma unroll
-    for (int ks = 0; ks < KC / 4; ++ks) {
-        T a[2], b[8];
-        a[0] = ap0[ks * 4 * LDS_KS];
-        a[1] = ap1[ks * 4 * LDS_KS];
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-            if (!DIAG || n <= 7 - W || n <= W) b[n] = bp[ks * 4 * LDS_KS + n * 16];
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            if (!DIAG || n <= W) acc[0][n] = Mfma<T>::run(a[0], b[n], acc[0][n]);
-            if (!DIAG || n <= 7 - W) acc[1][n] = Mfma<T>::run(a[1], b[n], acc[1][n]);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // se_fill_kernel: K[n, m] = variance * exp(-0.5 * sum_d ((x_nd - z_md) * inv_ls_d)^2), zero in the padding.
@@ -193,7 +59,6 @@ __device__ __forceinline__ void mma_chunk_krow(typename Mfma<T>::acc_t (&acc)[2]
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int FILL_ROWS = 64;
 constexpr int FILL_ROWS_DEFAULT = 64;
-constexpr int FILL_COLS = 512;
 
 // DT = D padded to a compile-time size (padded dimensions are zeros on both sides).  The thread's two Z columns live in
 // registers and only the X rows go through LDS (FILL_ROWS * DT elements, wave-uniform 16-byte reads), the distance loop
@@ -352,121 +217,6 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, TSV
             for (int rr = nvalid; rr < nrows; ++rr) *reinterpret_cast<vec_t*>(Kp + (int64_t)rr * ldk) = zero;
         }
         if (rb + rb_step < nrb) __syncthreads();  // Xs is rewritten by the next row block
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// kgrad_kernel: the N-sized part of d ELBO / d (variance, lengthscales, Z) for one latent GP (M-step, reference
-// experiments/uci_regression.py:159-160).  With s = sum_d s_d^2, s_d = (x_nd - z_md) / l_d and K = variance * f(s):
-//   V[n, m]  = g0[n] * beta[m] - 2 * g1[n] * U[n, m]                       (U = K_fu Q, a tsvgp_trmm product)
-//   dvar    += V * f(s)
-//   dls[d]  += V * variance * f'(s) * (-2 s_d^2 / l_d)
-//   dZ[m,d] += V * variance * f'(s) * (-2 s_d   / l_d)
-// f'(s) in closed form: SE -f/2;  Matern-3/2 -(3/2) e^-a, a = sqrt(3 s);  Matern-5/2 -(5/6)(1 + a) e^-a, a = sqrt(5 s).
-// HBM bound (one read of U).  Grid (row blocks of KG_ROWS, column tiles of FILL_COLS); thread = two columns, its dZ sums
-// stay in registers over the block's rows; per-block partials are written out and summed by the caller in a fixed order
-// (bitwise reproducible, no atomics).  DT = D padded to a compile-time size (padded dimensions contribute zeros).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int KG_ROWS = 1024;
-constexpr int KG_CHUNK = 64;
-
-template <typename T, int KIND, int DT>
-__global__ __launch_bounds__(NTHREADS) void kgrad_kernel(const T* __restrict__ X, const T* __restrict__ Z,
-                                                         const T* __restrict__ inv_ls, T variance,
-                                                         const T* __restrict__ U, int64_t ldu, const T* __restrict__ g0,
-                                                         const T* __restrict__ g1, int gstride,
-                                                         const T* __restrict__ beta, int bstride, int64_t N, int M, int D,
-                                                         double* __restrict__ zpart, double* __restrict__ lpart,
-                                                         double* __restrict__ vpart, int Mp) {
-    __shared__ T Xs[KG_CHUNK][DT];
-    __shared__ T Gs[KG_CHUNK][2];
-    __shared__ double red[NTHREADS / 64][DT + 1];
-    typedef typename Mfma<T>::pair_t pair_t;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int64_t n0 = (int64_t)blockIdx.x * KG_ROWS;
-    const int m0 = blockIdx.y * FILL_COLS + 2 * t;
-    const bool c0 = m0 < M, c1 = m0 + 1 < M;
-    T z[2][DT], il[DT];
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-        il[d] = d < D ? inv_ls[d] : T(0);
-        z[0][d] = (c0 && d < D) ? Z[(int64_t)m0 * D + d] * il[d] : T(0);
-        z[1][d] = (c1 && d < D) ? Z[(int64_t)(m0 + 1) * D + d] * il[d] : T(0);
-    }
-    const T b0 = c0 ? beta[(int64_t)m0 * bstride] : T(0), b1 = c1 ? beta[(int64_t)(m0 + 1) * bstride] : T(0);
-    double za[2][DT], la[DT], va = 0.0;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) za[0][d] = za[1][d] = la[d] = 0.0;
-    const int64_t nend = (n0 + KG_ROWS < N) ? n0 + KG_ROWS : N;
-    for (int64_t nc = n0; nc < nend; nc += KG_CHUNK) {
-        __syncthreads();
-        for (int idx = t; idx < KG_CHUNK * DT; idx += NTHREADS) {
-            const int rr = idx / DT, d = idx - rr * DT;
-            const int64_t n = nc + rr;
-            Xs[rr][d] = (n < nend && d < D) ? X[n * D + d] * inv_ls[d] : T(0);
-        }
-        if (t < KG_CHUNK) {
-            const int64_t n = nc + t;
-            Gs[t][0] = n < nend ? g0[n * gstride] : T(0);
-            Gs[t][1] = n < nend ? g1[n * gstride] : T(0);
-        }
-        __syncthreads();
-        const int nr = (int)((nend - nc < KG_CHUNK) ? nend - nc : KG_CHUNK);
-        if (c0) {
-#pragma unroll 2
-            for (int rr = 0; rr < nr; ++rr) {
-                const pair_t u = *reinterpret_cast<const pair_t*>(U + (nc + rr) * ldu + m0);
-                const T gg0 = Gs[rr][0], gg1 = Gs[rr][1];
-                T sd[2][DT], s0 = T(0), s1 = T(0);
-#pragma unroll
-                for (int d = 0; d < DT; ++d) {
-                    const T x = Xs[rr][d];
-                    sd[0][d] = x - z[0][d];
-                    sd[1][d] = x - z[1][d];
-                    s0 += sd[0][d] * sd[0][d];
-                    s1 += sd[1][d] * sd[1][d];
-                }
-                T f0, df0, f1, df1;
-                kernel_profile_grad<KIND>(s0, f0, df0);
-                kernel_profile_grad<KIND>(s1, f1, df1);
-                const T v0 = gg0 * b0 - T(2) * gg1 * u[0];
-                const T v1 = c1 ? gg0 * b1 - T(2) * gg1 * u[1] : T(0);
-                va += (double)(v0 * f0) + (double)(v1 * f1);
-                const T w0 = T(-2) * variance * v0 * df0, w1 = T(-2) * variance * v1 * df1;
-#pragma unroll
-                for (int d = 0; d < DT; ++d) {
-                    const T p0 = w0 * sd[0][d], p1 = w1 * sd[1][d];
-                    za[0][d] += (double)p0;  // times 1 / l_d below
-                    za[1][d] += (double)p1;
-                    la[d] += (double)(p0 * sd[0][d]) + (double)(p1 * sd[1][d]);
-                }
-            }
-        }
-    }
-    // dZ partials: this thread's two columns
-    const int64_t zb = ((int64_t)blockIdx.x * Mp) * DT;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-        if (c0) zpart[zb + (int64_t)m0 * DT + d] = za[0][d] * (double)il[d];
-        if (c1) zpart[zb + (int64_t)(m0 + 1) * DT + d] = za[1][d] * (double)il[d];
-    }
-    // lengthscale / variance partials: sum over the workgroup's threads
-#pragma unroll
-    for (int d = 0; d <= DT; ++d) {
-        double v = d < DT ? la[d < DT ? d : 0] * (double)il[d < DT ? d : 0] : va;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[w][d] = v;
-    }
-    __syncthreads();
-    if (t <= DT) {
-        double v = 0.0;
-        for (int u = 0; u < NTHREADS / 64; ++u) v += red[u][t];
-        const int64_t blk = (int64_t)blockIdx.x * gridDim.y + blockIdx.y;
-        if (t < DT)
-            lpart[blk * DT + t] = v;
-        else
-            vpart[blk] = v;
     }
 }
 
@@ -3347,792 +3097,6 @@ int gram_to_kernel(int kind, T* K, const T* xx, const T* zz, T variance, int64_t
     return launch_status();
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// cov_kernel: the joint predictive covariance of one latent over N test points (GPflow conditional(full_cov=True) [ext],
-// reference src/models/tsvgp.py:103-112) from the stored moments product T [Np x Mp] (row n = Tm a_n, tsvgp_trmm):
-//     C[i, j] = C[j, i] = base(i, j) + sign * sum_m T[i, m] T[j, m],    base = variance * k(r(x_i, x_j))  or  C[i, j] on entry
-// a symmetric rank-Mp update with the kernel function in the epilogue.  One workgroup per 128 x 128 tile of the LOWER block
-// triangle (tile (it, jt), jt <= it, from the linear workgroup index); the k-loop is panel_kernel's dense one -- both
-// 128-row panels of T as [row][k] images, two LDS buffers, one barrier per chunk, mma_chunk_rowk -- and the epilogue
-//   * stages the two 128-row X panels (pre-scaled by inv_ls) over the operand buffers and evaluates kernel_profile on the
-//     scaled squared distance in the fill's difference form, sum_d (x~_id - x~_jd)^2 in the order of d (runtime D <= 32);
-//   * forces the padding (row or column >= N) to the identity block tsvgp_potrf_f64 asks for;
-//   * stores the tile from the accumulator layout (16 consecutive elements per row and 16 lanes), then the TRANSPOSED tile
-//     to (jt, it) through LDS in two halves of 64 columns, read back row-wise as 16-byte vectors.
-// A diagonal tile computes all of its entries but stores only those with column <= row directly and those with column > row
-// from the transposed image, so its upper part is a copy of its lower part: the matrix is symmetric bit for bit.  No atomics,
-// one workgroup per output element pair, a fixed k order: run-to-run identical.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int COV_XS = 33;  // X panel image: row stride in elements (D <= 32; odd: the 16 rows of a fragment column hit 16 banks)
-template <typename T>
-struct CovArgs {
-    const T* Tt;      // [Np x Mp]
-    const T* X;       // [N x D]
-    const T* inv_ls;  // [D]
-    T* C;             // [Np x ldc]
-    T variance, sign;
-    int64_t N, ldc;
-    int Mp, D, accumulate;
-};
-
-template <typename T, int KIND>
-__global__ __launch_bounds__(NTHREADS, 2) void cov_kernel(CovArgs<T> a) {
-    constexpr int RS = PanelK<T>::RS, KC = PanelK<T>::KC, H = PanelK<T>::H;  // KC shadows the site kernel's constant
-    constexpr int VW = 16 / sizeof(T);                    // elements per 16-byte vector
-    constexpr int TS = sizeof(T) == 8 ? 130 : 132;        // transposed half-tile image [64 columns][128 rows]: column stride
-    static_assert(2 * TILE * COV_XS <= 4 * TILE * RS && 64 * TS <= 4 * TILE * RS, "the epilogue images reuse the operand buffers");
-    __shared__ __attribute__((aligned(16))) T lds[2][2][TILE * RS];
-    typedef typename Mfma<T>::acc_t acc_t;
-    typedef typename std::conditional<sizeof(T) == 8, v2d, v4f>::type vec_t;
-
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    // tile (it, jt), jt <= it, of the lower block triangle: workgroup b = it (it + 1) / 2 + jt
-    const int bid = blockIdx.x;
-    int it = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
-    while ((it + 1) * (it + 2) / 2 <= bid) ++it;
-    while (it * (it + 1) / 2 > bid) --it;
-    const int jt = bid - it * (it + 1) / 2;
-    const bool diag = it == jt;
-    const int64_t i0 = (int64_t)it * TILE, j0 = (int64_t)jt * TILE;
-    const int Mp = a.Mp, nchunk = Mp / KC;
-    const int srow = t >> 1, skh = t & 1;  // staging role: row of the panel, which half of the k-chunk
-
-    const T* Arow = a.Tt + (i0 + srow) * Mp + skh * H;
-    const T* Brow = a.Tt + (j0 + srow) * Mp + skh * H;
-    T* const lds_wr = &lds[0][0][srow * RS + skh * H];
-    constexpr int BUF_STRIDE = 2 * TILE * RS, OP_STRIDE = TILE * RS;
-
-    acc_t acc[2][8];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int n = 0; n < 8; ++n) acc[s][n] = acc_t{0, 0, 0, 0};
-
-    T ra[H], rb[H];
-    load_run<T, H>(ra, Arow);
-    load_run<T, H>(rb, Brow);
-    store_run<T, H>(lds_wr, ra);
-    store_run<T, H>(lds_wr + OP_STRIDE, rb);
-    __syncthreads();
-    int buf = 0;
-    for (int c = 0; c < nchunk; ++c) {
-        const bool has_next = c + 1 < nchunk;
-        if (has_next) {
-            load_run<T, H>(ra, Arow + (c + 1) * KC);
-            load_run<T, H>(rb, Brow + (c + 1) * KC);
-        }
-        mma_chunk_rowk<T, 0xFF, 0xFF>(acc, &lds[buf][0][0], &lds[buf][1][0], w, lane);
-        if (has_next) {
-            store_run<T, H>(lds_wr + (buf ^ 1) * BUF_STRIDE, ra);
-            store_run<T, H>(lds_wr + (buf ^ 1) * BUF_STRIDE + OP_STRIDE, rb);
-        }
-        __syncthreads();
-        buf ^= 1;
-    }
-
-    // ---- epilogue (every wave is past its last fragment read: the operand buffers are free)
-    T* const img = &lds[0][0][0];
-    const int D = a.D;
-    if (!a.accumulate) {
-        for (int idx = t; idx < 2 * TILE * D; idx += NTHREADS) {
-            const int side = idx / (TILE * D), rem = idx - side * (TILE * D);
-            const int rr = rem / D, d = rem - rr * D;
-            const int64_t n = (side ? j0 : i0) + rr;
-            img[(side * TILE + rr) * COV_XS + d] = n < a.N ? a.X[n * D + d] * a.inv_ls[d] : T(0);
-        }
-        __syncthreads();
-    }
-    const int lr = lane & 15;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int li = row_block(w, s) * 16 + Mfma<T>::row(lane, r);
-            const int64_t gi = i0 + li;
-            T* const Cr = a.C + gi * a.ldc + j0 + lr;
-            T base[8];
-            if (a.accumulate) {
-#pragma unroll
-                for (int n = 0; n < 8; ++n) base[n] = (!diag || n * 16 + lr <= li) ? Cr[n * 16] : T(0);
-            } else {
-                T sv[8];
-#pragma unroll
-                for (int n = 0; n < 8; ++n) sv[n] = T(0);
-                const T* xi = img + li * COV_XS;
-                const T* xj = img + (TILE + lr) * COV_XS;
-                for (int d = 0; d < D; ++d) {
-                    const T x = xi[d];
-#pragma unroll
-                    for (int n = 0; n < 8; ++n) {
-                        const T dd = x - xj[n * 16 * COV_XS + d];
-                        sv[n] += dd * dd;
-                    }
-                }
-#pragma unroll
-                for (int n = 0; n < 8; ++n) base[n] = a.variance * kernel_profile<KIND>(sv[n]);
-            }
-#pragma unroll
-            for (int n = 0; n < 8; ++n) {
-                const int lj = n * 16 + lr;
-                const int64_t gj = j0 + lj;
-                T v = base[n] + a.sign * acc[s][n][r];
-                if (gi >= a.N || gj >= a.N) v = (gi == gj) ? T(1) : T(0);  // identity block in the padding
-                acc[s][n][r] = v;
-                if (!diag || lj <= li) Cr[n * 16] = v;
-            }
-        }
-
-    // ---- the mirror image: C[j0 + c, i0 + row] = tile[row, c], 64 columns c at a time through LDS
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        __syncthreads();  // the X panels (h = 0) / the first half's image (h = 1) have been read
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int li = row_block(w, s) * 16 + Mfma<T>::row(lane, r);
-#pragma unroll
-                for (int n = 0; n < 4; ++n) img[(n * 16 + lr) * TS + li] = acc[s][4 * h + n][r];
-            }
-        __syncthreads();
-        constexpr int UPR = TILE / VW;  // 16-byte units per image column (= output row)
-        for (int u = t; u < 64 * UPR; u += NTHREADS) {
-            const int c = u / UPR, q = u - c * UPR;
-            const vec_t v = *reinterpret_cast<const vec_t*>(img + c * TS + q * VW);
-            const int lj = 64 * h + c;  // output row within the mirrored tile
-            T* const dst = a.C + (j0 + lj) * a.ldc + i0 + q * VW;
-            if (!diag) {
-                *reinterpret_cast<vec_t*>(dst) = v;
-            } else {
-#pragma unroll
-                for (int e = 0; e < VW; ++e)
-                    if (q * VW + e > lj) dst[e] = v[e];
-            }
-        }
-    }
-}
-
-template <typename T>
-int cov(int kind, const T* Tt, const T* X, const T* inv_ls, T variance, T sign, T* C, int64_t N, int64_t Np, int Mp, int D,
-        int64_t ldc, int flags, void* stream) {
-    if (flags & ~TSVGP_COV_ACCUMULATE) return TSVGP_EINVAL;
-    const bool accumulate = (flags & TSVGP_COV_ACCUMULATE) != 0;
-    if (!accumulate && ((kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) || D <= 0 ||
-                        D > 32 || !X || !inv_ls))
-        return TSVGP_EINVAL;
-    if (!(sign == T(1) || sign == T(-1))) return TSVGP_EINVAL;
-    if (!Tt || !C || N <= 0 || Np < N || Np - N >= TILE || (Np % TILE) || Mp <= 0 || (Mp % TILE)) return TSVGP_EINVAL;
-    if (Np / TILE > 32768) return TSVGP_EINVAL;  // it (it + 1) / 2 in 32 bits
-    if (ldc < Np || (ldc * sizeof(T)) % 16 != 0) return TSVGP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(Tt) & 15) != 0 || (reinterpret_cast<uintptr_t>(C) & 15) != 0) return TSVGP_EINVAL;
-    CovArgs<T> a{};
-    a.Tt = Tt;
-    a.X = X;
-    a.inv_ls = inv_ls;
-    a.C = C;
-    a.variance = variance;
-    a.sign = sign;
-    a.N = N;
-    a.ldc = ldc;
-    a.Mp = Mp;
-    a.D = accumulate ? 0 : D;
-    a.accumulate = accumulate ? 1 : 0;
-    const int64_t nt = Np / TILE;
-    const dim3 grid((unsigned)(nt * (nt + 1) / 2)), block(NTHREADS);
-    if (accumulate || kind == TSVGP_KERNEL_SE)
-        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_SE>), grid, block, 0, (hipStream_t)stream, a);
-    else if (kind == TSVGP_KERNEL_MATERN32)
-        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_MATERN32>), grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((cov_kernel<T, TSVGP_KERNEL_MATERN52>), grid, block, 0, (hipStream_t)stream, a);
-    return launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// t_VGP, the exact N x N model (reference src/models/tvgp.py:72-160).  With s = sqrt|lambda_2|, y~ = lambda_1 / lambda_2 and
-// K~ = K(X, X) + jitter I the model factors B = I + s s^T * K~ = L L^T and needs K~ s L^-T and L^-1 (s y~).
-// vgp_system_kernel writes, in one launch, the stacked operand tsvgp_potrf_solve_f64 takes:
-//     rows [0, Np)        B[i, j] = [i == j] + s_i s_j K~[i, j]     lower block triangle and full diagonal tiles -- what the
-//                                                                   factorisation reads (potrf_diag_kernel drops the strict upper
-//                                                                   triangle of a diagonal block, chol_tile_kernel<1> updates the
-//                                                                   32 x 32 tiles on and below the diagonal); s_n = 0 for n >= N,
-//                                                                   so the padding is the identity block
-//     rows [Np, 2 Np)     R[n, j] = K~[n, j] s_j                    the right-hand-side rows (both triangles), zero in the padding
-//     rows [2 Np, + 128)  row 0: s_j y~_j, the other 127 rows zero
-// One workgroup per 128 x 128 tile (it, jt), jt <= it, as cov_kernel; the kernel function is evaluated once per pair, in the
-// fill's difference form sum_d (x~_id - x~_jd)^2 in the order of d on inputs pre-scaled by inv_ls (so k(i, j) == k(j, i) bit for
-// bit), and an off-diagonal tile also stores the mirror image of its R tile, 16 rows at a time through LDS.  Lane l of wave w
-// owns the columns 2 l, 2 l + 1 (16-byte stores, a wave writes one 1 KB row segment) and the rows w, w + 4, .. of a chunk.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int VS_CH = 16;          // rows of the tile per pass
-constexpr int VS_TS = VS_CH + 1;   // mirror image [128 columns][16 rows]: column stride (odd: 16 lanes of a row hit 16 banks)
-struct VgpSysArgs {
-    const double* X;       // [N x D]
-    const double* inv_ls;  // [D]
-    const double* l1;      // [>= N]
-    const double* l2;      // [>= N]
-    double* S;             // [(2 Np + 128) x lds]
-    double variance, jitter;
-    int64_t N, Np, lds;
-    int D, rows;
-};
-
-template <int KIND>
-__global__ __launch_bounds__(NTHREADS) void vgp_system_kernel(VgpSysArgs a) {
-    __shared__ double xj[TILE * COV_XS];
-    __shared__ double xi[VS_CH * COV_XS];
-    __shared__ double img[TILE * VS_TS];
-    __shared__ double sj[TILE], si[TILE];
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int bid = blockIdx.x;
-    int it = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
-    while ((it + 1) * (it + 2) / 2 <= bid) ++it;
-    while (it * (it + 1) / 2 > bid) --it;
-    const int jt = bid - it * (it + 1) / 2;
-    const bool diag = it == jt;
-    const int64_t i0 = (int64_t)it * TILE, j0 = (int64_t)jt * TILE;
-    const int D = a.D;
-
-    for (int idx = t; idx < TILE * D; idx += NTHREADS) {
-        const int rr = idx / D, d = idx - rr * D;
-        const int64_t n = j0 + rr;
-        xj[rr * COV_XS + d] = n < a.N ? a.X[n * D + d] * a.inv_ls[d] : 0.0;
-    }
-    {
-        const int r = t & (TILE - 1);
-        const int64_t n = (t < TILE ? j0 : i0) + r;
-        (t < TILE ? sj : si)[r] = n < a.N ? sqrt(fabs(a.l2[n])) : 0.0;
-    }
-    __syncthreads();
-    const int c = 2 * lane;
-    const int64_t gj = j0 + c;
-    const double sj0 = sj[c], sj1 = sj[c + 1];
-    double* const Bm = a.S;
-    double* const Rm = a.S + a.Np * a.lds;
-
-    for (int ch = 0; ch < TILE / VS_CH; ++ch) {
-        if (ch) __syncthreads();  // the previous pass has read its rows and its image
-        for (int idx = t; idx < VS_CH * D; idx += NTHREADS) {
-            const int rr = idx / D, d = idx - rr * D;
-            const int64_t n = i0 + ch * VS_CH + rr;
-            xi[rr * COV_XS + d] = n < a.N ? a.X[n * D + d] * a.inv_ls[d] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < VS_CH / 4; ++k) {
-            const int lr = w + 4 * k, li = ch * VS_CH + lr;
-            const int64_t gi = i0 + li;
-            double s0 = 0.0, s1 = 0.0;
-            for (int d = 0; d < D; ++d) {
-                const double x = xi[lr * COV_XS + d];
-                const double d0 = x - xj[c * COV_XS + d], d1 = x - xj[(c + 1) * COV_XS + d];
-                s0 += d0 * d0;
-                s1 += d1 * d1;
-            }
-            double k0 = a.variance * kernel_profile<KIND>(s0), k1 = a.variance * kernel_profile<KIND>(s1);
-            if (gi == gj) k0 += a.jitter;
-            if (gi == gj + 1) k1 += a.jitter;
-            if (gi >= a.N || gj >= a.N) k0 = 0.0;
-            if (gi >= a.N || gj + 1 >= a.N) k1 = 0.0;
-            const double sr = si[li];
-            v2d b;
-            b[0] = (gi == gj ? 1.0 : 0.0) + sr * sj0 * k0;
-            b[1] = (gi == gj + 1 ? 1.0 : 0.0) + sr * sj1 * k1;
-            *reinterpret_cast<v2d*>(Bm + gi * a.lds + gj) = b;
-            if (a.rows) {
-                v2d r;
-                r[0] = k0 * sj0;
-                r[1] = k1 * sj1;
-                *reinterpret_cast<v2d*>(Rm + gi * a.lds + gj) = r;
-                if (!diag) {
-                    img[c * VS_TS + lr] = k0;
-                    img[(c + 1) * VS_TS + lr] = k1;
-                }
-            }
-        }
-        if (a.rows && !diag) {  // R[j0 + lj, i0 + 16 ch + e] = K~[i, j] s_i: 128 rows of 16 columns
-            __syncthreads();
-            for (int u = t; u < TILE * VS_CH / 2; u += NTHREADS) {
-                const int lj = u >> 3, e = (u & 7) * 2;
-                v2d v;
-                v[0] = img[lj * VS_TS + e] * si[ch * VS_CH + e];
-                v[1] = img[lj * VS_TS + e + 1] * si[ch * VS_CH + e + 1];
-                *reinterpret_cast<v2d*>(Rm + (j0 + lj) * a.lds + i0 + ch * VS_CH + e) = v;
-            }
-        }
-    }
-    if (a.rows && diag) {  // the row s * y~ and the 127 zero rows below it, this tile's 128 columns
-        double* const rrow = a.S + 2 * a.Np * a.lds + j0;
-        for (int u = t; u < TILE * TILE / 2; u += NTHREADS) {
-            const int r = u >> 6, e = (u & 63) * 2;
-            v2d v{0.0, 0.0};
-            if (r == 0) {
-                if (j0 + e < a.N) v[0] = sj[e] * (a.l1[j0 + e] / a.l2[j0 + e]);
-                if (j0 + e + 1 < a.N) v[1] = sj[e + 1] * (a.l1[j0 + e + 1] / a.l2[j0 + e + 1]);
-            }
-            *reinterpret_cast<v2d*>(rrow + (int64_t)r * a.lds + e) = v;
-        }
-    }
-}
-
-int vgp_system(int kind, const double* X, const double* inv_ls, double variance, double jitter, const double* l1, const double* l2,
-               double* S, int64_t N, int64_t Np, int D, int64_t lds, int flags, void* stream) {
-    if (flags & ~TSVGP_VGP_NO_ROWS) return TSVGP_EINVAL;
-    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
-    if (!X || !inv_ls || !l1 || !l2 || !S || N <= 0 || D <= 0 || D > 32) return TSVGP_EINVAL;
-    if (Np < N || Np - N >= TILE || (Np % TILE) || Np / TILE > 32768) return TSVGP_EINVAL;
-    if (lds < Np || (lds % 2) != 0 || (reinterpret_cast<uintptr_t>(S) & 15) != 0) return TSVGP_EINVAL;
-    if (!(jitter >= 0.0)) return TSVGP_EINVAL;
-    VgpSysArgs a{};
-    a.X = X;
-    a.inv_ls = inv_ls;
-    a.l1 = l1;
-    a.l2 = l2;
-    a.S = S;
-    a.variance = variance;
-    a.jitter = jitter;
-    a.N = N;
-    a.Np = Np;
-    a.lds = lds;
-    a.D = D;
-    a.rows = (flags & TSVGP_VGP_NO_ROWS) ? 0 : 1;
-    const int64_t nt = Np / TILE;
-    const dim3 grid((unsigned)(nt * (nt + 1) / 2)), block(NTHREADS);
-    if (kind == TSVGP_KERNEL_SE)
-        hipLaunchKernelGGL((vgp_system_kernel<TSVGP_KERNEL_SE>), grid, block, 0, (hipStream_t)stream, a);
-    else if (kind == TSVGP_KERNEL_MATERN32)
-        hipLaunchKernelGGL((vgp_system_kernel<TSVGP_KERNEL_MATERN32>), grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((vgp_system_kernel<TSVGP_KERNEL_MATERN52>), grid, block, 0, (hipStream_t)stream, a);
-    return launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// vgp_rows_kernel: the sweep over the solved rows C = R L^-T [. x ldc] behind the factorisation (reference
-// src/models/tvgp.py:135-157): per row n < N
-//     q = sum_{i < K} C[n, i]^2,   mean = sum_i C[n, i] z[i],   var = kdiag - q,
-// then the likelihood map (never cropped), ve and E_q log t = -1/2 lambda_2 ((y~ - mean)^2 + var) of the OLD sites into
-// per-128-row partials, and the site update in place (beta = 0: no store at all).  HBM bound: C is read once.  One workgroup
-// per 128 rows; a wave takes 32 of them, eight at a time, lane l the element pairs 2 l + 128 k (16-byte loads, a wave reads 1 KB
-// of a row per instruction) with the pair of z loaded once for the eight rows; the lane sums are folded by a butterfly, so the
-// order of every sum is fixed by the shape alone.  The epilogue is diag_site_step_kernel's: two threads per row share the
-// Bernoulli quadrature.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int VR_ROWS = 8;  // rows a wave carries through one sweep of k
-struct VgpRowsArgs {
-    const double* C;
-    const double* z;
-    const double* Y;
-    double* l1;
-    double* l2;
-    double* mean;
-    double* var;
-    double* ve_partial;
-    double* eqt_partial;
-    int32_t* nonpos_partial;
-    double kdiag, lik_param, beta;
-    int64_t ldc, N;
-    int K, lik;
-};
-
-__global__ __launch_bounds__(NTHREADS) void vgp_rows_kernel(VgpRowsArgs a) {
-    __shared__ double qs[TILE], ms[TILE];
-    __shared__ double red[2][NTHREADS / 64];
-    __shared__ int redi[NTHREADS / 64];
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t r0 = (int64_t)blockIdx.x * TILE;
-    for (int g = 0; g < TILE / 4 / VR_ROWS; ++g) {
-        const int lrow = w * (TILE / 4) + g * VR_ROWS;
-        const double* Cr = a.C + (r0 + lrow) * a.ldc + 2 * lane;
-        double q[VR_ROWS], m[VR_ROWS];
-#pragma unroll
-        for (int r = 0; r < VR_ROWS; ++r) q[r] = m[r] = 0.0;
-        for (int k = 2 * lane; k < a.K; k += 128) {
-            v2d zz{0.0, 0.0};
-            if (a.z) zz = *reinterpret_cast<const v2d*>(a.z + k);
-            v2d cv[VR_ROWS];
-#pragma unroll
-            for (int r = 0; r < VR_ROWS; ++r) cv[r] = *reinterpret_cast<const v2d*>(Cr + r * a.ldc);
-#pragma unroll
-            for (int r = 0; r < VR_ROWS; ++r) {
-                q[r] = fma(cv[r][0], cv[r][0], q[r]);
-                q[r] = fma(cv[r][1], cv[r][1], q[r]);
-                m[r] = fma(cv[r][0], zz[0], m[r]);
-                m[r] = fma(cv[r][1], zz[1], m[r]);
-            }
-            Cr += 128;
-        }
-#pragma unroll
-        for (int r = 0; r < VR_ROWS; ++r) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                q[r] += __shfl_xor(q[r], o);
-                m[r] += __shfl_xor(m[r], o);
-            }
-            if (lane == 0) {
-                qs[lrow + r] = q[r];
-                ms[lrow + r] = m[r];
-            }
-        }
-    }
-    __syncthreads();
-
-    const int srow = t >> 1, skh = t & 1;
-    const int64_t n = r0 + srow;
-    const bool live = n < a.N;
-    const double mu = (live && a.z) ? ms[srow] : 0.0;
-    const double v = live ? a.kdiag - qs[srow] : 1.0;
-    double ve_acc = 0.0, eqt_acc = 0.0;
-    int nonpos = 0;
-    if (a.lik == TSVGP_LIK_NONE) {
-        if (live && skh == 0 && (!(v > 0.0) || !(fabs(mu) <= 1.79769313486231570815e308))) nonpos = 1;
-    } else {
-        double g0 = 0.0, g1 = 0.0, ve = 0.0;
-        if (a.lik == TSVGP_LIK_BERNOULLI) {
-            double a0, a1, av;
-            const double sd = sqrt(v);
-            bern_sums_t<double>(mu, sd, live && a.Y[live ? n : 0] == 1.0, skh * 5, skh * 5 + 5, a0, a1, av);
-            a0 += __shfl_xor(a0, 1);
-            a1 += __shfl_xor(a1, 1);
-            av += __shfl_xor(av, 1);
-            g0 = a0;
-            g1 = a1 / (2.0 * sd);
-            ve = av;
-        } else if (live) {
-            lik_eval(TSVGP_LIK_GAUSSIAN | TSVGP_LIK_NOCROP, a.lik_param, mu, v, a.Y[n], g0, g1, ve);
-        }
-        if (live && skh == 0) {
-            const double o1 = a.l1[n], o2 = a.l2[n];
-            const double dy = o1 / o2 - mu;
-            ve_acc = ve;
-            eqt_acc = -0.5 * o2 * (dy * dy + v);  // tvgp.py:107
-            if (!(v > 0.0) || !(fabs(mu) <= 1.79769313486231570815e308) || !(fabs(g0) <= 1.79769313486231570815e308) ||
-                !(fabs(g1) <= 1.79769313486231570815e308))
-                nonpos = 1;
-            if (a.beta != 0.0) {
-                a.l1[n] = (1.0 - a.beta) * o1 + a.beta * (g0 - 2.0 * g1 * mu);  // tvgp.py:156
-                a.l2[n] = (1.0 - a.beta) * o2 + a.beta * (-2.0 * g1);           // tvgp.py:157
-            }
-        }
-    }
-    if (live && skh == 0) {
-        if (a.mean) a.mean[n] = mu;
-        if (a.var) a.var[n] = v;
-    }
-    double s = ve_acc, e = eqt_acc;
-    int c = nonpos;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o);
-        e += __shfl_xor(e, o);
-        c += __shfl_xor(c, o);
-    }
-    if (lane == 0) {
-        red[0][w] = s;
-        red[1][w] = e;
-        redi[w] = c;
-    }
-    __syncthreads();
-    if (t == 0) {
-        if (a.ve_partial) a.ve_partial[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        if (a.eqt_partial) a.eqt_partial[blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        a.nonpos_partial[blockIdx.x] = redi[0] + redi[1] + redi[2] + redi[3];
-    }
-}
-
-int vgp_rows(const double* C, int64_t ldc, const double* z, const double* Y, double* l1, double* l2, double kdiag, int lik,
-             double lik_param, double beta, double* mean, double* var, double* ve_partial, double* eqt_partial,
-             int32_t* nonpos_partial, int64_t N, int64_t Np, int K, void* stream) {
-    if (!C || !nonpos_partial || N <= 0 || Np < N || Np - N >= TILE || (Np % TILE) || K <= 0 || (K % 2) != 0) return TSVGP_EINVAL;
-    if (ldc < K || (ldc % 2) != 0 || (reinterpret_cast<uintptr_t>(C) & 15) != 0 || (reinterpret_cast<uintptr_t>(z) & 15) != 0)
-        return TSVGP_EINVAL;
-    if (lik != TSVGP_LIK_NONE && lik != TSVGP_LIK_GAUSSIAN && lik != TSVGP_LIK_BERNOULLI) return TSVGP_EINVAL;
-    if (lik == TSVGP_LIK_NONE) {
-        if (!mean && !var) return TSVGP_EINVAL;
-    } else {
-        if (!z || !Y || !l1 || !l2 || !ve_partial || !eqt_partial || !(beta >= 0.0 && beta <= 1.0)) return TSVGP_EINVAL;
-        if (lik == TSVGP_LIK_GAUSSIAN && !(lik_param > 0.0)) return TSVGP_EINVAL;
-    }
-    VgpRowsArgs a{};
-    a.C = C;
-    a.z = z;
-    a.Y = Y;
-    a.l1 = l1;
-    a.l2 = l2;
-    a.mean = mean;
-    a.var = var;
-    a.ve_partial = ve_partial;
-    a.eqt_partial = eqt_partial;
-    a.nonpos_partial = nonpos_partial;
-    a.kdiag = kdiag;
-    a.lik_param = lik_param;
-    a.beta = beta;
-    a.ldc = ldc;
-    a.N = N;
-    a.K = K;
-    a.lik = lik;
-    hipLaunchKernelGGL(vgp_rows_kernel, dim3((unsigned)(Np / TILE)), dim3(NTHREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// vgp_kgrad_kernel: the N x N contraction behind d ELBO / d (variance, lengthscales) of t_VGP (models/tvgp.py: elbo_and_grads).
-// With G[i, j] = W[i, j] + 1/2 (a_i c_j + c_i a_j) symmetric, x~ = X / lengthscales, s = |x~_i - x~_j|^2 and K = variance f(s):
-//     part[tile][0]     = weight * sum_{i, j in tile} G[i, j] f(s)                                      (dK / d variance = f)
-//     part[tile][1 + d] = weight * sum_{i, j in tile} G[i, j] variance f'(s) (-2) (x~_id - x~_jd)^2     (= l_d dK / d l_d)
-// over the tiles of the lower block triangle, weight = 2 off the diagonal (G and K are symmetric; only the tiles vgp_system_kernel
-// writes are read), f and f' from kernel_profile_grad as kgrad_kernel.  G is formed in registers: no N x N x D array and no second
-// N x N buffer.  HBM bound on the one read of W: lane l of wave w owns the columns 2 l, 2 l + 1 (16-byte loads, a wave reads one
-// 1 KB row segment per instruction) and the rows w, w + 4, ..; the column panel of x~ sits in LDS, the row's x~ is a wave-uniform
-// LDS read.  A pair with i >= N or j >= N is masked by a select (whatever W holds there, NaN included), a, c and X are not read
-// beyond N.  Every sum has an order fixed by the shape: lane sums, a butterfly, the four waves in order; vgp_kgrad_reduce_kernel
-// then adds the tiles' partials in a fixed order (256 strided chains, a tree over them).  No atomics.
-// DT = D padded to a compile-time size (padded dimensions are zeros on both sides).
-// ---------------------------------------------------------------------------------------------------------------
-struct VgpKgradArgs {
-    const double* X;       // [N x D]
-    const double* inv_ls;  // [D]
-    const double* W;       // [Np x ldw]
-    const double* a;       // [>= N]
-    const double* c;       // [>= N]
-    double* part;          // [(ntiles + 1) x (1 + DT)]
-    double variance;
-    int64_t N, ldw;
-    int D;
-};
-
-template <int KIND, int DT>
-__global__ __launch_bounds__(NTHREADS) void vgp_kgrad_kernel(VgpKgradArgs a) {
-    constexpr int XS = DT + 1;  // odd row stride (DT >= 2): a wave's 64 column reads spread over the banks
-    constexpr int VG_CH = 64;   // rows of x~ staged per pass (with DT = 32 the two full panels would not fit 64 KB of LDS)
-    __shared__ double xj[TILE * XS];
-    __shared__ double xi[VG_CH * DT];  // wave-uniform reads: no padding needed
-    __shared__ double aj[TILE], cj[TILE], ai[TILE], ci[TILE];
-    __shared__ double red[NTHREADS / 64][DT + 1];
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int bid = blockIdx.x;
-    int it = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
-    while ((it + 1) * (it + 2) / 2 <= bid) ++it;
-    while (it * (it + 1) / 2 > bid) --it;
-    const int jt = bid - it * (it + 1) / 2;
-    const int64_t i0 = (int64_t)it * TILE, j0 = (int64_t)jt * TILE;
-    const int D = a.D;
-
-    for (int idx = t; idx < TILE * DT; idx += NTHREADS) {
-        const int rr = idx / DT, d = idx - rr * DT;
-        const int64_t nj = j0 + rr;
-        xj[rr * XS + d] = (d < D && nj < a.N) ? a.X[nj * D + d] * a.inv_ls[d] : 0.0;
-    }
-    if (t < TILE) {
-        const int64_t nj = j0 + t, ni = i0 + t;
-        aj[t] = nj < a.N ? a.a[nj] : 0.0;
-        cj[t] = nj < a.N ? a.c[nj] : 0.0;
-        ai[t] = ni < a.N ? a.a[ni] : 0.0;
-        ci[t] = ni < a.N ? a.c[ni] : 0.0;
-    }
-    __syncthreads();
-
-    const int c = 2 * lane;
-    const int64_t gj = j0 + c;
-    const bool live0 = gj < a.N, live1 = gj + 1 < a.N;
-    const double a0 = aj[c], a1 = aj[c + 1], c0 = cj[c], c1 = cj[c + 1];
-    double acc[DT + 1];
-#pragma unroll
-    for (int d = 0; d <= DT; ++d) acc[d] = 0.0;
-    const double m2v = -2.0 * a.variance;
-
-    for (int ch = 0; ch < TILE / VG_CH; ++ch) {
-        if (ch) __syncthreads();  // the previous pass has read its rows
-        for (int idx = t; idx < VG_CH * DT; idx += NTHREADS) {
-            const int rr = idx / DT, d = idx - rr * DT;
-            const int64_t ni = i0 + ch * VG_CH + rr;
-            xi[idx] = (d < D && ni < a.N) ? a.X[ni * D + d] * a.inv_ls[d] : 0.0;
-        }
-        __syncthreads();
-        for (int lr = w; lr < VG_CH; lr += 4) {
-            const int li = ch * VG_CH + lr;
-            const int64_t gi = i0 + li;
-            if (gi >= a.N) break;  // wave-uniform (the rows of a wave ascend); no barrier inside this loop
-            const v2d wv = *reinterpret_cast<const v2d*>(a.W + gi * a.ldw + gj);
-            const double ar = ai[li], cr = ci[li];
-            const double g0 = live0 ? wv[0] + 0.5 * (ar * c0 + cr * a0) : 0.0;
-            const double g1 = live1 ? wv[1] + 0.5 * (ar * c1 + cr * a1) : 0.0;
-            double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DT; ++d) {
-                const double x = xi[lr * DT + d];
-                const double d0 = x - xj[c * XS + d], d1 = x - xj[(c + 1) * XS + d];
-                s0 += d0 * d0;
-                s1 += d1 * d1;
-            }
-            double f0, df0, f1, df1;
-            kernel_profile_grad<KIND>(s0, f0, df0);
-            kernel_profile_grad<KIND>(s1, f1, df1);
-            acc[0] += g0 * f0 + g1 * f1;
-            const double q0 = g0 * m2v * df0, q1 = g1 * m2v * df1;
-#pragma unroll
-            for (int d = 0; d < DT; ++d) {
-                const double x = xi[lr * DT + d];
-                const double d0 = x - xj[c * XS + d], d1 = x - xj[(c + 1) * XS + d];
-                acc[1 + d] += q0 * (d0 * d0) + q1 * (d1 * d1);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 0; d <= DT; ++d) {
-        double v = acc[d];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[w][d] = v;
-    }
-    __syncthreads();
-    if (t <= DT) {
-        const double v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-        a.part[(int64_t)bid * (DT + 1) + t] = (it == jt ? 1.0 : 2.0) * v;
-    }
-}
-
-// the totals of the tiles' partials, row ntiles of part: one workgroup per column, thread t the tiles t, t + 256, .. in order
-__global__ __launch_bounds__(NTHREADS) void vgp_kgrad_reduce_kernel(double* part, int64_t ntiles, int cols) {
-    __shared__ double red[NTHREADS];
-    const int t = threadIdx.x, col = blockIdx.x;
-    double v = 0.0;
-    for (int64_t k = t; k < ntiles; k += NTHREADS) v += part[k * cols + col];
-    red[t] = v;
-    __syncthreads();
-    for (int o = NTHREADS / 2; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) part[ntiles * cols + col] = red[0];
-}
-
-inline int vgp_kgrad_dpad(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
-template <int KIND>
-void vgp_kgrad_launch(const VgpKgradArgs& a, int DT, dim3 grid, hipStream_t st) {
-    const dim3 block(NTHREADS);
-    switch (DT) {
-        case 1: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 1>), grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 2>), grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 4>), grid, block, 0, st, a); break;
-        case 8: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 8>), grid, block, 0, st, a); break;
-        case 16: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 16>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((vgp_kgrad_kernel<KIND, 32>), grid, block, 0, st, a); break;
-    }
-}
-
-int vgp_kernel_grad(int kind, const double* X, const double* inv_ls, double variance, const double* W, int64_t ldw, const double* av,
-                    const double* cv, int64_t N, int64_t Np, int D, double* part, void* stream) {
-    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
-    if (!X || !inv_ls || !W || !av || !cv || !part || N <= 0 || D <= 0 || D > 32) return TSVGP_EINVAL;
-    if (Np < N || Np - N >= TILE || (Np % TILE) || Np / TILE > 32768) return TSVGP_EINVAL;
-    if (ldw < Np || (ldw % 2) != 0 || (reinterpret_cast<uintptr_t>(W) & 15) != 0) return TSVGP_EINVAL;
-    VgpKgradArgs a{};
-    a.X = X;
-    a.inv_ls = inv_ls;
-    a.W = W;
-    a.a = av;
-    a.c = cv;
-    a.part = part;
-    a.variance = variance;
-    a.N = N;
-    a.ldw = ldw;
-    a.D = D;
-    const int DT = vgp_kgrad_dpad(D);
-    const int64_t nt = Np / TILE, ntiles = nt * (nt + 1) / 2;
-    const dim3 grid((unsigned)ntiles);
-    hipStream_t st = (hipStream_t)stream;
-    if (kind == TSVGP_KERNEL_SE)
-        vgp_kgrad_launch<TSVGP_KERNEL_SE>(a, DT, grid, st);
-    else if (kind == TSVGP_KERNEL_MATERN32)
-        vgp_kgrad_launch<TSVGP_KERNEL_MATERN32>(a, DT, grid, st);
-    else
-        vgp_kgrad_launch<TSVGP_KERNEL_MATERN52>(a, DT, grid, st);
-    if (hipGetLastError() != hipSuccess) return TSVGP_ELAUNCH;
-    hipLaunchKernelGGL(vgp_kgrad_reduce_kernel, dim3((unsigned)(DT + 1)), dim3(NTHREADS), 0, st, part, ntiles, DT + 1);
-    return launch_status();
-}
-
-// M-step gradient for input dimensions beyond kgrad_kernel's compile-time sizes (D > 16): the contraction with dK/d(theta, Z)
-// in the same GEMM form as the fill above.  With s = |x~|^2 + |z~|^2 - 2 G (G = x~ z~^T from the BLAS library), V = g0 beta^T -
-// 2 g1 * U and W = -2 variance V * k'(s), everything N-sized that is left is
-//     d variance = sum V k(s);    W^T x~ [M, D], the row and column sums of W     (BLAS GEMM + two reductions, on the host side)
-// and dZ, d lengthscales follow in M x D (estep.kernel_grad).  This kernel turns G into W IN PLACE (padding zero) and writes
-// one partial sum of V k(s) per workgroup.  One thread per two adjacent columns, one row per blockIdx.y.
-template <typename T, int KIND>
-__global__ __launch_bounds__(NTHREADS) void gram_to_gradw_kernel(T* __restrict__ G, const T* __restrict__ xx,
-                                                                 const T* __restrict__ zz, T variance, const T* __restrict__ U,
-                                                                 int64_t ldu, const T* __restrict__ g0, const T* __restrict__ g1,
-                                                                 int gstride, const T* __restrict__ beta, int bstride, int64_t N,
-                                                                 int M, int64_t ldk, int64_t rows_pad, int cols_pad,
-                                                                 double* __restrict__ vpart) {
-    typedef typename Mfma<T>::pair_t pair_t;
-    __shared__ double red[NTHREADS / 64];
-    const int64_t n = blockIdx.y;
-    const int m = (blockIdx.x * NTHREADS + threadIdx.x) * 2;
-    double va = 0.0;
-    if (n < rows_pad && m < cols_pad) {
-        pair_t* p = reinterpret_cast<pair_t*>(G + n * ldk + m);
-        pair_t out;
-        out[0] = out[1] = T(0);
-        if (n < N) {
-            const pair_t g = *p;
-            const pair_t u = *reinterpret_cast<const pair_t*>(U + n * ldu + m);
-            const T x = xx[n], gg0 = g0[n * gstride], gg1 = g1[n * gstride];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (m + q < M) {
-                    T f, df;
-                    kernel_profile_grad<KIND>(x + zz[m + q] - T(2) * g[q], f, df);
-                    const T v = gg0 * beta[(int64_t)(m + q) * bstride] - T(2) * gg1 * u[q];
-                    va += (double)(v * f);
-                    out[q] = T(-2) * variance * v * df;
-                }
-        }
-        *p = out;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) va += __shfl_xor(va, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = va;
-    __syncthreads();
-    if (threadIdx.x == 0) vpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-template <typename T>
-int gram_to_gradw(int kind, T* G, const T* xx, const T* zz, T variance, const T* U, int64_t ldu, const T* g0, const T* g1,
-                  int gstride, const T* beta, int bstride, int64_t N, int M, int64_t ldk, double* vpart, void* stream) {
-    if (!G || !xx || !zz || !U || !g0 || !g1 || !beta || !vpart || N <= 0 || M <= 0 || gstride <= 0 || bstride <= 0 ||
-        (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52))
-        return TSVGP_EINVAL;
-    const int64_t rows_pad = (N + TILE - 1) / TILE * TILE;
-    const int cols_pad = (M + TILE - 1) / TILE * TILE;
-    if (ldk < cols_pad || (ldk % 2) != 0 || ldu < cols_pad || (ldu % 2) != 0 || rows_pad > 0x7fffffff) return TSVGP_EINVAL;
-    // a thread moves its two columns of G and of U as one vector each (m, ldk, ldu even): 16 bytes in fp64, 8 in fp32
-    if ((reinterpret_cast<uintptr_t>(G) & (2 * sizeof(T) - 1)) != 0 || (reinterpret_cast<uintptr_t>(U) & (2 * sizeof(T) - 1)) != 0)
-        return TSVGP_EINVAL;
-    const dim3 block(NTHREADS);
-    const unsigned gx = (unsigned)((cols_pad / 2 + NTHREADS - 1) / NTHREADS);
-    for (int64_t r0 = 0; r0 < rows_pad; r0 += 65535) {
-        const unsigned gy = (unsigned)((rows_pad - r0 < 65535) ? rows_pad - r0 : 65535);
-        const int64_t Nr = N - r0 > 0 ? N - r0 : 0;
-        const int64_t ro = r0 < N ? r0 : 0;  // rows past N are only zero-filled: no per-row operand is read
-#define TSVGP_G2W(KIND_)                                                                                                         \
-    hipLaunchKernelGGL((gram_to_gradw_kernel<T, KIND_>), dim3(gx, gy), block, 0, (hipStream_t)stream, G + r0 * ldk, xx + ro, zz,  \
-                       variance, U + ro * ldu, ldu, g0 + ro * gstride, g1 + ro * gstride, gstride, beta, bstride, Nr, M, ldk,      \
-                       (int64_t)gy, cols_pad, vpart + r0 * gx)
-        if (kind == TSVGP_KERNEL_SE) TSVGP_G2W(TSVGP_KERNEL_SE);
-        else if (kind == TSVGP_KERNEL_MATERN32) TSVGP_G2W(TSVGP_KERNEL_MATERN32);
-        else TSVGP_G2W(TSVGP_KERNEL_MATERN52);
-#undef TSVGP_G2W
-    }
-    return launch_status();
-}
-
 // P latents in one launch: inv_ls [P x D] (device), variance [P] (HOST: the scalars travel as kernel arguments, like the
 // single-latent entry point's `variance`), K + p * strideK.
 template <typename T>
@@ -4490,252 +3454,6 @@ int potrf(double* A, int M, int lda, int batch, int64_t stride, int* info, doubl
     return launch_status();
 }
 
-template <typename T>
-int kernel_grad(int kind, const T* X, const T* Z, const T* inv_ls, T variance, const T* U, int64_t ldu, const T* g0,
-                const T* g1, int gstride, const T* beta, int bstride, int64_t N, int M, int D, double* zpart,
-                double* lpart, double* vpart, void* stream) {
-    if (!X || !Z || !inv_ls || !U || !g0 || !g1 || !beta || !zpart || !lpart || !vpart || N <= 0 || M <= 0 || D <= 0 ||
-        D > 16 || gstride <= 0 || bstride <= 0 || (ldu % 2) != 0)
-        return TSVGP_EINVAL;
-    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
-    const int Mp = (M + TILE - 1) / TILE * TILE;
-    if (ldu < Mp) return TSVGP_EINVAL;
-    const dim3 grid((unsigned)((N + KG_ROWS - 1) / KG_ROWS), (unsigned)((Mp + FILL_COLS - 1) / FILL_COLS));
-    hipStream_t st = (hipStream_t)stream;
-    const int DT = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : 16;
-    if (hipMemsetAsync(zpart, 0, sizeof(double) * (size_t)grid.x * Mp * DT, st) != hipSuccess) return TSVGP_ELAUNCH;
-#define TSVGP_KG_LAUNCH(KIND_, DT_)                                                                                  \
-    hipLaunchKernelGGL((kgrad_kernel<T, KIND_, DT_>), grid, dim3(NTHREADS), 0, st, X, Z, inv_ls, variance, U, ldu, g0, g1, \
-                       gstride, beta, bstride, N, M, D, zpart, lpart, vpart, Mp)
-#define TSVGP_KG_DT(KIND_)                          \
-    switch (DT) {                                   \
-        case 1: TSVGP_KG_LAUNCH(KIND_, 1); break;   \
-        case 2: TSVGP_KG_LAUNCH(KIND_, 2); break;   \
-        case 4: TSVGP_KG_LAUNCH(KIND_, 4); break;   \
-        case 8: TSVGP_KG_LAUNCH(KIND_, 8); break;   \
-        default: TSVGP_KG_LAUNCH(KIND_, 16); break; \
-    }
-    if (kind == TSVGP_KERNEL_SE) {
-        TSVGP_KG_DT(TSVGP_KERNEL_SE)
-    } else if (kind == TSVGP_KERNEL_MATERN32) {
-        TSVGP_KG_DT(TSVGP_KERNEL_MATERN32)
-    } else {
-        TSVGP_KG_DT(TSVGP_KERNEL_MATERN52)
-    }
-#undef TSVGP_KG_DT
-#undef TSVGP_KG_LAUNCH
-    return launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// mvjp_kernel: the vector-Jacobian product of the marginal moments of one latent GP with respect to the rows of X
-// (tsvgp_moments_vjp_*; predict_f under torch autograd).  With mean[n] = k_n^T beta, var[n] = variance - k_n^T Q k_n,
-// k_n = K(Z, x_n), cotangents cm, cv and U = K(X, Z) Q (Q symmetric), s = sum_d s_d^2, s_d = (x_nd - z_md) / l_d, K = variance * f(s):
-//   V[n, m]   = cm[n] * beta[m] - 2 * cv[n] * U[n, m]
-//   dX[n, d] (+)= sum_m V[n, m] * variance * f'(s_nm) * 2 s_d / l_d
-// -- the dZ term of kgrad_kernel with the opposite sign, summed over m per row instead of over n per column; f' is
-// kernel_profile_grad (the Matern profiles take r = sqrt(max(s, 1e-36)): on an inducing point s_d = 0 makes the term an exact
-// zero).  HBM traffic is one read of U; measured, the launch is bound by instruction issue (4 to 8 times that read).  Lanes run along m: a lane owns 16 bytes of a row of U (two doubles, four floats), a wave
-// sweeps 64 * CPL columns at a time and carries RW rows per pass (RW * DT fp64 sums in registers: 4 rows up to DT = 2, 2 up to
-// 8, 1 beyond); at the end of a pass a halving exchange over the wave leaves each sum on one lane group (RW DT - 1 + 6 - log2(RW DT)
-// exchanges instead of 6 RW DT), which owns it from there.  A workgroup takes mvjp_rows(DT) rows.  z~ [DT][columns] (m fastest: a
-// lane's columns are one 16-byte LDS read per dimension, consecutive lanes consecutive slots) and beta are staged in LDS, x~, cm,
-// cv per 64 rows (read wave-uniformly).  A stage holds mvjp_stage_cols columns (32 KiB of z~, 1024 at most); a wider M is walked
-// stage by stage, the workgroup's rows inside each, and the rows' running sums wait in LDS (Acc) between stages -- so that what
-// is added to dX at the end is the whole sum, whatever M is.  Arithmetic in T, accumulation in fp64; no atomics; every sum's order
-// is fixed by (M, D): the lane a column falls on, the sweep order, the exchange tree, the stage order -- a row's result does not
-// depend on N, on its position or on the other rows.  DT = D padded to a compile-time size (padded dimensions are zero on both
-// sides).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int MV_SUB = 64;  // rows per stage of x~, cm, cv: 16 per wave
-constexpr int MV_STAGE_BYTES = 32768;
-
-constexpr int mvjp_rows(int DT) { return DT <= 8 ? 256 : DT == 16 ? 128 : 32; }  // rows per workgroup: 16 KiB of Acc at most
-constexpr int mvjp_rows_per_pass(int DT) { return DT <= 2 ? 4 : DT <= 8 ? 2 : 1; }
-template <typename T>
-constexpr int mvjp_stage_cols(int DT) {
-    return MV_STAGE_BYTES / (DT * (int)sizeof(T)) < 1024 ? MV_STAGE_BYTES / (DT * (int)sizeof(T)) : 1024;
-}
-constexpr int mvjp_dpad(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
-// One halving step of the exchange: of CNT sums a lane keeps the half its bit `o` selects and adds the partner's copy of it.
-template <int CNT>
-__device__ __forceinline__ void mvjp_exchange(double* a, int lane, int o) {
-    if constexpr (CNT > 1) {
-        const bool up = (lane & o) != 0;
-#pragma unroll
-        for (int i = 0; i < CNT / 2; ++i) {
-            const double send = up ? a[i] : a[i + CNT / 2];
-            const double keep = up ? a[i + CNT / 2] : a[i];
-            a[i] = keep + __shfl_xor(send, o);
-        }
-        mvjp_exchange<CNT / 2>(a, lane, o >> 1);
-    }
-}
-
-template <typename T, int KIND, int DT>
-__global__ __launch_bounds__(NTHREADS) void mvjp_kernel(const T* __restrict__ X, const T* __restrict__ Z,
-                                                        const T* __restrict__ inv_ls, T variance, const T* __restrict__ U,
-                                                        int64_t ldu, const T* __restrict__ cm, const T* __restrict__ cv,
-                                                        int cstride, const T* __restrict__ beta, int bstride, int64_t N, int M,
-                                                        int D, double* __restrict__ dX, int accumulate) {
-    // Contraction is off and the fused operations are written out: left to the compiler, the unrolled copies of the pair term (one per
-    // row of a pass and column of a lane) were fused differently, and a row's bits depended on its place in the pass.
-#pragma clang fp contract(off)
-    constexpr int CPL = 16 / (int)sizeof(T), SWEEP = 64 * CPL, RW = mvjp_rows_per_pass(DT), MC = mvjp_stage_cols<T>(DT);
-    constexpr int ROWS = mvjp_rows(DT), SUB = ROWS < MV_SUB ? ROWS : MV_SUB, WROWS = SUB / (NTHREADS / 64), NV = RW * DT;
-    constexpr int LV = NV == 32 ? 5 : NV == 16 ? 4 : NV == 8 ? 3 : 2;  // log2(NV): NV is 4, 8, 16 or 32
-    static_assert(NV == (1 << LV) && MC % SWEEP == 0 && WROWS % RW == 0 && ROWS % SUB == 0, "tiling");
-    typedef T vec_t __attribute__((ext_vector_type(CPL)));
-    __shared__ __attribute__((aligned(16))) T Zs[DT][MC];  // pre-scaled by inv_ls, zero beyond (M, D)
-    __shared__ __attribute__((aligned(16))) T Bs[MC];
-    __shared__ __attribute__((aligned(16))) T Xs[SUB][DT];  // pre-scaled by inv_ls
-    __shared__ T Cs[SUB][2];
-    __shared__ double Acc[ROWS][DT];  // the rows' sums over the stages behind (M > MC only)
-    const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t n0 = (int64_t)blockIdx.x * ROWS;
-    const int64_t nend = (n0 + ROWS < N) ? n0 + ROWS : N;
-    const T v2 = T(2) * variance;
-    for (int m0 = 0; m0 < M; m0 += MC) {
-        const int mc = M - m0 < MC ? M - m0 : MC;  // columns of this stage
-        const bool first = m0 == 0, last = m0 + MC >= M;
-        if (!first) __syncthreads();  // the previous stage has been read
-        for (int idx = t; idx < MC * DT; idx += NTHREADS) {
-            const int m = idx / DT, d = idx - m * DT;
-            Zs[d][m] = (m < mc && d < D) ? Z[(int64_t)(m0 + m) * D + d] * inv_ls[d] : T(0);
-        }
-        for (int m = t; m < MC; m += NTHREADS) Bs[m] = m < mc ? beta[(int64_t)(m0 + m) * bstride] : T(0);
-        for (int64_t nb = n0; nb < nend; nb += SUB) {
-            if (nb > n0) __syncthreads();  // the previous rows have been read
-            for (int idx = t; idx < SUB * DT; idx += NTHREADS) {
-                const int rr = idx / DT, d = idx - rr * DT;
-                const int64_t n = nb + rr;
-                Xs[rr][d] = (n < nend && d < D) ? X[n * D + d] * inv_ls[d] : T(0);
-            }
-            if (t < SUB) {
-                const int64_t n = nb + t;
-                Cs[t][0] = n < nend ? cm[n * cstride] : T(0);
-                Cs[t][1] = n < nend ? cv[n * cstride] : T(0);
-            }
-            __syncthreads();
-            for (int pr = 0; pr < WROWS; pr += RW) {
-                const int rb = w * WROWS + pr;  // the pass's first row within the rows staged
-                const int64_t nr0 = nb + rb;
-                const int nr = (int)((nend - nr0 < RW) ? nend - nr0 : RW);  // wave-uniform
-                if (nr <= 0) break;
-                double acc[NV];
-#pragma unroll
-                for (int i = 0; i < NV; ++i) acc[i] = 0.0;
-                for (int m = lane * CPL; m < mc; m += SWEEP) {
-                    vec_t u[RW];
-#pragma unroll
-                    for (int r = 0; r < RW; ++r) {
-#pragma unroll
-                        for (int c = 0; c < CPL; ++c) u[r][c] = T(0);
-                        if (r < nr) {
-                            const T* up = U + (nr0 + r) * ldu + m0 + m;
-                            if (m + CPL <= mc) {
-                                u[r] = *reinterpret_cast<const vec_t*>(up);
-                            } else {  // the last columns of an M that is no multiple of CPL: nothing beyond M is read
-#pragma unroll
-                                for (int c = 0; c < CPL; ++c)
-                                    if (m + c < mc) u[r][c] = up[c];
-                            }
-                        }
-                    }
-                    vec_t z[DT];
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) z[d] = *reinterpret_cast<const vec_t*>(&Zs[d][m]);
-                    const vec_t b = *reinterpret_cast<const vec_t*>(&Bs[m]);
-#pragma unroll
-                    for (int r = 0; r < RW; ++r) {
-                        if (r < nr) {
-                            const T gm = Cs[rb + r][0], gv = Cs[rb + r][1];
-#pragma unroll
-                            for (int c = 0; c < CPL; ++c) {
-                                T s = T(0);
-#pragma unroll
-                                for (int d = 0; d < DT; ++d) {
-                                    const T dd = Xs[rb + r][d] - z[d][c];
-                                    s = fma(dd, dd, s);
-                                }
-                                T f, df;
-                                kernel_profile_grad<KIND>(s, f, df);
-                                const T v = gm * b[c] - T(2) * gv * u[r][c];
-                                const T wgt = (m + c < mc) ? v2 * v * df : T(0);
-#pragma unroll
-                                for (int d = 0; d < DT; ++d) {
-                                    const T sd = Xs[rb + r][d] - z[d][c];  // times 1 / l_d below
-                                    if constexpr (sizeof(T) == 8)
-                                        acc[r * DT + d] = fma((double)wgt, (double)sd, acc[r * DT + d]);
-                                    else
-                                        acc[r * DT + d] += (double)(wgt * sd);
-                                }
-                            }
-                        }
-                    }
-                }
-                // sum idx = r * DT + d ends up on the lanes whose upper LV bits are idx
-                mvjp_exchange<NV>(acc, lane, 32);
-#pragma unroll
-                for (int o = 32 >> LV; o > 0; o >>= 1) acc[0] += __shfl_xor(acc[0], o);
-                if ((lane & ((64 >> LV) - 1)) == 0) {
-                    const int idx = lane >> (6 - LV), r = idx / DT, d = idx - r * DT;
-                    if (r < nr && d < D) {
-                        const int row = (int)(nr0 + r - n0);  // this wave's in every stage: no other wave touches Acc[row]
-                        double tot = acc[0];
-                        if (!first) tot += Acc[row][d];
-                        if (!last) {
-                            Acc[row][d] = tot;
-                        } else {
-                            double* const out = dX + (nr0 + r) * D + d;
-                            const double g = tot * (double)inv_ls[d];
-                            *out = accumulate ? *out + g : g;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-template <typename T>
-int moments_vjp(int kind, const T* X, const T* Z, const T* inv_ls, T variance, const T* U, int64_t ldu, const T* cm, const T* cv,
-                int cstride, const T* beta, int bstride, int64_t N, int M, int D, double* dX, int accumulate, void* stream) {
-    constexpr int CPL = 16 / (int)sizeof(T);
-    if (!X || !Z || !inv_ls || !U || !cm || !cv || !beta || !dX || N <= 0 || M <= 0 || D < 1 || D > 32 || cstride <= 0 ||
-        bstride <= 0 || ldu < M || (ldu % CPL) != 0 || ((uintptr_t)U % 16) != 0 || ((uintptr_t)dX % 8) != 0)
-        return TSVGP_EINVAL;
-    if (kind != TSVGP_KERNEL_SE && kind != TSVGP_KERNEL_MATERN32 && kind != TSVGP_KERNEL_MATERN52) return TSVGP_EINVAL;
-    const int DT = mvjp_dpad(D);
-    const int64_t blocks = (N + mvjp_rows(DT) - 1) / mvjp_rows(DT);
-    if (blocks > 0x7fffffff) return TSVGP_EINVAL;
-    const dim3 grid((unsigned)blocks);
-    hipStream_t st = (hipStream_t)stream;
-#define TSVGP_MV_LAUNCH(KIND_, DT_)                                                                                              \
-    hipLaunchKernelGGL((mvjp_kernel<T, KIND_, DT_>), grid, dim3(NTHREADS), 0, st, X, Z, inv_ls, variance, U, ldu, cm, cv, cstride, \
-                       beta, bstride, N, M, D, dX, accumulate ? 1 : 0)
-#define TSVGP_MV_DT(KIND_)                          \
-    switch (DT) {                                   \
-        case 1: TSVGP_MV_LAUNCH(KIND_, 1); break;   \
-        case 2: TSVGP_MV_LAUNCH(KIND_, 2); break;   \
-        case 4: TSVGP_MV_LAUNCH(KIND_, 4); break;   \
-        case 8: TSVGP_MV_LAUNCH(KIND_, 8); break;   \
-        case 16: TSVGP_MV_LAUNCH(KIND_, 16); break; \
-        default: TSVGP_MV_LAUNCH(KIND_, 32); break; \
-    }
-    if (kind == TSVGP_KERNEL_SE) {
-        TSVGP_MV_DT(TSVGP_KERNEL_SE)
-    } else if (kind == TSVGP_KERNEL_MATERN32) {
-        TSVGP_MV_DT(TSVGP_KERNEL_MATERN32)
-    } else {
-        TSVGP_MV_DT(TSVGP_KERNEL_MATERN52)
-    }
-#undef TSVGP_MV_DT
-#undef TSVGP_MV_LAUNCH
-    return launch_status();
-}
-
 }  // namespace
 
 extern "C" {
@@ -4780,31 +3498,6 @@ int tsvgp_gram_to_kernel_f64(int kind, double* K, const double* xx, const double
 int tsvgp_gram_to_kernel_f32(int kind, float* K, const float* xx, const float* zz, float variance, int64_t N, int M,
                              int64_t ldk, void* stream) {
     return gram_to_kernel<float>(kind, K, xx, zz, variance, N, M, ldk, stream);
-}
-int tsvgp_cov_f64(int kind, const double* T, const double* X, const double* inv_ls, double variance, double sign, double* C,
-                  int64_t N, int64_t Np, int Mp, int D, int64_t ldc, int flags, void* stream) {
-    return cov<double>(kind, T, X, inv_ls, variance, sign, C, N, Np, Mp, D, ldc, flags, stream);
-}
-int tsvgp_cov_f32(int kind, const float* T, const float* X, const float* inv_ls, float variance, float sign, float* C, int64_t N,
-                  int64_t Np, int Mp, int D, int64_t ldc, int flags, void* stream) {
-    return cov<float>(kind, T, X, inv_ls, variance, sign, C, N, Np, Mp, D, ldc, flags, stream);
-}
-// vpart: one double per workgroup = ceil(Mp / 512) * Np of them (tsvgp_gram_to_gradw_parts)
-int64_t tsvgp_gram_to_gradw_parts(int64_t N, int M) {
-    if (N <= 0 || M <= 0) return -1;
-    const int64_t rows_pad = (N + TILE - 1) / TILE * TILE;
-    const int64_t cols_pad = (M + TILE - 1) / TILE * TILE;
-    return rows_pad * ((cols_pad / 2 + NTHREADS - 1) / NTHREADS);
-}
-int tsvgp_gram_to_gradw_f64(int kind, double* G, const double* xx, const double* zz, double variance, const double* U, int64_t ldu,
-                            const double* g0, const double* g1, int gstride, const double* beta, int bstride, int64_t N, int M,
-                            int64_t ldk, double* vpart, void* stream) {
-    return gram_to_gradw<double>(kind, G, xx, zz, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, ldk, vpart, stream);
-}
-int tsvgp_gram_to_gradw_f32(int kind, float* G, const float* xx, const float* zz, float variance, const float* U, int64_t ldu,
-                            const float* g0, const float* g1, int gstride, const float* beta, int bstride, int64_t N, int M,
-                            int64_t ldk, double* vpart, void* stream) {
-    return gram_to_gradw<float>(kind, G, xx, zz, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, ldk, vpart, stream);
 }
 
 int tsvgp_trmm_f64(const double* A, const double* Tm, double* C, int64_t Np, int Mp, int mode, void* stream) {
@@ -4901,26 +3594,6 @@ int tsvgp_potrf_solve_f64(double* A, int M, int lda, int batch, int64_t stride, 
     if (rhs_rows <= 0) return TSVGP_EINVAL;
     return potrf(A, M, lda, batch, stride, info, work, flags, stream, nullptr, nullptr, nullptr, rhs_rows);
 }
-int tsvgp_vgp_system_f64(int kind, const double* X, const double* inv_ls, double variance, double jitter, const double* lambda_1,
-                         const double* lambda_2, double* S, int64_t N, int64_t Np, int D, int64_t lds, int flags, void* stream) {
-    return vgp_system(kind, X, inv_ls, variance, jitter, lambda_1, lambda_2, S, N, Np, D, lds, flags, stream);
-}
-int tsvgp_vgp_rows_f64(const double* C, int64_t ldc, const double* z, const double* Y, double* lambda_1, double* lambda_2,
-                       double kdiag, int lik, double lik_param, double beta, double* mean, double* var, double* ve_partial,
-                       double* eqt_partial, int32_t* nonpos_partial, int64_t N, int64_t Np, int K, void* stream) {
-    return vgp_rows(C, ldc, z, Y, lambda_1, lambda_2, kdiag, lik, lik_param, beta, mean, var, ve_partial, eqt_partial,
-                    nonpos_partial, N, Np, K, stream);
-}
-// part: one row of 1 + Dp doubles per tile of the lower block triangle, and one more for the totals
-int64_t tsvgp_vgp_kernel_grad_parts(int64_t Np, int D) {
-    if (Np <= 0 || (Np % TILE) || Np / TILE > 32768 || D <= 0 || D > 32) return -1;
-    const int64_t nt = Np / TILE;
-    return (nt * (nt + 1) / 2 + 1) * (1 + vgp_kgrad_dpad(D));
-}
-int tsvgp_vgp_kernel_grad_f64(int kind, const double* X, const double* inv_ls, double variance, const double* W, int64_t ldw,
-                              const double* a, const double* c, int64_t N, int64_t Np, int D, double* part, void* stream) {
-    return vgp_kernel_grad(kind, X, inv_ls, variance, W, ldw, a, c, N, Np, D, part, stream);
-}
 int tsvgp_flip_transpose_f64(const double* src, int lds, int64_t sstride, double* dst, int ldd, int64_t dstride, int M, int batch,
                              void* stream) {
     if (!src || !dst || M <= 0 || lds < M || ldd < M || batch <= 0 || batch > 65535) return TSVGP_EINVAL;
@@ -5010,34 +3683,6 @@ int tsvgp_sym_unpack_f64(const double* packed, double* A, int lda, int64_t strid
     return launch_status();
 }
 
-int tsvgp_kernel_grad_rows(void) { return KG_ROWS; }
-int tsvgp_kernel_grad_dpad(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : 16; }
-int tsvgp_kernel_grad_f64(int kind, const double* X, const double* Z, const double* inv_ls, double variance,
-                          const double* U, int64_t ldu, const double* g0, const double* g1, int gstride,
-                          const double* beta, int bstride, int64_t N, int M, int D, double* zpart, double* lpart,
-                          double* vpart, void* stream) {
-    return kernel_grad<double>(kind, X, Z, inv_ls, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, D, zpart, lpart,
-                               vpart, stream);
-}
-int tsvgp_kernel_grad_f32(int kind, const float* X, const float* Z, const float* inv_ls, float variance, const float* U,
-                          int64_t ldu, const float* g0, const float* g1, int gstride, const float* beta, int bstride,
-                          int64_t N, int M, int D, double* zpart, double* lpart, double* vpart, void* stream) {
-    return kernel_grad<float>(kind, X, Z, inv_ls, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, D, zpart, lpart,
-                              vpart, stream);
-}
-int tsvgp_moments_vjp_rows(int D) { return D < 1 || D > 32 ? -1 : mvjp_rows(mvjp_dpad(D)); }
-int tsvgp_moments_vjp_stage_f64(int D) { return D < 1 || D > 32 ? -1 : mvjp_stage_cols<double>(mvjp_dpad(D)); }
-int tsvgp_moments_vjp_stage_f32(int D) { return D < 1 || D > 32 ? -1 : mvjp_stage_cols<float>(mvjp_dpad(D)); }
-int tsvgp_moments_vjp_f64(int kind, const double* X, const double* Z, const double* inv_ls, double variance, const double* U,
-                          int64_t ldu, const double* cm, const double* cv, int cstride, const double* beta, int bstride, int64_t N,
-                          int M, int D, double* dX, int accumulate, void* stream) {
-    return moments_vjp<double>(kind, X, Z, inv_ls, variance, U, ldu, cm, cv, cstride, beta, bstride, N, M, D, dX, accumulate, stream);
-}
-int tsvgp_moments_vjp_f32(int kind, const float* X, const float* Z, const float* inv_ls, float variance, const float* U, int64_t ldu,
-                          const float* cm, const float* cv, int cstride, const float* beta, int bstride, int64_t N, int M, int D,
-                          double* dX, int accumulate, void* stream) {
-    return moments_vjp<float>(kind, X, Z, inv_ls, variance, U, ldu, cm, cv, cstride, beta, bstride, N, M, D, dX, accumulate, stream);
-}
 int tsvgp_selftest_mfma_f64(const double* a, const double* b, double* c, void* stream) {
     if (!a || !b || !c) return TSVGP_EINVAL;
     hipLaunchKernelGGL(selftest_kernel<double>, dim3(1), dim3(64), 0, (hipStream_t)stream, a, b, c);

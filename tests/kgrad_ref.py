@@ -1,5 +1,5 @@
 """NumPy fp64 restatement of the M-step gradient contraction (``tsvgp_kernel_grad_*``, ``tsvgp_gram_to_gradw_*``), written from
-the formulas alone (the comment block above ``kgrad_kernel`` in t-svgp_amd/csrc/tsvgp_kernels.hip), not from the kernels' loops.
+the formulas alone (the comment block above ``kgrad_kernel`` in t-svgp_amd/csrc/tsvgp_grad.hip), not from the kernels' loops.
 
 With x~ = X * inv_ls, z~ = Z * inv_ls, s_d = x~_nd - z~_md, s = sum_d s_d^2, K = variance * f(s):
     V[n, m]  = g0[n] beta[m] - 2 g1[n] U[n, m]

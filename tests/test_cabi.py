@@ -27,6 +27,16 @@ def test_library_builds_and_exports_every_declared_symbol(repo_root):
     assert lib.tsvgp_version().decode().startswith("tsvgp_hip gfx950")
 
 
+def test_every_source_and_header_of_csrc_is_listed_for_the_build():
+    """A ``*.hip`` missing from ``SOURCES`` is not linked; a ``*.h`` missing from ``HEADERS`` is not in ``build_library()``'s (and
+    ``tools/isa_diff.py --keep``'s) staleness check, so an edit to it would reuse the previous build."""
+    B = pkg()._backend
+    on_disk = sorted(os.listdir(B.CSRC))
+    assert sorted(os.path.basename(p) for p in B.SOURCES) == [f for f in on_disk if f.endswith(".hip")]
+    assert sorted(os.path.basename(p) for p in B.HEADERS if os.path.dirname(p) == B.CSRC) == [f for f in on_disk if f.endswith(".h")]
+    assert B.HEADER_PATH in B.HEADERS
+
+
 def test_argument_validation_needs_no_gpu():
     lib = pkg()._backend.lib()
     # null pointers / unpadded sizes are rejected before any launch

@@ -1,5 +1,5 @@
 """The Gaussian and Bernoulli gradient maps (mean, var, y) -> (g0, g1, ve) at every one of their six sites in
-``csrc/`` (``lik_eval`` of ``tsvgp_device.h``; the sites are in ``tsvgp_kernels.hip`` and ``tsvgp_likmap.hip``), entry by entry against the oracle over the whole range a fit feeds them:
+``csrc/`` (``lik_eval`` of ``tsvgp_device.h``; the sites are in ``tsvgp_kernels.hip``, ``tsvgp_likmap.hip`` and ``tsvgp_vgp.hip``), entry by entry against the oracle over the whole range a fit feeds them:
 
     panel1_kernel epilogue     tsvgp_moments_*, mode 0 / 1                  test_moments_epilogue
     panel_kernel epilogue      tsvgp_moments_*, mode 2                      test_moments_epilogue
