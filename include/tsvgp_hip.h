@@ -149,6 +149,20 @@ int tsvgp_kernel_fill_sum_f64(const int *kinds_host, const double *X, const doub
 int tsvgp_kernel_fill_sum_f32(const int *kinds_host, const float *X, const float *Z, const float *inv_ls,
                               const float *variance_host, float *K, int64_t N, int M, int D, int64_t ldk, int C, void *stream);
 
+/* (1p) The fill of a PRODUCT of C stationary kernels (gpflow.kernels.Product / k1 * k2 [ext]) on shared inputs, in ONE launch and
+ *     one write of K:
+ *        K[n, m] = variance * prod_c k_{kind[c]}(r_c),   r_c^2 = sum_d ((x_nd - z_md) * inv_ls[c*D + d])^2,
+ *     variance = prod_c variance_c formed by the caller.  The kernel of (1s) under a compile-time flag: the same device functions
+ *     for the profiles and the difference-form distance, the components multiplied in index order starting from 1, the variance
+ *     last.  inv_ls [C x D] is a device array (zeros on a component's inactive columns), kinds_host [C] a HOST array.  Everything
+ *     else as (1s): 1 <= C <= TSVGP_MAX_COMPONENTS, the reserved kind 1 refused, padding rows and columns written as exact zeros,
+ *     D <= 32, ldk even and K on a boundary of two elements (the fp32 four-column store where K is on a 16-byte boundary and ldk a
+ *     multiple of 4), non-temporal stores from 512 MB up, both register forms; TSVGP_EINVAL before any launch otherwise. */
+int tsvgp_kernel_fill_prod_f64(const int *kinds_host, const double *X, const double *Z, const double *inv_ls, double variance,
+                               double *K, int64_t N, int M, int D, int64_t ldk, int C, void *stream);
+int tsvgp_kernel_fill_prod_f32(const int *kinds_host, const float *X, const float *Z, const float *inv_ls, float variance,
+                               float *K, int64_t N, int M, int D, int64_t ldk, int C, void *stream);
+
 /* (1d) Input dimensions beyond 32 (the reference's MNIST notebook has D = 784): the scaled squared distance is then a
  *     GEMM, r2[n,m] = xx[n] + zz[m] - 2 G[n,m] with G = (X/l)(Z/l)^T (GPflow's square_distance form [ext]), which the caller
  *     takes from the BLAS library into K [rows_pad x ldk]; this call turns it into K = variance * k(r2) in place and
@@ -646,6 +660,26 @@ int tsvgp_kernel_grad_f64(int kind, const double *X, const double *Z, const doub
 int tsvgp_kernel_grad_f32(int kind, const float *X, const float *Z, const float *inv_ls, float variance, const float *U,
                           int64_t ldu, const float *g0, const float *g1, int gstride, const float *beta, int bstride,
                           int64_t N, int M, int D, double *zpart, double *lpart, double *vpart, void *stream);
+
+/* (8p) The contraction of (8) for a PRODUCT of C stationary kernels (1p), all C parameter sets in ONE pass over U.  With
+ *     K = variance * prod_c f_c(s_c), s_c = sum_d s_cd^2, s_cd = (x_nd - z_md) * inv_ls[c*D + d], V as in (8) and
+ *     P_c = prod_{c' != c} f_c'(s_c') (running prefix and suffix products, never a division by f_c):
+ *        vpart  sums V * prod_c f_c              (the caller: d / d variance_c = (variance / variance_c) * sum)
+ *        w_c  = -2 * variance * V * P_c * f_c'(s_c)
+ *        d lengthscale[c, d] = sum_{n,m} w_c s_cd^2 inv_ls[c, d],        dZ[m, d] = sum_n sum_c w_c s_cd inv_ls[c, d].
+ *     kinds_host [C] is a HOST array, inv_ls [C x D] a device array, variance the product of the components' variances.  Operands,
+ *     strides and the per-block partials as (8), with lpart [nrb x ncb x C x Dp] (component-major inside a block); fp64
+ *     accumulation, no atomics, bitwise reproducible.  D <= 16, 1 <= C <= TSVGP_MAX_COMPONENTS, ldu even and >= Mp, U on a boundary
+ *     of two elements; TSVGP_EINVAL before any launch otherwise (the reserved kind 1 included).  The kernel stages X and keeps its Z
+ *     columns unscaled and scales the difference per component, so its registers do not grow with C beyond the C x Dp sums. */
+int tsvgp_kernel_grad_prod_f64(const int *kinds_host, const double *X, const double *Z, const double *inv_ls, double variance,
+                               const double *U, int64_t ldu, const double *g0, const double *g1, int gstride,
+                               const double *beta, int bstride, int64_t N, int M, int D, int C, double *zpart, double *lpart,
+                               double *vpart, void *stream);
+int tsvgp_kernel_grad_prod_f32(const int *kinds_host, const float *X, const float *Z, const float *inv_ls, float variance,
+                               const float *U, int64_t ldu, const float *g0, const float *g1, int gstride, const float *beta,
+                               int bstride, int64_t N, int M, int D, int C, double *zpart, double *lpart, double *vpart,
+                               void *stream);
 
 /* (9) Greedy conditional-variance selection of inducing points (Burt, Rasmussen, van der Wilk 2020, "ConditionalVariance"; [ext]:
  *     nothing in the reference chooses Z): pivoted Cholesky of K(X, X) that always takes the row with the largest residual prior

@@ -9,7 +9,7 @@ from .base import Parameter, default_float, default_jitter
 from .inducing_variables import (InducingPoints, InducingSelection, KMeansInducing, KMeansSeeding,
                                  SharedIndependentInducingVariables, inducingpoint_wrapper, kmeans_inducing_points, kmeanspp_seeds,
                                  select_inducing_points)
-from .kernels import LinearCoregionalization, Matern32, Matern52, SeparateIndependent, SquaredExponential, Sum
+from .kernels import LinearCoregionalization, Matern32, Matern52, Product, SeparateIndependent, SquaredExponential, Sum
 from .likelihoods import Bernoulli, Gaussian, HeteroskedasticTFPConditional, MultiClass, Poisson, RobustMax, Softmax, StudentT
 from .likelihoods import Exponential, Gamma, Ordinal
 from .models import base_SVGP, t_SVGP, t_SVGP_sites, t_SVGP_white, t_VGP
@@ -21,7 +21,7 @@ __all__ = [
     "MultiClass", "RobustMax", "Gamma", "Exponential", "Ordinal",
     "InducingPoints", "select_inducing_points", "InducingSelection", "kmeans_inducing_points", "KMeansInducing", "kmeanspp_seeds", "KMeansSeeding",
     "FunctionSamples",
-    "SeparateIndependent", "LinearCoregionalization", "SharedIndependentInducingVariables", "Matern32", "Matern52", "Sum",
+    "SeparateIndependent", "LinearCoregionalization", "SharedIndependentInducingVariables", "Matern32", "Matern52", "Sum", "Product",
     "inducingpoint_wrapper", "Parameter", "default_float", "default_jitter", "HipExtensionError", "build_library",
     "distributed", "util", "training",
 ]

@@ -120,6 +120,10 @@ _PROTOTYPES = {
                                           c_void_p]),
     "tsvgp_kernel_fill_sum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int,
                                           c_void_p]),
+    "tsvgp_kernel_fill_prod_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int, c_int, c_int64, c_int,
+                                           c_void_p]),
+    "tsvgp_kernel_fill_prod_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int64, c_int,
+                                           c_void_p]),
     "tsvgp_gram_to_kernel_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int, c_int64, c_void_p]),
     "tsvgp_gram_to_kernel_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_int64, c_void_p]),
     "tsvgp_cov_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int64, c_int64, c_int, c_int, c_int64,
@@ -137,6 +141,10 @@ _PROTOTYPES = {
                                       c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_kernel_grad_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                       c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tsvgp_kernel_grad_prod_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tsvgp_kernel_grad_prod_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tsvgp_trmm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_trmm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "tsvgp_trmm_batched_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),

@@ -245,9 +245,261 @@ int kernel_grad(int kind, const T* X, const T* Z, const T* inv_ls, T variance, c
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// kgrad_prod_kernel: the same contraction for a PRODUCT of C stationary kernels, K = variance * prod_c f_c(s_c) with
+// variance = prod_c variance_c and s_c = sum_d s_cd^2, s_cd = (x_nd - z_md) * inv_ls[c, d] -- all C parameter sets in ONE pass
+// over U.  With V as above and P_c = prod_{c' != c} f_c'(s_c'):
+//   vsum      += V * prod_c f_c                          (d / d variance_c = (variance / variance_c) * vsum: the caller's)
+//   w_c        = -2 * variance * V * P_c * f_c'(s_c)
+//   dls[c, d] += w_c * s_cd^2 * inv_ls[c, d]
+//   dZ[m, d]  += sum_c w_c * s_cd * inv_ls[c, d]
+// P_c comes from running prefix and suffix products, never from a division by f_c (a profile can flush to zero in fp32).
+// Geometry of kgrad_kernel: KG_ROWS-row blocks, KG_CHUNK-row chunks staged in LDS, two columns per thread, one 16-byte read of U
+// per row, per-block partials (lpart [nrb x ncb x C x DT]), fp64 accumulation, no atomics.
+// What differs is how the C scalings are held.  C pre-scaled copies of the thread's Z columns would take 2 * C * DT registers
+// (256 VGPRs at C = 4, DT = 16 in fp64) beside the C * DT lengthscale sums; instead X is staged and Z is kept UNSCALED, the
+// difference x_d - z_d is formed once per row and column, and component c multiplies it by inv_ls[c, d] (read from LDS at a
+// wave-uniform address) where the pre-scaled form subtracts: one multiply for one subtract, 2 * DT registers of Z for any C.
+// The kind of a component is uniform over the launch: a scalar branch per component picks the profile.
+// ---------------------------------------------------------------------------------------------------------------
+struct ProdGradKinds {
+    int kind[TSVGP_MAX_COMPONENTS];
+};
+
+template <typename T>
+__device__ __forceinline__ void prod_profile_grad(int kind, T s, T& f, T& df) {
+    if (kind == TSVGP_KERNEL_SE) kernel_profile_grad<TSVGP_KERNEL_SE>(s, f, df);
+    else if (kind == TSVGP_KERNEL_MATERN32) kernel_profile_grad<TSVGP_KERNEL_MATERN32>(s, f, df);
+    else kernel_profile_grad<TSVGP_KERNEL_MATERN52>(s, f, df);
+}
+
+template <typename T, int DT, int C, int QS>
+__global__ __launch_bounds__(NTHREADS) void kgrad_prod_kernel(const T* __restrict__ X, const T* __restrict__ Z,
+                                                              const T* __restrict__ inv_ls, ProdGradKinds kinds, T variance,
+                                                              const T* __restrict__ U, int64_t ldu, const T* __restrict__ g0,
+                                                              const T* __restrict__ g1, int gstride,
+                                                              const T* __restrict__ beta, int bstride, int64_t N, int M, int D,
+                                                              double* __restrict__ zpart, double* __restrict__ lpart,
+                                                              double* __restrict__ vpart, int Mp) {
+    static_assert(QS == 1 || QS == 2, "columns per pass");
+    __shared__ T Xs[KG_CHUNK][DT];  // unscaled
+    __shared__ T Gs[KG_CHUNK][2];
+    __shared__ T Il[C][DT];         // inv_ls, zero in the padded dimensions
+    __shared__ double red[NTHREADS / 64][C * DT + 1];
+    typedef typename Mfma<T>::pair_t pair_t;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t n0 = (int64_t)blockIdx.x * KG_ROWS;
+    const int m0 = blockIdx.y * FILL_COLS + 2 * t;
+    if (t < C * DT) {
+        const int c = t / DT, d = t - c * DT;
+        Il[c][d] = d < D ? inv_ls[c * D + d] : T(0);
+    }
+    double la[C][DT], va = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int d = 0; d < DT; ++d) la[c][d] = 0.0;
+    const int64_t nend = (n0 + KG_ROWS < N) ? n0 + KG_ROWS : N;
+    const int64_t zb = ((int64_t)blockIdx.x * Mp) * DT;
+    // QS = 2: one pass over the block's rows on both columns; QS = 1: two passes, one column each
+#pragma unroll 1
+    for (int mq = m0; mq < m0 + 2; mq += QS) {
+        bool cv[QS];
+        T z[QS][DT], b[QS];
+        double za[QS][DT];
+#pragma unroll
+        for (int j = 0; j < QS; ++j) {
+            cv[j] = mq + j < M;
+            b[j] = cv[j] ? beta[(int64_t)(mq + j) * bstride] : T(0);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                z[j][d] = (cv[j] && d < D) ? Z[(int64_t)(mq + j) * D + d] : T(0);
+                za[j][d] = 0.0;
+            }
+        }
+        for (int64_t nc = n0; nc < nend; nc += KG_CHUNK) {
+            __syncthreads();  // (the first: Il is written)
+            for (int idx = t; idx < KG_CHUNK * DT; idx += NTHREADS) {
+                const int rr = idx / DT, d = idx - rr * DT;
+                const int64_t n = nc + rr;
+                Xs[rr][d] = (n < nend && d < D) ? X[n * D + d] : T(0);
+            }
+            if (t < KG_CHUNK) {
+                const int64_t n = nc + t;
+                Gs[t][0] = n < nend ? g0[n * gstride] : T(0);
+                Gs[t][1] = n < nend ? g1[n * gstride] : T(0);
+            }
+            __syncthreads();
+            const int nr = (int)((nend - nc < KG_CHUNK) ? nend - nc : KG_CHUNK);
+            if (cv[0]) {
+                for (int rr = 0; rr < nr; ++rr) {
+                    // Il is read from LDS where it is used, in both sweeps over the components: held in registers across the rows
+                    // (C * DT values, which the compiler hoists when left to itself) it costs what keeping Z unscaled saves
+                    asm volatile("" ::: "memory");
+                    T u[QS];
+                    if constexpr (QS == 2) {
+                        const pair_t uu = *reinterpret_cast<const pair_t*>(U + (nc + rr) * ldu + mq);
+                        u[0] = uu[0];
+                        u[1] = uu[1];
+                    } else {
+                        u[0] = U[(nc + rr) * ldu + mq];
+                    }
+                    const T gg0 = Gs[rr][0], gg1 = Gs[rr][1];
+                    T df[QS][DT];  // x_d - z_d
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) {
+                        const T x = Xs[rr][d];
+#pragma unroll
+                        for (int j = 0; j < QS; ++j) df[j][d] = x - z[j][d];
+                    }
+                    T f[C][QS], dfs[C][QS];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        T s[QS];
+#pragma unroll
+                        for (int j = 0; j < QS; ++j) s[j] = T(0);
+#pragma unroll
+                        for (int d = 0; d < DT; ++d) {
+                            const T il = Il[c][d];
+#pragma unroll
+                            for (int j = 0; j < QS; ++j) {
+                                const T a = df[j][d] * il;
+                                s[j] += a * a;
+                            }
+                        }
+#pragma unroll
+                        for (int j = 0; j < QS; ++j) prod_profile_grad(kinds.kind[c], s[j], f[c][j], dfs[c][j]);
+                    }
+                    // suf[c] = prod_{c' > c} f_c'; pre = prod_{c' < c} f_c' runs forward below: P_c = pre * suf[c]
+                    T suf[C][QS], pre[QS], q[QS];
+#pragma unroll
+                    for (int j = 0; j < QS; ++j) {
+                        suf[C - 1][j] = T(1);
+#pragma unroll
+                        for (int c = C - 2; c >= 0; --c) suf[c][j] = suf[c + 1][j] * f[c + 1][j];
+                        const T v = cv[j] ? gg0 * b[j] - T(2) * gg1 * u[j] : T(0);
+                        va += (double)(v * (f[0][j] * suf[0][j]));
+                        q[j] = T(-2) * variance * v;
+                        pre[j] = T(1);
+                    }
+                    asm volatile("" ::: "memory");
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        T wc[QS];
+#pragma unroll
+                        for (int j = 0; j < QS; ++j) {
+                            wc[j] = q[j] * (pre[j] * suf[c][j]) * dfs[c][j];
+                            pre[j] *= f[c][j];
+                        }
+#pragma unroll
+                        for (int d = 0; d < DT; ++d) {
+                            const T il = Il[c][d];
+#pragma unroll
+                            for (int j = 0; j < QS; ++j) {
+                                const T a = df[j][d] * il;
+                                const T p = wc[j] * a;
+                                za[j][d] += (double)(p * il);
+                                la[c][d] += (double)(p * a);  // times inv_ls[c, d] below
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        // dZ partials: this thread's columns
+#pragma unroll
+        for (int j = 0; j < QS; ++j)
+#pragma unroll
+            for (int d = 0; d < DT; ++d)
+                if (cv[j]) zpart[zb + (int64_t)(mq + j) * DT + d] = za[j][d];
+    }
+    // lengthscale / variance partials: sum over the workgroup's threads
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int d = 0; d < DT; ++d) {
+            double v = la[c][d] * (double)Il[c][d];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0) red[w][c * DT + d] = v;
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) va += __shfl_xor(va, o);
+    if (lane == 0) red[w][C * DT] = va;
+    __syncthreads();
+    if (t <= C * DT) {
+        double v = 0.0;
+        for (int u = 0; u < NTHREADS / 64; ++u) v += red[u][t];
+        const int64_t blk = (int64_t)blockIdx.x * gridDim.y + blockIdx.y;
+        if (t < C * DT)
+            lpart[blk * (C * DT) + t] = v;
+        else
+            vpart[blk] = v;
+    }
+}
+
+template <typename T>
+int kernel_grad_prod(const int* kinds, const T* X, const T* Z, const T* inv_ls, T variance, const T* U, int64_t ldu,
+                     const T* g0, const T* g1, int gstride, const T* beta, int bstride, int64_t N, int M, int D, int C,
+                     double* zpart, double* lpart, double* vpart, void* stream) {
+    if (!kinds || !X || !Z || !inv_ls || !U || !g0 || !g1 || !beta || !zpart || !lpart || !vpart || N <= 0 || M <= 0 || D <= 0 ||
+        D > 16 || C < 1 || C > TSVGP_MAX_COMPONENTS || gstride <= 0 || bstride <= 0 || (ldu % 2) != 0)
+        return TSVGP_EINVAL;
+    ProdGradKinds kk{};
+    for (int c = 0; c < C; ++c) {
+        if (kinds[c] != TSVGP_KERNEL_SE && kinds[c] != TSVGP_KERNEL_MATERN32 && kinds[c] != TSVGP_KERNEL_MATERN52)
+            return TSVGP_EINVAL;
+        kk.kind[c] = kinds[c];
+    }
+    const int Mp = (M + TILE - 1) / TILE * TILE;
+    // a thread reads its two columns of U as one vector (m, ldu even): 16 bytes in fp64, 8 in fp32
+    if (ldu < Mp || (reinterpret_cast<uintptr_t>(U) & (2 * sizeof(T) - 1)) != 0) return TSVGP_EINVAL;
+    const int64_t nrb = (N + KG_ROWS - 1) / KG_ROWS;
+    if (nrb > 0x7fffffff) return TSVGP_EINVAL;
+    const dim3 grid((unsigned)nrb, (unsigned)((Mp + FILL_COLS - 1) / FILL_COLS));
+    hipStream_t st = (hipStream_t)stream;
+    const int DT = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : 16;
+    if (hipMemsetAsync(zpart, 0, sizeof(double) * (size_t)grid.x * Mp * DT, st) != hipSuccess) return TSVGP_ELAUNCH;
+#define TSVGP_PG_LAUNCH(DT_, C_)                                                                                                \
+    hipLaunchKernelGGL((kgrad_prod_kernel<T, DT_, C_, (C_ * DT_ * sizeof(T) >= 256 ? 1 : 2)>), grid, dim3(NTHREADS), 0, st, X, Z, inv_ls, kk, variance, U, ldu, g0, g1, \
+                       gstride, beta, bstride, N, M, D, zpart, lpart, vpart, Mp)
+#define TSVGP_PG_C(DT_)                          \
+    switch (C) {                                 \
+        case 1: TSVGP_PG_LAUNCH(DT_, 1); break;  \
+        case 2: TSVGP_PG_LAUNCH(DT_, 2); break;  \
+        case 3: TSVGP_PG_LAUNCH(DT_, 3); break;  \
+        default: TSVGP_PG_LAUNCH(DT_, 4); break; \
+    }
+    switch (DT) {
+        case 1: TSVGP_PG_C(1) break;
+        case 2: TSVGP_PG_C(2) break;
+        case 4: TSVGP_PG_C(4) break;
+        case 8: TSVGP_PG_C(8) break;
+        default: TSVGP_PG_C(16) break;
+    }
+#undef TSVGP_PG_C
+#undef TSVGP_PG_LAUNCH
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+
+int tsvgp_kernel_grad_prod_f64(const int* kinds_host, const double* X, const double* Z, const double* inv_ls, double variance,
+                               const double* U, int64_t ldu, const double* g0, const double* g1, int gstride,
+                               const double* beta, int bstride, int64_t N, int M, int D, int C, double* zpart, double* lpart,
+                               double* vpart, void* stream) {
+    return kernel_grad_prod<double>(kinds_host, X, Z, inv_ls, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, D, C, zpart,
+                                    lpart, vpart, stream);
+}
+int tsvgp_kernel_grad_prod_f32(const int* kinds_host, const float* X, const float* Z, const float* inv_ls, float variance,
+                               const float* U, int64_t ldu, const float* g0, const float* g1, int gstride, const float* beta,
+                               int bstride, int64_t N, int M, int D, int C, double* zpart, double* lpart, double* vpart,
+                               void* stream) {
+    return kernel_grad_prod<float>(kinds_host, X, Z, inv_ls, variance, U, ldu, g0, g1, gstride, beta, bstride, N, M, D, C, zpart,
+                                   lpart, vpart, stream);
+}
 
 // vpart: one double per workgroup = ceil(Mp / 512) * Np of them (tsvgp_gram_to_gradw_parts)
 int64_t tsvgp_gram_to_gradw_parts(int64_t N, int M) {

@@ -23,6 +23,15 @@
 //                                 tile is 128 KB at most) -- one reload per 8 rows of arithmetic on them.
 // The kind of a component is uniform over the launch: a scalar branch per (row chunk, component) picks the profile.  The
 // per-component scalars (kind, variance) travel as kernel arguments in a by-value struct, like FillBatch.
+//
+// The same kernel fills a PRODUCT of stationary kernels (gpflow.kernels.Product, tsvgp_kernel_fill_prod_*) under the compile-time
+// flag PROD:
+//
+//     K[n, m] = variance * prod_c k_{kind[c]}(r_c)         variance = prod_c variance[c], formed on the host (args.variance[0])
+//
+// The accumulator starts at 1, "acc *= k" stands where the variance-weighted fma of the sum stands, and the variance multiplies
+// last (a zero for a column >= M, as in the sum).  Geometry, staging and both register forms are shared; with PROD = false every
+// `if constexpr (PROD)` below drops out and the instantiation is the sum's own.
 
 #include <hip/hip_runtime.h>
 
@@ -69,6 +78,18 @@ struct SfVec<float, 4> {
 };
 
 // acc[r][q] += variance * k_KIND(s[r][q]) on the pairs of R rows
+// acc[r][q] *= k_KIND(s[r][q]) on the pairs of R rows (PROD)
+template <int KIND, typename T, int R, int NP>
+__device__ __forceinline__ void sf_profile_mul(typename SfPair<T>::type (&acc)[R][NP], const typename SfPair<T>::type (&s)[R][NP]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            acc[r][q][0] = acc[r][q][0] * kernel_profile<KIND>(s[r][q][0]);
+            acc[r][q][1] = acc[r][q][1] * kernel_profile<KIND>(s[r][q][1]);
+        }
+}
+
 template <int KIND, typename T, int R, int NP>
 __device__ __forceinline__ void sf_profile_add(typename SfPair<T>::type (&acc)[R][NP], const typename SfPair<T>::type (&s)[R][NP],
                                                const typename SfPair<T>::type (&varc)[NP]) {
@@ -81,7 +102,7 @@ __device__ __forceinline__ void sf_profile_add(typename SfPair<T>::type (&acc)[R
         }
 }
 
-template <typename T, int DT, int CPT, int CH>
+template <typename T, int DT, int CPT, int CH, bool PROD>
 __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict__ X, const T* __restrict__ Z,
                                                             const T* __restrict__ inv_ls, SumFillArgs<T> args,
                                                             T* __restrict__ K, int64_t N, int M, int D, int64_t ldk,
@@ -140,7 +161,7 @@ __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict_
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int q = 0; q < NP; ++q) acc[r][q] = pair_t{T(0), T(0)};
+            for (int q = 0; q < NP; ++q) acc[r][q] = PROD ? pair_t{T(1), T(1)} : pair_t{T(0), T(0)};
         if (r0 < nvalid) {
             auto component = [&](int c, int k) {
                 pair_t s[R][NP];
@@ -162,6 +183,13 @@ __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict_
                         }
                     }
                 }
+                const int kind = args.kind[c];  // uniform over the launch
+                if constexpr (PROD) {
+                    if (kind == TSVGP_KERNEL_SE) sf_profile_mul<TSVGP_KERNEL_SE, T, R, NP>(acc, s);
+                    else if (kind == TSVGP_KERNEL_MATERN32) sf_profile_mul<TSVGP_KERNEL_MATERN32, T, R, NP>(acc, s);
+                    else sf_profile_mul<TSVGP_KERNEL_MATERN52, T, R, NP>(acc, s);
+                    return;
+                }
                 const T variance = args.variance[c];
                 pair_t varc[NP];
 #pragma unroll
@@ -169,7 +197,6 @@ __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict_
                     varc[q][0] = (m + 2 * q < M) ? variance : T(0);
                     varc[q][1] = (m + 2 * q + 1 < M) ? variance : T(0);
                 }
-                const int kind = args.kind[c];  // uniform over the launch
                 if (kind == TSVGP_KERNEL_SE) sf_profile_add<TSVGP_KERNEL_SE, T, R, NP>(acc, s, varc);
                 else if (kind == TSVGP_KERNEL_MATERN32) sf_profile_add<TSVGP_KERNEL_MATERN32, T, R, NP>(acc, s, varc);
                 else sf_profile_add<TSVGP_KERNEL_MATERN52, T, R, NP>(acc, s, varc);
@@ -182,6 +209,14 @@ __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict_
                 for (int c = 0; c < C; ++c) {
                     load_z(c, 0);
                     component(c, 0);
+                }
+            }
+            if constexpr (PROD) {  // the variance last; a column >= M (computed on zero Z columns: finite) takes a zero
+#pragma unroll
+                for (int q = 0; q < NP; ++q) {
+                    const pair_t varc = {(m + 2 * q < M) ? args.variance[0] : T(0), (m + 2 * q + 1 < M) ? args.variance[0] : T(0)};
+#pragma unroll
+                    for (int r = 0; r < R; ++r) acc[r][q] = acc[r][q] * varc;
                 }
             }
         }
@@ -203,7 +238,8 @@ __global__ __launch_bounds__(NTHREADS) void sum_fill_kernel(const T* __restrict_
     }
 }
 
-template <typename T>
+// variance: [C] for the sum, the one product of the components' variances for PROD
+template <typename T, bool PROD>
 int sum_fill(const int* kinds, const T* X, const T* Z, const T* inv_ls, const T* variance, T* K, int64_t N, int M, int D,
              int64_t ldk, int C, void* stream) {
     if (!kinds || !X || !Z || !inv_ls || !variance || !K || N <= 0 || M <= 0 || D <= 0 || C < 1 || C > TSVGP_MAX_COMPONENTS)
@@ -213,7 +249,7 @@ int sum_fill(const int* kinds, const T* X, const T* Z, const T* inv_ls, const T*
         if (kinds[c] != TSVGP_KERNEL_SE && kinds[c] != TSVGP_KERNEL_MATERN32 && kinds[c] != TSVGP_KERNEL_MATERN52)
             return TSVGP_EINVAL;
         args.kind[c] = kinds[c];
-        args.variance[c] = variance[c];
+        args.variance[c] = PROD ? variance[0] : variance[c];
     }
     const int64_t rows_pad = (N + TILE - 1) / TILE * TILE;
     const int cols_pad = (M + TILE - 1) / TILE * TILE;
@@ -233,7 +269,7 @@ int sum_fill(const int* kinds, const T* X, const T* Z, const T* inv_ls, const T*
     const int stream_out = (double)rows_pad * (double)ldk * sizeof(T) >= 512.0 * 1024 * 1024 ? 1 : 0;
     const int CH = C * DT <= 32 ? C : 0;  // all components' Z columns in registers, or a reload per row chunk
 #define TSVGP_SF_LAUNCH(DT_, CPT_, CH_)                                                                                      \
-    hipLaunchKernelGGL((sum_fill_kernel<T, DT_, CPT_, CH_>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, X, Z, inv_ls,    \
+    hipLaunchKernelGGL((sum_fill_kernel<T, DT_, CPT_, CH_, PROD>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, X, Z, inv_ls,    \
                        args, K, N, M, D, ldk, cols_pad, stream_out, rows_blk, C)
 #define TSVGP_SF_CPT(DT_, CH_)                            \
     do {                                                  \
@@ -280,12 +316,21 @@ extern "C" {
 int tsvgp_kernel_fill_sum_f64(const int* kinds_host, const double* X, const double* Z, const double* inv_ls,
                               const double* variance_host, double* K, int64_t N, int M, int D, int64_t ldk, int C,
                               void* stream) {
-    return sum_fill<double>(kinds_host, X, Z, inv_ls, variance_host, K, N, M, D, ldk, C, stream);
+    return sum_fill<double, false>(kinds_host, X, Z, inv_ls, variance_host, K, N, M, D, ldk, C, stream);
 }
 int tsvgp_kernel_fill_sum_f32(const int* kinds_host, const float* X, const float* Z, const float* inv_ls,
                               const float* variance_host, float* K, int64_t N, int M, int D, int64_t ldk, int C,
                               void* stream) {
-    return sum_fill<float>(kinds_host, X, Z, inv_ls, variance_host, K, N, M, D, ldk, C, stream);
+    return sum_fill<float, false>(kinds_host, X, Z, inv_ls, variance_host, K, N, M, D, ldk, C, stream);
+}
+
+int tsvgp_kernel_fill_prod_f64(const int* kinds_host, const double* X, const double* Z, const double* inv_ls, double variance,
+                               double* K, int64_t N, int M, int D, int64_t ldk, int C, void* stream) {
+    return sum_fill<double, true>(kinds_host, X, Z, inv_ls, &variance, K, N, M, D, ldk, C, stream);
+}
+int tsvgp_kernel_fill_prod_f32(const int* kinds_host, const float* X, const float* Z, const float* inv_ls, float variance,
+                               float* K, int64_t N, int M, int D, int64_t ldk, int C, void* stream) {
+    return sum_fill<float, true>(kinds_host, X, Z, inv_ls, &variance, K, N, M, D, ldk, C, stream);
 }
 
 }  // extern "C"

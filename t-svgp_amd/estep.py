@@ -42,7 +42,7 @@ import torch
 
 from . import _backend as B
 from .distributed import world_size
-from .kernels import LinearCoregionalization, SeparateIndependent, Sum
+from .kernels import COMBINED, LinearCoregionalization, Product, SeparateIndependent, Sum, refuse_product
 from .side_branch import SideBranch, SideStream
 
 MAX_INPUT_DIM = 32  # the fill kernel pads D to a compile-time size (1, 2, 4, 8, 16, 32)
@@ -348,17 +348,38 @@ class EStepEngine:
                                     out.stride(0), C, self._stream()))
         return out
 
+    def prod_fill(self, X: torch.Tensor, Z: torch.Tensor, kernel: Product, out: torch.Tensor):
+        """out[Np x Mp] <- prod_c K_c(X, Z) (padding zero) for a ``Product`` kernel: one launch of ``tsvgp_kernel_fill_prod_*``."""
+        N, D = X.shape
+        M = Z.shape[0]
+        if D > MAX_INPUT_DIM:
+            raise NotImplementedError(f"a Product kernel takes at most {MAX_INPUT_DIM} input columns (the fused fill's compile-time "
+                                      f"sizes; the GEMM form is per component), got D = {D}")
+        C = len(kernel.kernels)
+        inv_ls = kernel.inv_lengthscales(D, X.dtype, self.device)  # [C, D]
+        kinds = (ctypes.c_int * C)(*kernel.kinds)
+        var = kernel.prior_variance()
+        fn = self._fn("tsvgp_kernel_fill_prod", X.dtype)
+        with torch.cuda.device(self.device):
+            self._launch("tsvgp_se_fill" if N != M or X.data_ptr() != Z.data_ptr() else "tsvgp_se_fill(Kuu)",
+                         lambda: fn(kinds, X.data_ptr(), Z.data_ptr(), inv_ls.data_ptr(), var, out.data_ptr(), N, M, D,
+                                    out.stride(0), C, self._stream()))
+        return out
+
     def fill(self, X: torch.Tensor, Z: torch.Tensor, kernel, out: torch.Tensor):
         """out[Np x Mp] <- K(X, Z) (padding zero) of ONE latent GP's kernel: a stationary kernel through ``se_fill``, a ``Sum``
-        through ``sum_fill``.  X, Z and out share one dtype."""
+        through ``sum_fill``, a ``Product`` through ``prod_fill``.  X, Z and out share one dtype."""
+        if isinstance(kernel, Product):
+            return self.prod_fill(X, Z, kernel, out)
         if isinstance(kernel, Sum):
             return self.sum_fill(X, Z, kernel, out)
         return self.se_fill(X, Z, kernel.inv_lengthscales(X.shape[1], X.dtype, self.device), kernel.variance.item(), out, kernel.kind)
 
     @staticmethod
     def kdiag(kernel) -> float:
-        """The prior variance k(x, x) of ONE latent GP's kernel as a Python float: ``variance``, or its sum over a ``Sum``."""
-        return kernel.prior_variance() if isinstance(kernel, Sum) else kernel.variance.item()
+        """The prior variance k(x, x) of ONE latent GP's kernel as a Python float: ``variance``, its sum over a ``Sum``, its
+        product over a ``Product``."""
+        return kernel.prior_variance() if isinstance(kernel, COMBINED) else kernel.variance.item()
 
     def kuu(self, Z: torch.Tensor, kernel) -> torch.Tensor:
         """K(Z, Z) in fp64, [M, M] (no jitter); [P, M, M] for separate per-latent kernels."""
@@ -865,6 +886,46 @@ class EStepEngine:
                 vpart.data_ptr(), self._stream()))
         return vpart.sum(), lpart.sum(dim=(0, 1))[:D], zpart.sum(dim=0)[:M, :D]
 
+    def kernel_grad_prod(self, X, Z, kernel, U, g0, g1, beta):
+        """``kernel_grad`` for a ``Product`` kernel: all C parameter sets in ONE ``tsvgp_kernel_grad_prod_*`` launch on U.
+        Returns (d_variance [C], d_lengthscales [C, D], d_Z [M, D]) in fp64; d / d variance_c = (prod variance / variance_c) * the
+        launch's sum of V prod_c f_c."""
+        T, dev = self.dtype, self.device
+        X = X.to(device=dev, dtype=T).contiguous()
+        Z = Z.to(device=dev, dtype=T).contiguous()
+        N, D = X.shape
+        M = Z.shape[0]
+        if D > MAX_INPUT_DIM_GRAD:
+            raise NotImplementedError(f"the M-step gradient of a Product kernel takes at most {MAX_INPUT_DIM_GRAD} input columns "
+                                      f"(tsvgp_kernel_grad_prod_*'s compile-time sizes; the GEMM form is per kernel), got D = {D}")
+        C = len(kernel.kernels)
+        Mp = B.round_up(M)
+        inv_ls = kernel.inv_lengthscales(D, T, dev)  # [C, D]
+        kinds = (ctypes.c_int * C)(*kernel.kinds)
+        variances = kernel.variances()
+        var = kernel.prior_variance()
+        rows, Dp = int(self.lib.tsvgp_kernel_grad_rows()), int(self.lib.tsvgp_kernel_grad_dpad(D))
+        nrb, ncb = (N + rows - 1) // rows, (Mp + 511) // 512
+        zpart = torch.empty((nrb, Mp, Dp), dtype=torch.float64, device=dev)
+        lpart = torch.empty((nrb, ncb, C, Dp), dtype=torch.float64, device=dev)
+        vpart = torch.empty((nrb, ncb), dtype=torch.float64, device=dev)
+        bt = beta.to(device=dev, dtype=T).contiguous()
+        assert g0.dim() == 1 and g1.dim() == 1 and g0.stride(0) == g1.stride(0)
+        with torch.cuda.device(dev):
+            self._launch("tsvgp_kernel_grad", lambda: self._fn("tsvgp_kernel_grad_prod")(
+                kinds, X.data_ptr(), Z.data_ptr(), inv_ls.data_ptr(), var, U.data_ptr(), U.shape[1], g0.data_ptr(), g1.data_ptr(),
+                g0.stride(0), bt.data_ptr(), 1, N, M, D, C, zpart.data_ptr(), lpart.data_ptr(), vpart.data_ptr(), self._stream()))
+        # variance / variance_c without a division: the product of the others, in index order
+        others = []
+        for c in range(C):
+            o = 1.0
+            for c2, v in enumerate(variances):
+                if c2 != c:
+                    o *= v
+            others.append(o)
+        dvar = vpart.sum() * torch.tensor(others, dtype=torch.float64, device=dev)
+        return dvar, lpart.sum(dim=(0, 1))[:, :D], zpart.sum(dim=0)[:M, :D]
+
     def _kernel_grad_gemm(self, X, Z, kernel, U, g0, g1, beta):
         """``kernel_grad`` for D beyond the fused kernel's sizes, in the GEMM form of the large-D fill (reference
         docs/notebooks/mnist.py:117-192, D = 784): G = x~ z~^T from the BLAS library, ``tsvgp_gram_to_gradw_*`` turns it into
@@ -943,6 +1004,14 @@ class EStepEngine:
         Per kernel one K(X, Z) fill, per latent U = K_fu Q_p by the BLAS library into the engine's "U" buffer (the dense branch of
         ``t_SVGP.elbo_and_grads``, in the compute dtype) and one ``moments_vjp``, latents in index order.  The N-sized memory is
         the engine's reusable "Kfu" and "U" buffers."""
+        if isinstance(kernel, SeparateIndependent):
+            kernels = list(kernel.kernels)
+        elif isinstance(kernel, (list, tuple)):
+            kernels = list(kernel)
+        else:
+            kernels = [kernel]
+        for kern in kernels:  # before anything is moved or allocated
+            refuse_product(kern, "predict_f_vjp")
         T, dev = self.dtype, self.device
         X = X.detach().to(device=dev, dtype=T).contiguous()
         Z = Z.detach().to(device=dev, dtype=T).contiguous()
@@ -965,12 +1034,6 @@ class EStepEngine:
         if tuple(cm.shape) != (N, P) or (cv is not None and tuple(cv.shape) != (N, P)):
             raise ValueError(f"predict_vjp: the cotangents must be [N, P] = [{N}, {P}]")
         cv = torch.zeros_like(cm) if cv is None else cv.detach().to(device=dev, dtype=T).contiguous()
-        if isinstance(kernel, SeparateIndependent):
-            kernels = list(kernel.kernels)
-        elif isinstance(kernel, (list, tuple)):
-            kernels = list(kernel)
-        else:
-            kernels = [kernel]
         if len(kernels) not in (1, P):
             raise ValueError(f"predict_vjp: one kernel or one per latent (P = {P}), got {len(kernels)}")
         if len(kernels) == P and all(k is kernels[0] for k in kernels):
@@ -1585,8 +1648,8 @@ class EStepEngine:
             self.trmm(A, Tm, tile, moment_mode)
             mean[:, p] = torch.mv(A[:N], gam[:, p])  # gam: [Mp, P], rows >= M zero
             C = cov[p] if Cw is None else Cw
-            if D > MAX_INPUT_DIM or isinstance(kp, Sum):
-                # the GEMM form, or the fused fill of a Sum (the padding is zero: the call below sets it)
+            if D > MAX_INPUT_DIM or isinstance(kp, COMBINED):
+                # the GEMM form, or the fused fill of a Sum or a Product (the padding is zero: the call below sets it)
                 self.fill(X, X, kp, C)
                 base = dict(accumulate=True)
             else:

@@ -5,7 +5,9 @@ experiment on this path uses: reference tests/models/test_tsvgp.py:100, experime
 The N-sized evaluations K(X, Z) run in the HIP fill kernel (``tsvgp_se_fill_*``); nothing here loops over data.
 
 ``Sum`` (``k1 + k2``) adds up to four stationary components, each with its own variance, lengthscales and ``active_dims``;
-its K(X, Z) is one launch of ``tsvgp_kernel_fill_sum_*`` ("Sum kernels").
+its K(X, Z) is one launch of ``tsvgp_kernel_fill_sum_*`` ("Sum kernels").  ``Product`` (``k1 * k2``) multiplies them:
+one launch of ``tsvgp_kernel_fill_prod_*`` for K(X, Z), one of ``tsvgp_kernel_grad_prod_*`` for the M-step contraction of all
+components (DESIGN.md, "Product kernels").
 """
 from __future__ import annotations
 
@@ -39,6 +41,9 @@ class SquaredExponential:
 
     def __add__(self, other):
         return Sum([self, other])
+
+    def __mul__(self, other):
+        return Product([self, other])
 
     def stamp(self):
         """Cache key of the kernel's hyperparameters (identity + ``Parameter.stamp`` of each): what a carried-over K(X, Z), a
@@ -154,6 +159,9 @@ class Sum:
         if not flat:
             raise ValueError("Sum needs at least one component kernel")
         for k in flat:
+            if isinstance(k, Product):
+                raise NotImplementedError("a Sum of Product kernels is not implemented (the fused fill adds or multiplies "
+                                          "stationary components, not both)")
             if isinstance(k, SeparateIndependent):
                 raise ValueError(f"a Sum component must be a single-output stationary kernel, got the multi-output {type(k).__name__}")
             if not isinstance(k, SquaredExponential):
@@ -165,6 +173,10 @@ class Sum:
 
     def __add__(self, other):
         return Sum([self, other])
+
+    def __mul__(self, other):
+        raise NotImplementedError("Sum * kernel: a Product of a Sum kernel is not implemented (the fused fill adds or multiplies "
+                                  "stationary components, not both)")
 
     @property
     def kinds(self):
@@ -213,10 +225,83 @@ class Sum:
         return out
 
 
+class Product:
+    """``gpflow.kernels.Product`` [ext] of 1 to ``MAX_COMPONENTS`` stationary kernels (as the components of a ``Sum``):
+    k(x, z) = prod_c k_c(x, z), one latent GP.  k(x, x) = prod_c variance_c is a constant, so everything behind the fill takes it
+    unchanged; K(X, Z) is ONE launch of ``tsvgp_kernel_fill_prod_*`` and the M-step contraction of all components ONE launch of
+    ``tsvgp_kernel_grad_prod_*``.  The component bookkeeping (``kinds``, ``stamp``, ``variances``, ``inv_lengthscales`` and its
+    cache slots) is ``Sum``'s own; the two are siblings, so ``isinstance(k, Sum)`` never takes a product down a linear path."""
+
+    MAX_COMPONENTS = Sum.MAX_COMPONENTS
+    kinds = Sum.kinds
+    stamp = Sum.stamp
+    variances = Sum.variances
+    inv_lengthscales = Sum.inv_lengthscales
+
+    def __init__(self, kernels, name=None):
+        flat = []
+        for k in kernels:
+            flat.extend(k.kernels if isinstance(k, Product) else [k])
+        if not flat:
+            raise ValueError("Product needs at least one component kernel")
+        for k in flat:
+            if isinstance(k, SeparateIndependent):
+                raise ValueError(f"a Product component must be a single-output stationary kernel, got the multi-output {type(k).__name__}")
+            if isinstance(k, Sum):
+                raise NotImplementedError("a Product of a Sum kernel is not implemented (the fused fill adds or multiplies "
+                                          "stationary components, not both)")
+            if not isinstance(k, SquaredExponential):
+                raise ValueError(f"a Product component must be SquaredExponential, Matern32 or Matern52, got {type(k).__name__}")
+        if len(flat) > self.MAX_COMPONENTS:
+            raise ValueError(f"Product takes at most {self.MAX_COMPONENTS} components (TSVGP_MAX_COMPONENTS), got {len(flat)}")
+        self.kernels = flat
+        self.name = name or "product"
+
+    def __add__(self, other):
+        raise NotImplementedError("Product + kernel: a Sum of Product kernels is not implemented (the fused fill adds or multiplies "
+                                  "stationary components, not both)")
+
+    def __mul__(self, other):
+        return Product([self, other])
+
+    def prior_variance(self) -> float:
+        """k(x, x) = prod_c variance_c as a Python float (no device read), the components multiplied in index order."""
+        total = 1.0
+        for k in self.kernels:
+            total *= k.variance.item()
+        return total
+
+    def K_diag(self, X) -> torch.Tensor:
+        out = self.kernels[0].K_diag(X)
+        for k in self.kernels[1:]:
+            out = out * k.K_diag(X)
+        return out
+
+    def K_torch(self, Z: torch.Tensor, variances, lengthscales) -> torch.Tensor:
+        """K(Z, Z) as a differentiable torch expression of (Z, the components' variances and lengthscales: one entry per
+        component each), the components multiplied in index order."""
+        out = None
+        for k, v, ls in zip(self.kernels, variances, lengthscales):
+            Kc = k.K_torch(Z, v, ls)
+            out = Kc if out is None else out * Kc
+        return out
+
+
+COMBINED = (Sum, Product)  # one latent GP behind C stationary components: a constant k(x, x), one fused fill
+
+
 def refuse_sum(kernel, where: str):
-    """``NotImplementedError`` for a ``Sum`` kernel where only a single stationary kernel is implemented."""
+    """``NotImplementedError`` for a ``Sum`` or ``Product`` kernel where only a single stationary kernel is implemented."""
+    if isinstance(kernel, Product):
+        raise NotImplementedError(f"{where} does not take a Product kernel (a single SquaredExponential / Matern32 / Matern52 only)")
     if isinstance(kernel, Sum):
         raise NotImplementedError(f"{where} does not take a Sum kernel (a single SquaredExponential / Matern32 / Matern52 only)")
+
+
+def refuse_product(kernel, where: str):
+    """``NotImplementedError`` for a ``Product`` kernel where a ``Sum`` is taken but the product's own kernel is a later step."""
+    if isinstance(kernel, Product):
+        raise NotImplementedError(f"{where} does not take a Product kernel (it needs a kernel of its own, a later step)")
 
 
 class SeparateIndependent:

@@ -41,7 +41,7 @@ from ..base import default_device, default_float, default_jitter, to_tensor
 from ..estep import EStepStats, gaussian_g1_const, per_latent
 from ..side_branch import poll_current_stream
 from ..inducing_variables import inducingpoint_wrapper
-from ..kernels import LinearCoregionalization, SeparateIndependent, Sum, latent_kernels, refuse_sum
+from ..kernels import LinearCoregionalization, Product, SeparateIndependent, Sum, latent_kernels, refuse_product, refuse_sum
 from ..likelihoods import mapped_parameter
 from ..sites import DenseSites
 from ..util import (
@@ -284,6 +284,7 @@ class base_SVGP(abc.ABC):
         """Xnew on the device in fp64 through torch's own (differentiable) conversion when ``predict_f`` is to take part in
         autograd -- a tensor that requires grad, grad mode on -- else None."""
         if isinstance(Xnew, torch.Tensor) and Xnew.requires_grad and torch.is_grad_enabled():
+            refuse_product(self.kernel, "predict_f on an Xnew that requires grad")
             return Xnew.to(device=self.device, dtype=torch.float64)
         return None
 
@@ -295,6 +296,7 @@ class base_SVGP(abc.ABC):
         per latent (``EStepEngine.predict_vjp``); input dimension D <= 32.  ``predict_f`` itself takes part in torch autograd
         with respect to a Xnew that requires grad, and ``predict_y`` / ``predict_log_density`` with it."""
         self._refuse_lmc("predict_f_vjp")
+        refuse_product(self.kernel, "predict_f_vjp")
         X = Xnew if isinstance(Xnew, torch.Tensor) else torch.as_tensor(np.asarray(Xnew))
         X = X.detach().to(device=self.device, dtype=torch.float64)
         P = int(self.num_latent_gps)
@@ -503,7 +505,7 @@ class t_SVGP(base_SVGP):
     def _kernel_versions(self):
         # Parameter identity and the tensors' own edit counters ride along: a replaced Parameter restarts at version 0 and an
         # in-place edit of .value does not pass through assign()
-        # (a Sum's stamp covers every component's parameters)
+        # (a Sum's or a Product's stamp covers every component's parameters)
         return tuple(k.stamp() for k in latent_kernels(self.kernel, self.num_latent_gps))
 
     # Route gates on cond(K_uu + jitter I), per latent GP.  direct: K^-1 (sum g k k^T) K^-1 cancels two factors of K, so its
@@ -911,7 +913,8 @@ class t_SVGP(base_SVGP):
         own pass}), gradients of the ELBO
         with respect to the constrained parameter values; with one kernel per latent (``SeparateIndependent``) the kernel
         entries are named "kernels.<p>.variance" / "kernels.<p>.lengthscales"; with a ``Sum`` kernel, per component,
-        "components.<c>.variance" / "components.<c>.lengthscales" (one ``tsvgp_kernel_grad`` launch per component on the same U).  With ``LinearCoregionalization`` also "W" [P, L]:
+        "components.<c>.variance" / "components.<c>.lengthscales" (one ``tsvgp_kernel_grad`` launch per component on the same U), and
+        the same names with a ``Product`` kernel (ONE ``tsvgp_kernel_grad_prod`` launch per latent for all components; D <= 16).  With ``LinearCoregionalization`` also "W" [P, L]:
         with the sites fixed W enters through the mix alone, d ELBO / d W[p, l] = scale sum_n (g0_f[n, p] mean_g[n, l] +
         2 W[p, l] g1_f[n, p] var_g[n, l]), the block sums of the un-mix launch.  With more than one rank ``data`` is this
         rank's shard."""
@@ -927,7 +930,13 @@ class t_SVGP(base_SVGP):
         nk = len(kernels)
         # A Sum is ONE kernel for the N-pass (one fused fill) and C parameter sets for the gradient: the contraction is linear in
         # dK and V does not depend on the kernel, so every component takes its own tsvgp_kernel_grad launch on the same U
-        comps = list(self.kernel.kernels) if isinstance(self.kernel, Sum) else None
+        # A Product is one kernel for the N-pass as well, but dK / d theta_c carries the other components' values entry by entry:
+        # ONE tsvgp_kernel_grad_prod launch per latent returns all C parameter sets
+        prod = isinstance(self.kernel, Product)
+        comps = list(self.kernel.kernels) if isinstance(self.kernel, (Sum, Product)) else None
+        if prod and Dn > 16:
+            raise NotImplementedError(f"elbo_and_grads with a Product kernel takes at most 16 input columns (tsvgp_kernel_grad_prod_*'s "
+                                      f"compile-time sizes), got D = {Dn}")
         ng = nk if comps is None else len(comps)  # parameter sets (variance, lengthscales)
         Q = Dm.transpose(-1, -2) @ Dm  # [P, M, M]
         dvar = torch.zeros(ng, dtype=torch.float64, device=self.device)
@@ -973,24 +982,31 @@ class t_SVGP(base_SVGP):
             parts.append(st)
             Kfu, g0, g1 = eng._buf["Kfu"], eng._buf["g0"], eng._buf["g1"]  # [Np, Mp], [Np, len(lat)] (rows >= N are zero)
             Ubuf = eng._get("U", tuple(Kfu.shape), Kfu.dtype)
-            for c, p_ in enumerate(lat):
-                if tile_path:
-                    # U[n, m] = sum_{i <= m} t[n, i] D[i, m]: the lower-form product with D^T
-                    eng.trmm(st.tile, eng._pad_square(Dm[p_].transpose(-1, -2).contiguous(), Kfu.shape[1], "pad_Dt"), Ubuf, B.TRI_LOWER)
-                    for gi, kc in enumerate([kern] if comps is None else comps, 0 if comps is not None else ki):
-                        v, l, z = eng.kernel_grad(X, ops["Z"], kc, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
-                        dvar[gi] += v
-                        dls[gi] += l
-                        dZ += z
-                    continue
-                # U = K_fu Q_p: a plain dense GEMM, so it goes to the BLAS library (rocBLAS DGEMM holds 0.95 of the fp64 MFMA
-                # peak at this shape, tools/dgemm_ref.py: 28.1 ms at N = 1e6, M = 1024 against 33.8 for tsvgp_trmm's dense mode)
-                torch.mm(Kfu, eng._pad_square(0.5 * (Q[p_] + Q[p_].T), Kfu.shape[1], "pad_Q"), out=Ubuf)
+
+            def contract(c, p_, ki=ki, kern=kern, g0=g0, g1=g1):
+                """The N-sized contraction of latent p_ (column c of g0, g1) on the U in ``Ubuf``, added to dvar, dls, dZ."""
+                if prod:
+                    v, l, z = eng.kernel_grad_prod(X, ops["Z"], kern, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
+                    dvar.add_(v)
+                    dls.add_(l)
+                    dZ.add_(z)
+                    return
                 for gi, kc in enumerate([kern] if comps is None else comps, 0 if comps is not None else ki):
                     v, l, z = eng.kernel_grad(X, ops["Z"], kc, Ubuf, g0[:, c], g1[:, c], beta[:, p_])
                     dvar[gi] += v
                     dls[gi] += l
-                    dZ += z
+                    dZ.add_(z)
+
+            for c, p_ in enumerate(lat):
+                if tile_path:
+                    # U[n, m] = sum_{i <= m} t[n, i] D[i, m]: the lower-form product with D^T
+                    eng.trmm(st.tile, eng._pad_square(Dm[p_].transpose(-1, -2).contiguous(), Kfu.shape[1], "pad_Dt"), Ubuf, B.TRI_LOWER)
+                    contract(c, p_)
+                    continue
+                # U = K_fu Q_p: a plain dense GEMM, so it goes to the BLAS library (rocBLAS DGEMM holds 0.95 of the fp64 MFMA
+                # peak at this shape, tools/dgemm_ref.py: 28.1 ms at N = 1e6, M = 1024 against 33.8 for tsvgp_trmm's dense mode)
+                torch.mm(Kfu, eng._pad_square(0.5 * (Q[p_] + Q[p_].T), Kfu.shape[1], "pad_Q"), out=Ubuf)
+                contract(c, p_)
             sum_g1[ki] = g1.sum(dtype=torch.float64)
             if gaussian and not lmc:  # d ve / d s2 = -1/(2 s2) + ((y - m)^2 + v) / (2 s2^2), summed
                 res = res + torch.sum((Y[:, sl].to(st.mean.dtype) - st.mean) ** 2 + st.var)
@@ -1039,7 +1055,10 @@ class t_SVGP(base_SVGP):
             k_nn = lambda: sum(v_ * s_ for v_, s_ in zip(var_t, sum_g1))  # sum_np g1 * k(x, x), k(x, x) = variance
         else:
             k_torch = lambda: self.kernel.K_torch(Z_t, var_t, ls_t)[None]
-            k_nn = lambda: sum(var_t) * sum_g1[0]  # k(x, x) = sum_c variance_c
+            if prod:
+                k_nn = lambda: torch.stack(var_t).prod() * sum_g1[0]  # k(x, x) = prod_c variance_c
+            else:
+                k_nn = lambda: sum(var_t) * sum_g1[0]  # k(x, x) = sum_c variance_c
         Z_t = self._Z().detach().clone().requires_grad_(True)
         l1, L = self.lambda_1.value.detach(), self.lambda_2_sqrt.value.detach()
         Id = ops["Id"]

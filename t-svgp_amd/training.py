@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from .kernels import Sum
+from .kernels import COMBINED
 from .likelihoods import mapped_parameter
 
 
@@ -50,7 +50,7 @@ def trainable_parameters(model) -> dict:
     reference's M-step trains; the names are those of ``t_SVGP.elbo_and_grads`` ("kernels.<p>.variance" ... with one
     kernel per latent)."""
     kern = model.kernel
-    if isinstance(kern, Sum):  # one latent GP, C parameter sets
+    if isinstance(kern, COMBINED):  # a Sum or a Product: one latent GP, C parameter sets
         out = {}
         for c, k in enumerate(kern.kernels):
             out[f"components.{c}.variance"] = (k.variance, 0.0)
